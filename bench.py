@@ -7,7 +7,15 @@ source cloud, exact nearest-neighbour match against the target cloud, run the wh
 Huber/MAD Gauss-Newton loop, compose the pose.  Inputs are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0.
 
+A plain run times exactly --steps steps in one region and reports the headline alone.  --full adds
+everything else: the brute-force sweep, the weak-scaling, rotating-input and converging-pair lines, the
+kernels past the Infinity Cache, the HIP-event roofline of the search, the CPU baselines and the parity
+checks against the oracle, and five timed regions instead of one (value from the median).
+--dump-outputs DIR writes the last timed estimate() call's pose, inner-iteration counts and (one GPU)
+correspondence indices as DIR/*.npy (float64), for comparing two builds on the same seeded inputs.
+
   python bench.py --gpus 1 --steps 20 --warmup 2
+  python bench.py --gpus 1 --steps 20 --warmup 2 --full
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -26,6 +34,13 @@ FP64_VALU_PEAK_TFLOPS = 78.6   # MI355X vector FP64 (public spec; SURVEY.md 8(d)
 FP32_VALU_PEAK_TFLOPS = 157.3  # MI355X vector FP32 (MI355X_MICROARCH.md chip table)
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
 MAX_ITER = 20                  # outer iterations per estimate() call (both reference examples pass 20)
+# options of the lines beyond the headline: (default of a plain run, default with --full); a value given
+# on the command line holds either way
+LEG_DEFAULTS = {"brute_steps": (0, 3), "weak_steps": (0, 40), "cpu_iters": (0, 10), "converging_calls": (0, 3),
+                "repeats": (1, 5), "rotating_calls": (0, 9), "nn_points": (0, 16 * 1024 * 1024),
+                "gn_points": (0, 64 * 1024 * 1024)}
+WARM_MIN_S = 0.2               # one GPU: seconds of the timed call itself after the --warmup steps
+DUMP_MAX_ENTRIES = 1 << 21     # --dump-outputs: at most this many correspondences (16 MB as float64), else a seeded sample
 
 
 def parity_vs_oracle(tree, src, gpu, n_iter, blocks, threads, perm=None):
@@ -377,6 +392,23 @@ def reference_sized():
     return out
 
 
+def dump_outputs(d, res):
+    """--dump-outputs: what the last timed estimate() call returned, as float64 arrays: the pose (r00, r10, r01,
+    r11, tx, ty), the inner-iteration count of each of its outer iterations and (one GPU) the correspondence index
+    of every source point; above DUMP_MAX_ENTRIES points, those of a fixed seeded sample of source rows, whose
+    row numbers go to correspondence_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pose.npy"), res["T"].as_array().astype(np.float64))
+    np.save(os.path.join(d, "inner_iterations.npy"), np.asarray(res["last_inner"], dtype=np.float64))
+    idx = res["idx"]
+    if idx is not None:
+        if idx.size > DUMP_MAX_ENTRIES:
+            rows = np.sort(np.random.default_rng(0).choice(idx.size, DUMP_MAX_ENTRIES, replace=False))
+            np.save(os.path.join(d, "correspondence_rows.npy"), rows.astype(np.float64))
+            idx = idx[rows]
+        np.save(os.path.join(d, "correspondences.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -387,25 +419,34 @@ def main():
     ap.add_argument("--nn", choices=["auto", "brute", "grid"], default="auto",
                     help="NN engine of the headline value (auto = the library default: exact grid search "
                          "at this size); all engines return bit-identical correspondences")
-    ap.add_argument("--brute-steps", type=int, default=3,
-                    help="outer iterations of the brute-force sweep measured alongside (0 = skip)")
-    ap.add_argument("--weak-steps", type=int, default=40,
-                    help="N > 1: outer iterations of the weak-scaling line (N x n-src source points; 0 = skip)")
-    ap.add_argument("--cpu-iters", type=int, default=10,
-                    help="outer iterations of the CPU baseline: ~7 s on one core + ~3 s with all cores (0 = skip)")
-    ap.add_argument("--converging-calls", type=int, default=3,
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report every line beyond the headline (defaults below: plain run / --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed estimate() call returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--brute-steps", type=int,
+                    help="outer iterations of the brute-force sweep measured alongside (0 = skip; default 0 / 3)")
+    ap.add_argument("--weak-steps", type=int,
+                    help="N > 1: outer iterations of the weak-scaling line (N x n-src source points; 0 = skip; default 0 / 40)")
+    ap.add_argument("--cpu-iters", type=int,
+                    help="outer iterations of the CPU baseline: ~7 s on one core + ~3 s with all cores (0 = skip; default 0 / 10)")
+    ap.add_argument("--converging-calls", type=int,
                     help="estimate(20) calls on the CONVERGING 1M pair (src re-observes points of dst: inner loops of "
-                         "several updates, the regime of the reference's real scans) timed as a side line (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=5,
+                         "several updates, the regime of the reference's real scans) timed as a side line (0 = skip; default 0 / 3)")
+    ap.add_argument("--repeats", type=int,
                     help="the timed region of K steps is repeated this many times (each bracketed by barrier + synchronize); "
-                         "value = K / the MEDIAN region (a 3 ms region alone is +-3 % run to run)")
-    ap.add_argument("--rotating-calls", type=int, default=9,
-                    help="estimate(20) calls of the rotating-inputs side line: three different clouds / poses alternating (0 = skip)")
-    ap.add_argument("--nn-points", type=int, default=16 * 1024 * 1024,
-                    help="points of each cloud of the `nn_large` line: the search kernel past the Infinity Cache (0: skip)")
-    ap.add_argument("--gn-points", type=int, default=64 * 1024 * 1024,
-                    help="pairs of the separate 'reduce kernels alone, past the Infinity Cache' line (0 = skip)")
+                         "value = K / the MEDIAN region (a 3 ms region alone is +-3 %% run to run; default 1 / 5)")
+    ap.add_argument("--rotating-calls", type=int,
+                    help="estimate(20) calls of the rotating-inputs side line: three different clouds / poses alternating "
+                         "(0 = skip; default 0 / 9)")
+    ap.add_argument("--nn-points", type=int,
+                    help="points of each cloud of the `nn_large` line: the search kernel past the Infinity Cache "
+                         "(0 = skip; default 0 / 16M)")
+    ap.add_argument("--gn-points", type=int,
+                    help="pairs of the separate 'reduce kernels alone, past the Infinity Cache' line (0 = skip; default 0 / 64M)")
     args = ap.parse_args()
+    for name, (plain, full) in LEG_DEFAULTS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
 
     import torch
     import torch.distributed as dist
@@ -460,8 +501,10 @@ def main():
 
     loop_state = {"mode": None}
 
-    def measure(mode, steps, warmup, want_parity=False, weak=False, repeats=1):
+    def measure(mode, steps, warmup, want_parity=False, weak=False, repeats=1, want_idx=False, profile=True):
         """K timed outer iterations = one Icp3d::estimate(src, T, K) call on resident data.
+        profile: HIP events time the search launches (the roofline).  want_idx (one rank): the correspondence
+        indices of the last timed call, from the same call repeated after the timed regions.
         N ranks: the grid engine runs block-sharded (dist.BlockShardedIcp: every rank searches and
         evaluates the points of its reduction-tree blocks, two small exchanges per evaluation, same
         bits as one GPU); the sweep, whose search is 99.8 % of the step, keeps contiguous shards and a
@@ -475,6 +518,11 @@ def main():
             # evaluation that decides it); nothing else is enqueued on them
             if warmup > 0:
                 icp.estimate(d_src, T, warmup)
+            # ... then the timed call itself for WARM_MIN_S: the first ~20 ms of calls run ~3 % slower than the rest however
+            # many warm-up steps came before, and a plain run times one region
+            t_warm = time.perf_counter()
+            while time.perf_counter() - t_warm < WARM_MIN_S:
+                icp.estimate(d_src, I.Transform(), min(MAX_ITER, steps), return_info="inner")
         elif block:
             full = d_src_full
             if weak:
@@ -549,8 +597,9 @@ def main():
         # each 20-step estimate call then weighs exactly its 1-in-20 share, as in a rocprofv3 trace of
         # the same command); on longer runs around every 7th launch (an event pair costs a few us of
         # stream time; 7 is coprime with the 20-step cycle, so cold searches are sampled at their share)
-        icp.profile_enable(1 if steps <= 40 else 7)
-        icp.profile_read()
+        if profile:
+            icp.profile_enable(1 if steps <= 40 else 7)
+            icp.profile_read()
         regions, inner = [], []
         for _rep in range(max(repeats, 1)):
             barrier()
@@ -588,10 +637,20 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             regions = [float(x) for x in t.tolist()]
         elapsed = float(np.median(regions))
-        nn_ms, nn_launches = icp.profile_read()
+        # what the last timed estimate() call returned: its pose and its inner counts
+        last_k = (steps - 1) % MAX_ITER + 1
+        last_inner = inner[-last_k:]
+        idx = None
+        if world == 1 and want_idx:
+            # outside the timed region: the last call once more with the index buffer handed back; it must
+            # return the timed call's pose and inner counts bit for bit
+            Ti, idx, ki = icp.estimate(d_src, I.Transform(), last_k, return_info=True)
+            if Ti.as_array().tobytes() != T.as_array().tobytes() or [int(x) for x in ki] != last_inner:
+                raise SystemExit("bench.py: repeating the last timed call gave another pose or other inner counts")
+        nn_ms, nn_launches = icp.profile_read() if profile else (0.0, 0)
         icp.profile_enable(0)
         alone_ms = None
-        if world == 1 and steps >= 20:
+        if profile and world == 1 and steps >= 20:
             # outside the timed region: the same search kernel with nothing beside it (stage calls on one
             # stream: no speculative overlap), for comparison with the overlapped duration above
             solo = ShardedIcp(HipStages(icp), n, 0, 1)
@@ -618,7 +677,8 @@ def main():
             driver.disconnect_loop()  # (the peers' mappings go back before any rank pools its handle)
         icp.close()
         return dict(elapsed=elapsed, regions=regions, steps=steps, inner=inner, nn_ms=nn_ms, nn_launches=nn_launches, T=T,
-                    engine=engine, alone_ms=alone_ms, checked=checked, counters=counters, n_run=n_run)
+                    engine=engine, alone_ms=alone_ms, checked=checked, counters=counters, n_run=n_run,
+                    last_inner=last_inner, idx=idx)
 
     def nn_roofline(r, n_shard):
         """Roofline of the dominant kernel (the NN search) from the live HIP-event timing."""
@@ -660,7 +720,10 @@ def main():
                     "avg_launch_ms": r["alone_ms"], "achieved": nn_bytes / (1e-3 * r["alone_ms"]) / 1e9,
                     "frac": nn_bytes / (1e-3 * r["alone_ms"]) / 1e9 / HBM_PEAK_GBS}}
 
-    res = measure(nn_mode, args.steps, args.warmup, want_parity=args.cpu_iters > 0, repeats=args.repeats)
+    res = measure(nn_mode, args.steps, args.warmup, want_parity=args.cpu_iters > 0, repeats=args.repeats,
+                  want_idx=bool(args.dump_outputs) and rank == 0, profile=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     brute = None
     if args.brute_steps > 0 and res["engine"] != "brute":
         brute = measure(I.NN_BRUTE, args.brute_steps, 1, want_parity=args.cpu_iters > 0)
@@ -709,15 +772,16 @@ def main():
                                 "loop replicated"),
                 "seed": hex(synth.SEED),
             },
-            "roofline": nn_roofline(res, n_shard),
             "step_hbm": {"algorithmic_bytes_per_step": step_bytes,
                          "achieved_GBs": step_bytes / (elapsed / args.steps) / 1e9,
                          "frac_of_8TBs": step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS},
             "inner_iterations_per_step": inner,
-            "nn_share_of_step": (res["nn_ms"] / max(res["nn_launches"], 1)) / ms_per_step,
             "pose": T.as_array().tolist(),
             "pose_abs_err_vs_truth": float(np.max(np.abs(T.as_array() - truth))),
         }
+        if args.full:
+            out["roofline"] = nn_roofline(res, n_shard)
+            out["nn_share_of_step"] = (res["nn_ms"] / max(res["nn_launches"], 1)) / ms_per_step
         if res.get("counters"):
             out["sharded_evaluations"] = dict(res["counters"], inner_loops=loop_state["mode"], transport=loop_state.get("transport"),
                                               rccl_world=dist.get_world_size() if dist.is_initialized() else 1,

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(lib, extra_env=None):
     env = dict(os.environ, ICP_MI355X_LIB=os.path.abspath(lib), **(extra_env or {}))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "5", "--full",
                           "--brute-steps", "0", "--cpu-iters", "0", "--gn-points", "0"], env=env, capture_output=True,
                          text=True, timeout=600)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract_fields_and_is_consistent():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n-src", "120000", "--n-dst", "100000", "--steps", "20",
-                          "--warmup", "2", "--brute-steps", "1", "--cpu-iters", "1", "--gn-points", "0"],
+                          "--warmup", "2", "--full", "--brute-steps", "1", "--cpu-iters", "1", "--gn-points", "0"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -67,7 +67,7 @@ def test_two_rank_bench_lines_say_how_the_ranks_talked():
     env = dict(os.environ, ICP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n-src", "200000", "--n-dst",
-                          "150000", "--steps", "10", "--warmup", "2", "--brute-steps", "1", "--weak-steps", "5", "--cpu-iters", "0",
+                          "150000", "--steps", "10", "--warmup", "2", "--full", "--brute-steps", "1", "--weak-steps", "5", "--cpu-iters", "0",
                           "--gn-points", "0", "--nn-points", "0"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
@@ -81,3 +81,39 @@ def test_two_rank_bench_lines_say_how_the_ranks_talked():
         assert d[leg]["n_gpus"] == 2 and d[leg]["rccl_world"] == 2 and d[leg]["transport"] and d[leg]["scaling"] == scaling, leg
     if "parity" in d:
         assert d["parity"]["pose_bits_equal"] is True and d["parity"]["inner_iterations_equal"] is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_same_outputs_every_run(tmp_path):
+    """Without --full: one timed region of exactly --steps steps, the headline fields and none of the other lines.
+    --dump-outputs: the pose, inner counts and correspondences of the last timed call, the same bits run after run."""
+    import numpy as np
+
+    n_src, n_dst, steps = 120000, 100000, 25
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n-src", str(n_src), "--n-dst",
+                              str(n_dst), "--steps", str(steps), "--warmup", "2", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == steps and len(line["inner_iterations_per_step"]) == steps
+        assert line["timed_regions"]["repeats"] == 1
+        assert abs(line["value"] * line["ms_per_step"] / 1e3 - 1.0) < 1e-6
+        for key in ("roofline", "brute_force", "converging_pair", "rotating_inputs", "nn_large", "gn_large", "parity"):
+            assert key not in line, key
+        assert line["cpu_baseline"] is None
+        got = {f: np.load(d / f"{f}.npy") for f in ("pose", "inner_iterations", "correspondences")}
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert np.array_equal(got["pose"], np.array(line["pose"]))
+        assert got["inner_iterations"].tolist() == line["inner_iterations_per_step"][-(steps - 20):]  # the last call: 5 steps
+        c = got["correspondences"]
+        assert c.shape == (n_src,) and c.min() >= 0 and c.max() < n_dst and np.array_equal(c, np.round(c))
+        dumps.append(got)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
