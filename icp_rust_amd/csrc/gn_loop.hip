@@ -894,6 +894,7 @@ __global__ __launch_bounds__(kReduceThreads) void k_gn_loop_shard(LoopArgs A, Lo
   // (the flag words of the second wait and the prefix of their counts overlay the same workspace: they live between
   // phase B's last look at the cumulative counts and the first selection)
   unsigned long long *const s_seen = reinterpret_cast<unsigned long long *>(s_work), *const s_incl = s_seen + kReduceMaxBlocks;
+  static_assert(2 * kReduceMaxBlocks * sizeof(unsigned long long) <= sizeof(s_work), "s_seen and s_incl: a word each per workgroup");
   // (the members of the fine bins, staged by phase A behind the histograms: k_gn_loop has the explanation)
   constexpr unsigned kStageCap = (sizeof(s_work) - 2 * kWinBins * sizeof(uint32_t)) / sizeof(unsigned short);
   static_assert(kStageCap >= 4096 && kLoopMaxK <= 8, "staged members: 3 + 9 + 1 bits each");
@@ -1325,6 +1326,21 @@ __global__ __launch_bounds__(kReduceThreads) void k_gn_loop_shard(LoopArgs A, Lo
   }
 }
 
+// A launch is one tree of at most kReduceMaxBlocks workgroups: the flag words and block-sum rows below hold one per
+// workgroup, the polls gather them four per lane (flag_barrier, poll_words: s_seen, s_incl) and the folds take 256 rows
+// (fold_block_sums_256).  loop_slots() is 256 only because the MI355X has 256 CUs: the applies / launch functions check
+// the tree's size against kReduceMaxBlocks explicitly.
+static_assert(kReduceMaxBlocks == 4 * 64, "flag polls: four flag words per lane of one wave");
+static_assert(sizeof(LoopCtl::flag1) == kReduceMaxBlocks * sizeof(unsigned long long) &&
+                  sizeof(LoopCtl::flag2) == kReduceMaxBlocks * sizeof(unsigned long long),
+              "LoopCtl: a flag word per workgroup");
+static_assert(sizeof(LoopInbox::flag_block) == kReduceMaxBlocks * sizeof(unsigned long long) &&
+                  sizeof(LoopInbox::flag_cand) == kReduceMaxBlocks * sizeof(unsigned long long),
+              "LoopInbox: a flag word per workgroup");
+static_assert(sizeof(LoopInbox::partials[0]) == (size_t)kReduceMaxBlocks * (kNSum + 1) * sizeof(double) &&
+                  sizeof(LoopInbox::cand) / sizeof(LoopInbox::cand[0]) == kReduceMaxBlocks,
+              "LoopInbox: a block-sum row and a candidate row per workgroup");
+
 // Every workgroup of a launch must be running at once (they wait for each other): the device has to offer that many
 // slots for workgroups of this kernel with the most dynamic LDS a launch asks for.  Asked once per process (the current
 // device at the first call: the handles of a process live on devices of one kind).
@@ -1349,7 +1365,8 @@ bool gn_loop_applies(size_t n) {
   static const bool off = getenv("ICP_NO_GN_LOOP") != nullptr;
   int blocks, threads;
   reduce_geometry(n, &blocks, &threads);
-  return !off && n >= (size_t)(1u << 12) && n <= (size_t)kLoopMaxK * (size_t)blocks * (size_t)threads && blocks <= loop_slots();
+  return !off && n >= (size_t)(1u << 12) && n <= (size_t)kLoopMaxK * (size_t)blocks * (size_t)threads && blocks <= kReduceMaxBlocks &&
+         blocks <= loop_slots();
 }
 
 size_t gn_loop_partials_doubles() { return (size_t)2 * kReduceMaxBlocks * (kNSum + 1) + (size_t)2 * (kNSum + 1); }
@@ -1367,7 +1384,7 @@ hipError_t launch_gn_loop(icp_handle *h, const LoopArgs &args) {
     lds_granted = e == hipSuccess ? 1 : -1;
     if (e != hipSuccess) (void)hipGetLastError();
   }
-  if (lds_granted < 0 || K > (unsigned)kLoopMaxK) return hipErrorInvalidValue;
+  if (lds_granted < 0 || K > (unsigned)kLoopMaxK || blocks > kReduceMaxBlocks) return hipErrorInvalidValue;
   const size_t lds = (size_t)K * kReduceThreads * 2 * sizeof(double2);
   hipLaunchKernelGGL(k_gn_loop, dim3(blocks), dim3(threads), lds, h->stream, args, K);
   return hipGetLastError();
@@ -1380,7 +1397,7 @@ bool gn_loop_shard_applies(size_t n_total, int world) {
   // (ranks that share a device need all `blocks` slots on it; a rank with a device of its own needs fewer: the check is
   // the conservative one)
   return !off && world >= 1 && world <= kShardMaxWorld && blocks >= world && n_total >= (size_t)(1u << 12) &&
-         n_total <= (size_t)kLoopMaxK * (size_t)blocks * (size_t)threads && blocks <= loop_slots();
+         n_total <= (size_t)kLoopMaxK * (size_t)blocks * (size_t)threads && blocks <= kReduceMaxBlocks && blocks <= loop_slots();
 }
 
 hipError_t launch_gn_loop_shard(icp_handle *h, const LoopArgs &args, const LoopShardArgs &sh, const LoopRankPtrs &ptrs, int ranks) {
@@ -1398,7 +1415,8 @@ hipError_t launch_gn_loop_shard(icp_handle *h, const LoopArgs &args, const LoopS
   }
   int nb = 0;  // the widest of the ranks this launch carries
   for (int q = sh.rank; q < sh.rank + ranks; ++q) nb = std::max(nb, sh.first_block[q + 1] - sh.first_block[q]);
-  if (lds_granted < 0 || K > (unsigned)kLoopMaxK || nb < 1 || ranks < 1 || sh.rank + ranks > sh.world || sh.blocks_total != blocks)
+  if (lds_granted < 0 || K > (unsigned)kLoopMaxK || blocks > kReduceMaxBlocks || nb < 1 || ranks < 1 || sh.rank + ranks > sh.world ||
+      sh.blocks_total != blocks)
     return hipErrorInvalidValue;
   const size_t lds = (size_t)K * kReduceThreads * 2 * sizeof(double2);
   hipLaunchKernelGGL(k_gn_loop_shard, dim3(nb, ranks), dim3(threads), lds, h->stream, args, sh, ptrs, K);

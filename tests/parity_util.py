@@ -33,3 +33,131 @@ def check_fold_order(perm, cell):
         assert np.all(np.diff(c) >= 0)
         same = np.diff(c) == 0
         assert np.all(np.diff(perm)[same] > 0)
+
+
+def apply_pose(T, pts):
+    """Transform::transform (src/transform.rs:22-24) of many points at once, as the oracle does it for one:
+    (r00 x + r01 y) + tx, with no fused multiply-add (numpy evaluates each product and sum on its own).  `T`: an
+    oracle pose or a Transform."""
+    p = getattr(T, "pose", T)
+    x, y = pts[:, 0], pts[:, 1]
+    return np.stack([(p.r00 * x + p.r01 * y) + p.tx, (p.r10 * x + p.r11 * y) + p.ty], axis=1)
+
+
+def oracle_loop(a, b):
+    """estimate_transform (src/lib.rs:59-84) with every sum folded in the tree of icp_reduce_geometry: the device's
+    bits.  Returns (oracle pose, updates applied)."""
+    blocks, threads = I.reduce_geometry(len(a))
+    T = O.transform_identity()
+    prev, applied = np.finfo(np.float64).max, 0
+    if len(a) >= 2:
+        for _ in range(200):
+            rc, delta, err = O.weighted_gauss_newton_update_tree(T, a, b, blocks, threads)
+            if rc != O.OK:
+                break
+            if (delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < 1e-6:
+                break
+            if err > prev:
+                break
+            prev = err
+            T = O.transform_mul(O.transform_new(delta), T)
+            applied += 1
+    return T, applied
+
+
+def gn_large_pairs(n, seed, heavy=False):
+    """Pairs shaped like bench.py's gn_large line, drawn on the host: a uniform in [-40, 40)^2, b = a rotated by
+    0.015 rad and moved by (0.3, -0.2), plus N(0, 0.05^2) noise.  `heavy`: 10 % of b are outliers thrown
+    N(0, 5^2) around an offset of (4, -2.5), which also pulls the residuals' medians away from zero."""
+    rng = np.random.default_rng(seed)
+    a = (rng.random((n, 2)) - 0.5) * 80.0
+    c, s = np.cos(0.015), np.sin(0.015)
+    b = np.empty_like(a)
+    b[:, 0] = c * a[:, 0] - s * a[:, 1] + 0.3
+    b[:, 1] = s * a[:, 0] + c * a[:, 1] - 0.2
+    b += rng.normal(size=(n, 2)) * 0.05
+    if heavy:
+        k = rng.choice(n, size=n // 10, replace=False)
+        b[k] += rng.normal(size=(len(k), 2)) * 5.0 + np.array([4.0, -2.5])
+    return a, b
+
+
+PPF34 = 1.482602218505602  # 1 / PPF(0.75), src/stats.rs:41
+HUBER_K = 1.345            # src/lib.rs:32
+
+
+def _median_f64(v):
+    """stats::mutable_median (src/stats.rs:11-28): the middle order statistic, or the mean (b + c) / 2 of the two
+    middle ones, rounded once in f64.  Order statistics are exact, whichever algorithm finds them."""
+    n = len(v)
+    if n % 2 == 1:
+        return np.partition(v, n // 2)[n // 2]
+    p = np.partition(v, (n // 2 - 1, n // 2))
+    return (p[n // 2 - 1] + p[n // 2]) / 2.0
+
+
+def reference_stddevs(a, b):
+    """The residuals (r00 x + r01 y) + tx - d at the IDENTITY pose (= a - b exactly) and stats::calc_stddevs
+    (src/stats.rs:30-60) of them: PPF34 * median(|r - median(r)|) per dimension, all in f64 as the reference
+    rounds it.  Returns (residuals, stddevs)."""
+    r = a - b
+    sd = np.empty(2)
+    for j in range(2):
+        col = np.ascontiguousarray(r[:, j])
+        m = _median_f64(col)
+        sd[j] = PPF34 * _median_f64(np.abs(col - m))
+    return r, sd
+
+
+def reference_wgn_update_identity(a, b, skeel=False):
+    """weighted_gauss_newton_update (src/lib.rs:218-261) at the identity pose, written from the reference's
+    definition: the residuals and the four medians exactly in f64 (reference_stddevs), then the Huber weights
+    (src/huber.rs: drho(e, k) = 1 for e <= k^2, else k / sqrt(e)), the sums of w g J^T J and w g J^T r and the
+    3 x 3 solve -H^-1 g in np.longdouble.  At the identity J_x = (1, 0, -y), J_y = (0, 1, x).
+    Returns (delta as longdouble[3], stddevs as f64[2]); with `skeel`, also the Skeel condition number
+    || |H^-1| (|H|_abs |delta| + |g|_abs) ||_inf / ||delta||_inf of the solve, where |.|_abs are the sums of the
+    terms' magnitudes: a relative perturbation eps of every term moves delta by at most eps times it."""
+    L = np.longdouble
+    r, sd = reference_stddevs(a, b)
+    ax, ay = a[:, 0].astype(L), a[:, 1].astype(L)
+    H = np.zeros((3, 3), dtype=L)
+    g = np.zeros(3, dtype=L)
+    Habs = np.zeros((3, 3), dtype=L)
+    gabs = np.zeros(3, dtype=L)
+    k = L(HUBER_K)
+    for j in range(2):
+        if sd[j] == 0.0:
+            continue
+        rj = r[:, j].astype(L)
+        e = rj * rj
+        w = np.where(e <= k * k, L(1), k / np.sqrt(np.maximum(e, k * k)))
+        wg = w / L(sd[j])
+        J = (L(1), L(0), -ay) if j == 0 else (L(0), L(1), ax)
+        for p in range(3):
+            wJp = wg * J[p]
+            g[p] += np.sum(wJp * rj)
+            if skeel:
+                gabs[p] += np.sum(np.abs(wJp * rj))
+            for q in range(p, 3):
+                H[p, q] += np.sum(wJp * J[q])
+                H[q, p] = H[p, q]
+                if skeel:
+                    Habs[p, q] += np.sum(np.abs(wJp * J[q]))
+                    Habs[q, p] = Habs[p, q]
+    delta = -_solve3_longdouble(H, g)
+    if not skeel:
+        return delta, sd
+    Hinv = np.stack([_solve3_longdouble(H, e) for e in np.eye(3, dtype=L)], axis=1)
+    cond = np.max(np.abs(Hinv) @ (Habs @ np.abs(delta) + gabs)) / np.max(np.abs(delta))
+    return delta, sd, float(cond)
+
+
+def _solve3_longdouble(H, g):
+    """H^-1 g by the adjugate (numpy's solvers do not take longdouble)"""
+    c = np.empty((3, 3), dtype=H.dtype)
+    for i in range(3):
+        for j in range(3):
+            m = np.delete(np.delete(H, i, 0), j, 1)
+            c[i, j] = (-1) ** (i + j) * (m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0])
+    det = np.sum(H[0] * c[0])
+    return (c.T @ g) / det

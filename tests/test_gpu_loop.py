@@ -8,6 +8,7 @@ import pytest
 import icp_rust_amd as I
 import oracle_ffi as O
 from icp_rust_amd import _lib
+from parity_util import apply_pose, oracle_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -16,31 +17,11 @@ def pairs(n, seed, spread=0.05, scale=20.0, param=(0.4, -0.3, 0.02), outliers=Tr
     rng = np.random.default_rng(seed)
     a = rng.normal(size=(n, 2)) * scale
     Tt = O.transform_new(np.array(param))
-    b = O.transform_apply_many(Tt, a) + rng.normal(size=(n, 2)) * spread
+    b = apply_pose(Tt, a) + rng.normal(size=(n, 2)) * spread
     if outliers:
         k = rng.integers(0, n, size=n // 10)
         b[k] += rng.normal(size=(len(k), 2)) * 5
     return np.ascontiguousarray(a), np.ascontiguousarray(b)
-
-
-def oracle_loop(a, b):
-    """estimate_transform with every sum folded in the tree of icp_reduce_geometry: the device's bits"""
-    blocks, threads = I.reduce_geometry(len(a))
-    T = O.transform_identity()
-    prev, applied = np.finfo(np.float64).max, 0
-    if len(a) >= 2:
-        for _ in range(200):
-            rc, delta, err = O.weighted_gauss_newton_update_tree(T, a, b, blocks, threads)
-            if rc != O.OK:
-                break
-            if (delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < 1e-6:
-                break
-            if err > prev:
-                break
-            prev = err
-            T = O.transform_mul(O.transform_new(delta), T)
-            applied += 1
-    return T, applied
 
 
 def run(a, b):
@@ -51,8 +32,9 @@ def run(a, b):
 
 
 # 4 096: the smallest launch (8 workgroups, one point per thread); 131 072 / 131 073: one / two points per thread;
-# 2^20: eight per thread, the largest launch; 2^20 + 1: beyond it (stepped from the host)
-@pytest.mark.parametrize("n", [4_096, 5_001, 131_072, 131_073, 300_000, 524_289, 1_048_576, 1_048_577])
+# 2^20: eight per thread, the largest launch; 2^20 + 1: beyond it (stepped from the host); 2^23 + 1 and 2^24: a tree of
+# kTreeMaxBlocks blocks whose threads fold nine and sixteen pairs -- far more blocks than the launch's 256 slots
+@pytest.mark.parametrize("n", [4_096, 5_001, 131_072, 131_073, 300_000, 524_289, 1_048_576, 1_048_577, 8_388_609, 16_777_216])
 def test_one_launch_inner_loop_equals_the_tree_oracle(n):
     a, b = pairs(n, n)
     I.estimate_transform(a, b)  # (whatever ran: the scratch handle now has window predictions for every kind)

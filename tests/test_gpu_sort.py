@@ -54,3 +54,39 @@ def test_sort_on_hostile_keys(shape):
     ko, po = _sort(keys, bits)
     want = np.argsort(keys, kind="stable").astype(np.uint32)
     assert np.array_equal(po, want) and np.array_equal(ko, keys[want])
+
+
+# The sizes the benchmark's large lines sort (nn_large: 2^24 points) and beyond: 1 024 tiles of 16 384 keys, one more
+# key (a last tile of one), and 2 049 tiles -- 33 chunks of 64 tile rows in the row sums, against the 3 the sizes above
+# reach.  Kept out of the grid above: three bit widths each (one 11-bit digit pass and more, the full key).
+@pytest.mark.parametrize("n", [16_777_216, 16_777_217, 33_554_433])
+@pytest.mark.parametrize("bits", [21, 23, 32])
+def test_sort_at_the_benchmarks_sizes(n, bits):
+    rng = np.random.default_rng(n * 131 + bits)
+    keys = rng.integers(0, 1 << bits, size=n, dtype=np.uint64).astype(np.uint32)
+    ko, po = _sort(keys, bits)
+    want = np.argsort(keys, kind="stable").astype(np.uint32)
+    assert np.array_equal(po, want)
+    assert np.array_equal(ko, keys[want])
+
+
+def test_sort_at_its_capacity():
+    """exactly 8 192 tiles (134 217 728 keys): the most the two levels of row sums take"""
+    n, bits = 134_217_728, 32
+    keys = np.random.default_rng(8192).integers(0, 1 << bits, size=n, dtype=np.uint64).astype(np.uint32)
+    ko, po = _sort(keys, bits)
+    want = np.argsort(keys, kind="stable").astype(np.uint32)
+    assert np.array_equal(po, want)
+    del want
+    assert np.array_equal(ko, keys[po])
+
+
+def test_sort_beyond_its_capacity_is_refused():
+    """one key past 8 192 tiles: a status, and nothing written -- no partial order handed back"""
+    n = 134_217_729
+    keys = np.random.default_rng(8193).integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+    ko = np.full(n, 0xA5A5A5A5, dtype=np.uint32)
+    po = np.full(n, 0x5A5A5A5A, dtype=np.uint32)
+    rc = I.lib().icp_debug_sort_cells(C.c_void_p(keys.ctypes.data), n, 32, C.c_void_p(ko.ctypes.data), C.c_void_p(po.ctypes.data))
+    assert rc != 0
+    assert np.all(po == 0x5A5A5A5A) and np.all(ko == 0xA5A5A5A5)
