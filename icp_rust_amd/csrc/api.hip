@@ -166,10 +166,8 @@ hipError_t ensure_workspace(icp_handle *h, size_t n, bool need_src) {
     if ((e = alloc_ctx(w.alt, h->stream)) != hipSuccess) return e;
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    // ICP_EVAL_PRIORITY=low|normal: A/B switch for the evaluation stream's priority (default: highest)
-    int prio = prio_greatest;
-    if (const char *pe = exp_env("ICP_EVAL_PRIORITY")) prio = pe[0] == 'l' ? prio_least : (pe[0] == 'n' ? 0 : prio_greatest);
-    if ((e = hipStreamCreateWithPriority(&w.spec_stream, hipStreamNonBlocking, prio)) != hipSuccess) return e;
+    // the evaluation stream runs at the highest priority
+    if ((e = hipStreamCreateWithPriority(&w.spec_stream, hipStreamNonBlocking, prio_greatest)) != hipSuccess) return e;
     if ((e = hipMalloc(&w.d_ahead, sizeof(AheadPose))) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.d_ahead, 0, sizeof(AheadPose), h->stream)) != hipSuccess) return e;
     // the memsets above must have landed before either stream uses the scratch
@@ -446,12 +444,6 @@ extern "C" void icp_destroy(icp_handle *h) {
     }
     v->clear();
   }
-  if (exp_env("ICP_DBG_WIN") && h->ws.win_tried)
-    fprintf(stderr,
-            "[icp] window evaluations: %llu tried, %llu missed; speculative searches: %llu hit, %llu missed; "
-            "first evaluations launched ahead: %llu; refined windows (n > 4M): %llu tried, %llu missed\n",
-            h->ws.win_tried, h->ws.win_missed, h->ws.spec_hits, h->ws.spec_misses, h->ws.pre_evals,
-            h->ws.refine_tried, h->ws.refine_missed);
   static const bool no_pool = getenv("ICP_NO_POOL") != nullptr;
   if (!no_pool) {
     // back to the state of a fresh handle, buffers kept (everything logical is reset here; the
@@ -479,12 +471,11 @@ extern "C" void icp_destroy(icp_handle *h) {
     h->shard.refined_ready = h->shard.attempt_refined = false;
     h->normals_m = 0;
     h->normals_k = 0;
-    static const bool no_hints = exp_env("ICP_NO_POOL_HINTS") != nullptr;
     for (int k = 0; k < 5; ++k) {  // what the next owner may start from (common.hpp: hint_kind)
-      w.hint_kind[k] = no_hints ? Workspace::WinPred() : w.win_kind[k];
+      w.hint_kind[k] = w.win_kind[k];
       w.hint_kind[k].wide = false;
     }
-    w.hint_last_inner = no_hints ? 0xffffffffu : w.last_inner;
+    w.hint_last_inner = w.last_inner;
     w.win_valid = w.win_wide = false;
     for (auto &wk : w.win_kind) wk = Workspace::WinPred();
     // whatever the previous owner's last evaluations left in the selection scratch (a parked flag, a
@@ -492,7 +483,7 @@ extern "C" void icp_destroy(icp_handle *h) {
     // scratch at its first use
     w.gn_dirty = w.alt.gn_dirty = true;
     w.win_tried = w.win_missed = w.short_evals = w.radix_evals = 0;
-    w.spec_hits = w.spec_misses = w.pre_evals = 0;
+    w.spec_hits = w.spec_misses = 0;
     w.ahead_hits = w.ahead_misses = 0;
     w.ahead_on = w.ahead_seen_valid = false;
     w.loop_launches = w.loop_evals = w.loop_handbacks = 0;
@@ -500,7 +491,6 @@ extern "C" void icp_destroy(icp_handle *h) {
     w.loop_rank = -1;
     w.loop_world = 0;
     w.tiny_calls = w.tiny_evals = w.tiny_sorted = 0;
-    w.refine_tried = w.refine_missed = 0;
     w.last_inner = 0xffffffffu;
     std::lock_guard<std::mutex> lk(g_pool_mu);
     if (g_pool.size() < kPoolMax) {
@@ -529,11 +519,12 @@ extern "C" int icp_set_nn_mode(icp_handle *h, int mode) {
 
 // AUTO: the grid pays off once the target cloud is large enough to amortise the
 // scattered cell reads; tiny clouds (2-D LiDAR scans, ~650 points) stay on the sweep.
+static constexpr long kGridMinM = 8192;
+
 int icp::api::resolved_nn_mode(const icp_handle *h) {
-  static const long grid_min_m = exp_env("ICP_NN_GRID_MIN_M") ? atol(exp_env("ICP_NN_GRID_MIN_M")) : 8192;
   if (h->nn_mode == ICP_NN_BRUTE || !h->grid.built) return ICP_NN_BRUTE;
   if (h->nn_mode == ICP_NN_GRID) return ICP_NN_GRID;
-  return (long)h->m >= grid_min_m ? ICP_NN_GRID : ICP_NN_BRUTE;
+  return (long)h->m >= kGridMinM ? ICP_NN_GRID : ICP_NN_BRUTE;
 }
 
 static hipError_t launch_nn(icp_handle *h, const double *d_src, size_t n, const Pose *T, double *d_a,
@@ -634,11 +625,13 @@ extern "C" int icp_materialize_pairs_device(icp_handle *h, const double *d_src, 
   return ICP_OK;
 }
 
+// clouds smaller than this are searched in the caller's order: no snapshot
+static constexpr long kQsortMinN = 16384;
+
 extern "C" int icp_prepare_source_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T) {
   if (!h || !T || (n > 0 && !d_src) || n >= 0xffffffffull) return ICP_BAD_ARGUMENT;
   h->qsort.valid = false;
-  static const long min_n = exp_env("ICP_QSORT_MIN_N") ? atol(exp_env("ICP_QSORT_MIN_N")) : 16384;
-  if (resolved_nn_mode(h) != ICP_NN_GRID || (long)n < min_n) return ICP_OK;
+  if (resolved_nn_mode(h) != ICP_NN_GRID || (long)n < kQsortMinN) return ICP_OK;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(prepare_queries(h, d_src, n, *T));
   return ICP_OK;
@@ -654,7 +647,7 @@ __global__ void k_iota_u32(uint32_t *p, unsigned n) {
 // The fold order of an estimate call that starts at pose T (icp_last_fold_order), applied: d_sorted[k] =
 // d_src[perm[k]].  For hosts that drive the stage calls themselves (the sharded drivers) and want the bits of
 // icp_estimate_device: sort first, then treat the sorted cloud as the source.  Where icp_estimate_device would
-// take no snapshot or keeps the caller's order (sweep engine; up to grid_coop_max() = 65 536 points, ICP_NN_COOP_MAX_N) this
+// take no snapshot or keeps the caller's order (sweep engine; up to kGridCoopMaxN = 65 536 points) this
 // is a plain copy and the identity permutation.
 extern "C" int icp_sort_source_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T,
                                       double *d_sorted, uint32_t *d_perm) {
@@ -662,7 +655,7 @@ extern "C" int icp_sort_source_device(icp_handle *h, const double *d_src, size_t
   if (n == 0) return ICP_OK;
   HIP_TRY(hipSetDevice(h->device));
   bool sorted = false;
-  if ((long)n > grid_coop_max()) {  // exactly where icp_estimate_device folds in snapshot order
+  if ((long)n > kGridCoopMaxN) {  // exactly where icp_estimate_device folds in snapshot order
     const int prc = icp_prepare_source_device(h, d_src, n, T);
     if (prc != ICP_OK) return prc;
     sorted = h->qsort.valid && h->qsort.src == d_src && h->qsort.n == n;
@@ -705,16 +698,13 @@ static inline void cpu_relax() {
 #endif
 }
 hipError_t icp::api::wait_seq(icp_handle *h, volatile unsigned *seq, unsigned want, hipStream_t stream) {
-  static const bool no_poll = exp_env("ICP_NO_POLL") != nullptr;
-  if (!no_poll) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      for (int spins = 0; spins < 256; ++spins) {
-        if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) return hipSuccess;
-        cpu_relax();
-      }
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(250)) break;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (;;) {
+    for (int spins = 0; spins < 256; ++spins) {
+      if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) return hipSuccess;
+      cpu_relax();
     }
+    if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(250)) break;
   }
   return hipStreamSynchronize(stream ? stream : h->stream);
 }
@@ -769,7 +759,6 @@ template <typename Hook>
 static int wgn_step(icp_handle *h, const double *d_a, const double *d_b, size_t n, const Pose &T,
                     double delta[3], double *huber_err, Hook &&after_launch, bool pre_launched = false,
                     int kind = 2) {
-  static const bool force_radix = exp_env("ICP_GN_RADIX") != nullptr;
   Range range("icp: evaluation (weighted_gauss_newton_update + huber_error)");
   Workspace &w = h->ws;
   bool done = false, has_median = false, hooked = false;
@@ -787,87 +776,75 @@ static int wgn_step(icp_handle *h, const double *d_a, const double *d_b, size_t 
     HIP_TRY(launch_sel_init(h, n));
     w.gn_dirty = false;
   }
-  if (!force_radix) {
-    WinParams P;
-    if (pre_launched || w.bkt_pair_launched || window_usable(h, n, &P, kind)) {  // launches around the predicted median and sigma
-      if (!pre_launched && w.bkt_pair_launched) {
-        // this evaluation went out on the search stream, side by side with the next iteration's first evaluation
-        // (launch_bkt_pair): only its result is awaited
-        w.bkt_pair_launched = false;
-        on_stream = h->own_stream;
-        HIP_TRY(after_launch());
-        hooked = true;
-      } else if (!pre_launched) {
-        ++w.win_tried;
-        HIP_TRY(launch_weighted_gn_win(h, d_a, d_b, n, T, P));
-        HIP_TRY(after_launch());
-        hooked = true;
-      }
-#ifdef ICP_EXPERIMENTS
-      const auto tw0 = std::chrono::steady_clock::now();
-#endif
-      HIP_TRY(wait_result(h, on_stream));
-#ifdef ICP_EXPERIMENTS
-      (pre_launched ? w.dbg_wait_pre_us : w.dbg_wait_other_us) +=
-          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw0).count();
-#endif
-      done = has_median = !w.h_res->overflow;
-      if (pre_launched) {  // (the run-ahead search behind it read the same pose from the device)
-        w.ahead_seen_valid = w.h_res->next_valid != 0;
-        w.ahead_seen_pose = w.h_res->next_pose;
-      }
-      if (!done && w.h_res->overflow == 3) {  // the buckets were too small, not the window wrong: no wider windows,
-        ++w.bkt_misses;                       // the next evaluations of this handle take the second pass instead
-        w.bkt_off = 64;
-      } else if (!done) {
-        if (exp_env("ICP_WIN_TRACE")) fprintf(stderr, "[win] kind %d: the window missed\n", kind);
-        ++w.win_missed;
-        wide = true;
-      } else if (wide) {  // back to narrow windows once the statistics have settled
-        double shift = 0.;
-        for (int d = 0; d < 2; ++d)
-          shift = fmax(shift, (fabs(w.h_res->median[d] - p_med[d]) + fabs(w.h_res->sigma[d] - p_sigma[d])) / p_sigma[d]);
-        if (shift < 0.01) wide = false;
-      }
+  WinParams P;
+  if (pre_launched || w.bkt_pair_launched || window_usable(h, n, &P, kind)) {  // launches around the predicted median and sigma
+    if (!pre_launched && w.bkt_pair_launched) {
+      // this evaluation went out on the search stream, side by side with the next iteration's first evaluation
+      // (launch_bkt_pair): only its result is awaited
+      w.bkt_pair_launched = false;
+      on_stream = h->own_stream;
+      HIP_TRY(after_launch());
+      hooked = true;
+    } else if (!pre_launched) {
+      ++w.win_tried;
+      HIP_TRY(launch_weighted_gn_win(h, d_a, d_b, n, T, P));
+      HIP_TRY(after_launch());
+      hooked = true;
     }
-    if (!done && refine_applies(n)) {
-      // beyond 4M points: windows refined in two passes (gn_win.hip).  The exact statistics of a
-      // strided 1M-pair sample centre the first pass ...
-      ++w.refine_tried;
-      HIP_TRY(launch_sample_pairs(h, d_a, d_b, n));
-      HIP_TRY(launch_weighted_gn_pull(h, w.d_sa, w.d_sb, kRefineSample, T));
-      HIP_TRY(wait_result(h));
-      WinParams P1, P2;
-      bool ok = !w.h_res->overflow && !w.h_res->nan_flag;
-      if (ok) {
-        const double m[2] = {w.h_res->median[0], w.h_res->median[1]}, sg[2] = {w.h_res->sigma[0], w.h_res->sigma[1]};
-        ok = make_window(m, sg, 0.02, &P1);
-      }
-      if (ok) {  // ... whose counts place the windows of the second
-        HIP_TRY(launch_win_first_pass(h, d_a, d_b, n, T, P1));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        ok = refine_window(w.h_whist, n, P1, &P2);
-      }
-      if (ok) {
-        ++w.win_tried;
-        HIP_TRY(launch_win_second_pass(h, d_a, n, T, P2));
-        if (!hooked) HIP_TRY(after_launch());
-        hooked = true;
-        HIP_TRY(wait_result(h));
-        done = has_median = !w.h_res->overflow;
-        if (!done) ++w.win_missed;
-      }
-      if (!done) ++w.refine_missed;
+    HIP_TRY(wait_result(h, on_stream));
+    done = has_median = !w.h_res->overflow;
+    if (pre_launched) {  // (the run-ahead search behind it read the same pose from the device)
+      w.ahead_seen_valid = w.h_res->next_valid != 0;
+      w.ahead_seen_pose = w.h_res->next_pose;
     }
-    if (!done) {
-      ++w.short_evals;
-      HIP_TRY(launch_weighted_gn_fast(h, d_a, d_b, n, T));
+    if (!done && w.h_res->overflow == 3) {  // the buckets were too small, not the window wrong: no wider windows,
+      ++w.bkt_misses;                       // the next evaluations of this handle take the second pass instead
+      w.bkt_off = 64;
+    } else if (!done) {
+      ++w.win_missed;
+      wide = true;
+    } else if (wide) {  // back to narrow windows once the statistics have settled
+      double shift = 0.;
+      for (int d = 0; d < 2; ++d)
+        shift = fmax(shift, (fabs(w.h_res->median[d] - p_med[d]) + fabs(w.h_res->sigma[d] - p_sigma[d])) / p_sigma[d]);
+      if (shift < 0.01) wide = false;
+    }
+  }
+  if (!done && refine_applies(n)) {
+    // beyond 4M points: windows refined in two passes (gn_win.hip).  The exact statistics of a
+    // strided 1M-pair sample centre the first pass ...
+    HIP_TRY(launch_sample_pairs(h, d_a, d_b, n));
+    HIP_TRY(launch_weighted_gn_pull(h, w.d_sa, w.d_sb, kRefineSample, T));
+    HIP_TRY(wait_result(h));
+    WinParams P1, P2;
+    bool ok = !w.h_res->overflow && !w.h_res->nan_flag;
+    if (ok) {
+      const double m[2] = {w.h_res->median[0], w.h_res->median[1]}, sg[2] = {w.h_res->sigma[0], w.h_res->sigma[1]};
+      ok = make_window(m, sg, 0.02, &P1);
+    }
+    if (ok) {  // ... whose counts place the windows of the second
+      HIP_TRY(launch_win_first_pass(h, d_a, d_b, n, T, P1));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      ok = refine_window(w.h_whist, n, P1, &P2);
+    }
+    if (ok) {
+      ++w.win_tried;
+      HIP_TRY(launch_win_second_pass(h, d_a, n, T, P2));
       if (!hooked) HIP_TRY(after_launch());
       hooked = true;
       HIP_TRY(wait_result(h));
-      done = !w.h_res->overflow;
-      has_median = done && n > 1024;  // gn_pull.hip reports the median, the single-workgroup kernel does not
+      done = has_median = !w.h_res->overflow;
+      if (!done) ++w.win_missed;
     }
+  }
+  if (!done) {
+    ++w.short_evals;
+    HIP_TRY(launch_weighted_gn_fast(h, d_a, d_b, n, T));
+    if (!hooked) HIP_TRY(after_launch());
+    hooked = true;
+    HIP_TRY(wait_result(h));
+    done = !w.h_res->overflow;
+    has_median = done && n > 1024;  // gn_pull.hip reports the median, the single-workgroup kernel does not
   }
   if (!done) {  // heavy duplicates around a median: the general 6-pass radix select
     ++w.radix_evals;
@@ -878,11 +855,6 @@ static int wgn_step(icp_handle *h, const double *d_a, const double *d_b, size_t 
     w.gn_dirty = true;
   }
   const GnResult &r = *w.h_res;
-  static const bool win_trace = exp_env("ICP_WIN_TRACE") != nullptr;
-  if (win_trace)
-    fprintf(stderr, "[win] kind %d own %d predicted med %.6g %.6g sigma %.6g %.6g -> med %.6g %.6g sigma %.6g %.6g%s\n", kind,
-            (int)own, p_med[0], p_med[1], p_sigma[0], p_sigma[1], r.median[0], r.median[1], r.sigma[0], r.sigma[1],
-            has_median ? "" : " (no statistics)");
   record_statistics(w, kind, has_median, r);
   if (r.nan_flag) {
     w.gn_dirty = true;
@@ -1117,18 +1089,6 @@ static int estimate_transform_loop(icp_handle *h, const double *d_a, const doubl
         h->stream = eval_stream;
         h->ws.swap_ctx();
       }
-#ifdef ICP_EXPERIMENTS
-      // (timing experiment only: what an outer iteration costs WITHOUT its deciding evaluation -- the loop is taken to end
-      // after one update, as it does on the benchmark pair)
-      if (it == 1 && exp_env("ICP_HACK_SKIP_E2")) {
-        (void)second_eval_hook(T);
-        if (on_eval_stream) {
-          h->stream = first_stream;
-          h->ws.swap_ctx();
-        }
-        break;
-      }
-#endif
       if (it == 1 && hook_first) {
         const hipError_t he = second_eval_hook(T);
         if (he != hipSuccess) {
@@ -1224,8 +1184,6 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
     if (tiny_status == 3) return ICP_NAN_INPUT;
   }
   static const bool no_spec = getenv("ICP_NO_SPECULATION") != nullptr;
-  static const bool one_stream_env = exp_env("ICP_SPEC_SAME_STREAM") != nullptr;
-  static const bool nn_first = exp_env("ICP_SPEC_NN_LAST") == nullptr;
   Workspace &w = h->ws;
   // Two ways through an outer iteration, chosen per iteration from how the previous inner loop went:
   //  * it applied exactly ONE update (a settled registration; the benchmark pair): the host steps the two evaluations
@@ -1234,7 +1192,7 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
   //    wait, however many updates the loop applies; no bet.
   const bool loop_ok = gn_loop_applies(n);
   // with a caller-supplied stream everything stays on that stream
-  const bool two_streams = !no_spec && !one_stream_env && h->stream == h->own_stream;
+  const bool two_streams = !no_spec && h->stream == h->own_stream;
   Pose T = *init;
   if (max_iter > 0) {
     const int prc = icp_prepare_source_device(h, d_src, n, init);
@@ -1246,7 +1204,7 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
   // reproduce the sums), and only the indices of the last search go back to the caller's order.
   // (clouds small enough for the four-lanes-per-query search keep the caller's order: their scatter is cheap,
   // and frame-sized registrations stay comparable with stage-call drivers point for point)
-  const bool slot = h->qsort.valid && h->qsort.src == d_src && h->qsort.n == n && (long)n > grid_coop_max();
+  const bool slot = h->qsort.valid && h->qsort.src == d_src && h->qsort.n == n && (long)n > kGridCoopMaxN;
   h->qsort.slot_order = slot;
   if (slot) h->qsort.fold_n = n;
   uint32_t *const idx_target = slot ? w.d_idx_slot : d_last_idx;
@@ -1257,11 +1215,9 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
   // after it is enqueued at once, with its pose read from the device (k_win_finish solves the update there) -- the
   // search stream then runs search -> evaluation -> search -> ... without waiting for the host between them.  The
   // host still derives every pose itself and takes the pairs only if the device's pose has the same bits.
-  static const bool no_ahead = exp_env("ICP_NO_RUN_AHEAD") != nullptr;  // (ICP_NO_SPECULATION switches it off with the bet: no second stream)
-  const bool can_ahead = two_streams && !no_ahead && resolved_nn_mode(h) == ICP_NN_GRID;
+  // (ICP_NO_SPECULATION switches it off with the bet: no second stream)
+  const bool can_ahead = two_streams && resolved_nn_mode(h) == ICP_NN_GRID;
   bool ahead_issued = false;  // an ahead search into the buffers after next is in flight behind the current pre-evaluation
-  static const bool no_pre = exp_env("ICP_NO_PRE_EVAL") != nullptr;
-  static const bool pair_evals = !(exp_env("ICP_PAIR_EVALS") && atoi(exp_env("ICP_PAIR_EVALS")) == 0);
   bool hooked_first = false;  // this iteration's hook runs in front of the deciding evaluation's launches
   Pose spec_pose = T;
   // the bet needs "the inner loop took exactly one update last time"; across calls the handle
@@ -1302,7 +1258,7 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
       if (ahead_issued && (have_search || w.ahead_seen_valid)) ++(have_search ? w.ahead_hits : w.ahead_misses);
       ahead_issued = false;
       if (!have_search) e = launch_nn(h, d_src, n, &spec_pose, A[nxt], B[nxt], idx_out);
-      if (e == hipSuccess && two_streams && !no_pre) {
+      if (e == hipSuccess && two_streams) {
         // ... and the next iteration's FIRST evaluation (inner pose = identity) right behind it,
         // in the search stream's own evaluation scratch: if the bet holds, its result is waiting
         // when the host gets there
@@ -1314,7 +1270,6 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
         }
         if (e == hipSuccess && window_usable(h, n, &P, 0)) {
           ++w.win_tried;
-          ++w.pre_evals;
           const bool go_ahead = can_ahead && it + 2 < max_iter;
           // Round 5: where both evaluations can file their candidates, the launch that FINISHES this pre-launched one
           // (one workgroup, a serial chain the next search waits for) also carries the first launch of the DECIDING
@@ -1324,7 +1279,7 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
           // launch done (wgn_step: bkt_pair_launched).
           WinParams P2;
           const int kind2 = it == 0 ? 4 : 1;
-          bool pair = pair_evals && hooked_first && w.bkt_off == 0 && !w.alt.gn_dirty && !w.alt.bkt_pair_launched && bkt_fits(n, P);
+          bool pair = hooked_first && w.bkt_off == 0 && !w.alt.gn_dirty && !w.alt.bkt_pair_launched && bkt_fits(n, P);
           if (pair) {
             adopt_pool_hint(w, kind2);  // (estimate_transform_loop would, in front of that evaluation)
             pair = window_usable(h, n, &P2, kind2) && bkt_fits(n, P2);
@@ -1354,16 +1309,14 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
     uint32_t inner = 0;
     // two streams: the search is enqueued first; the evaluation's workgroups arrive on the
     // high-priority stream and are placed as soon as a CU has room
-    w.search_beside_eval = speculate;
     // (the hook -- next search / pre-evaluation / run-ahead search -- goes in front of the deciding evaluation's launches
     // unless the next search is in flight already and the cloud is frame-sized: there the host's launches are the
     // critical path)
-    hooked_first = two_streams && nn_first && !device_loop && !(ahead_issued && (long)n <= grid_coop_max());
+    hooked_first = two_streams && !device_loop && !(ahead_issued && (long)n <= kGridCoopMaxN);
     const int rc = estimate_transform_loop(h, A[cur], B[cur], n, &dT, &inner, hook,
                                            two_streams && !device_loop ? w.spec_stream : nullptr, hooked_first,
                                            first_pre_launched, it == 0 ? 3 : 0,
                                            it == 0 ? 4 : 1, device_loop);
-    w.search_beside_eval = false;
     if (rc != ICP_OK) return rc;
     if (inner_iters) inner_iters[it] = inner;
     prev_inner = inner;
@@ -1382,13 +1335,6 @@ extern "C" int icp_estimate_device(icp_handle *h, const double *d_src, size_t n,
     }
     T = T_next;
   }
-#ifdef ICP_EXPERIMENTS
-  if (exp_env("ICP_STEP_TRACE")) {
-    fprintf(stderr, "[step trace] %zu iterations: waiting for pre-launched first evaluations %.1f us, for other evaluations %.1f us\n",
-            max_iter, w.dbg_wait_pre_us, w.dbg_wait_other_us);
-    w.dbg_wait_pre_us = w.dbg_wait_other_us = 0.;
-  }
-#endif
   if (slot && d_last_idx && max_iter > 0 && n > 0) HIP_TRY(launch_unpermute_idx(h, w.d_idx_slot, n, d_last_idx));
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (two_streams) HIP_TRY(hipStreamSynchronize(w.spec_stream));

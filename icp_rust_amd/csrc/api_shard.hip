@@ -22,7 +22,6 @@ using namespace icp::api;
 
 namespace icp {
 __global__ void k_iota_u32(uint32_t *p, unsigned n);  // (api.hip)
-long grid_coop_max();
 }
 
 // ---- ... and over the ranks of a sharded registration (include/icp_mi355x.h section 5b) ---------------------------------
@@ -407,7 +406,7 @@ extern "C" int icp_shard_sort_take_device(icp_handle *h, const double *d_src_ful
   HIP_TRY(hipSetDevice(h->device));
   const unsigned words = (unsigned)(h->dim * 2);
   bool sorted = false;
-  if ((long)n_total > grid_coop_max() && resolved_nn_mode(h) == ICP_NN_GRID) {  // (exactly where icp_estimate_device folds in snapshot order)
+  if ((long)n_total > kGridCoopMaxN && resolved_nn_mode(h) == ICP_NN_GRID) {  // (exactly where icp_estimate_device folds in snapshot order)
     h->qsort.sort_only = true;
     const int prc = icp_prepare_source_device(h, d_src_full, n_total, T);
     sorted = prc == ICP_OK && !h->qsort.sort_only && h->qsort.src == d_src_full && h->qsort.n == n_total && !h->qsort.valid;

@@ -12,16 +12,10 @@
 
 namespace icp {
 
-// The product library reads FIVE environment variables -- ICP_NO_POOL (icp_destroy frees instead of pooling),
+// The library reads FIVE environment variables -- ICP_NO_POOL (icp_destroy frees instead of pooling),
 // ICP_NO_GN_LOOP (inner loops stepped from the host only), ICP_NO_SPECULATION (no bet on the next pose),
-// ICP_GN_NO_REFINE (no refined windows beyond 4M pairs), ICP_MULTI_DEBUG (icp_multi diagnostics on stderr).  Every
-// A/B switch and tuning knob of the development rounds exists only in a build with
-// -DICP_EXPERIMENTS (`make experiments` -> libicp_mi355x_exp.so), where exp_env is getenv; here it answers "unset".
-#ifdef ICP_EXPERIMENTS
-inline const char *exp_env(const char *name) { return getenv(name); }
-#else
-inline const char *exp_env(const char *) { return nullptr; }
-#endif
+// ICP_GN_NO_REFINE (no refined windows beyond 4M pairs), ICP_MULTI_DEBUG (icp_multi diagnostics on stderr)
+// (DESIGN.md section 10).  Every other choice of the development rounds is fixed at its measured best.
 
 // roctx ranges around the three device stages of an outer iteration (search, evaluation / inner
 // loop, solve), for `rocprofv3 --marker-trace`.  The marker library is looked up at run time (librocprofiler-sdk-roctx
@@ -214,11 +208,9 @@ struct Workspace : GnCtx {
   bool ahead_seen_valid = false;  // what the last pre-launched evaluation reported (GnResult::next_pose / next_valid)
   Pose ahead_seen_pose;
   unsigned long long ahead_hits = 0, ahead_misses = 0;
-  double dbg_wait_pre_us = 0., dbg_wait_other_us = 0.;  // experiments build: where the host of icp_estimate_device waits
-  unsigned long long spec_hits = 0, spec_misses = 0, pre_evals = 0;
+  unsigned long long spec_hits = 0, spec_misses = 0;
   uint32_t last_inner = 0xffffffffu;  // updates the inner loop applied in the last outer iteration of the previous call
   hipStream_t spec_stream = nullptr;  // later evaluations of an inner loop run beside the speculative search
-  bool search_beside_eval = false;    // this outer iteration bets on a speculative search: its deciding evaluation shares the CUs with it
   uint32_t *d_idx = nullptr;
   uint32_t *d_idx_slot = nullptr;  // the last search's indices in slot order (icp_estimate_device, QuerySort::slot_order)
   // refined windows (n > 4M, gn_win.hip): a strided sample of the pairs and a host copy of the histograms
@@ -228,7 +220,6 @@ struct Workspace : GnCtx {
   unsigned long long tiny_calls = 0, tiny_evals = 0, tiny_sorted = 0;
   double *d_rlist = nullptr;        // 2 x kRefineListCap: the residuals inside the second pass' fine windows
   unsigned *d_rlist_len = nullptr;  // [2]
-  unsigned long long refine_tried = 0, refine_missed = 0;
   // brute-force NN partial minima when the target range is split over blockIdx.y
   size_t cap_part = 0;
   double *d_part_d = nullptr;
@@ -358,7 +349,7 @@ struct QuerySort {
   // icp_estimate_device: the searches of this call emit a / b / idx in SLOT order (coalesced stores, no
   // scatter through `perm`) and the Gauss-Newton evaluations fold the pairs in that order
   bool slot_order = false;
-  bool identity = false;       // the snapshot keeps the caller's order (no sort: clouds of up to ICP_NN_COOP_MAX_N points)
+  bool identity = false;       // the snapshot keeps the caller's order (no sort: clouds of up to kGridCoopMaxN points)
   bool presorted = false;      // one-shot hint: the next snapshot's cloud is already in cell order (a rank's slice of a sorted cloud)
   bool sort_only = false;      // one-shot: the next prepare_queries only sorts (d_perm; no sorted copy, no snapshot): icp_shard_sort_take_device
   size_t fold_n = 0;           // > 0: d_perm / d_cell hold the fold order of the last estimate call on fold_n points
@@ -472,7 +463,8 @@ hipError_t build_grid(icp_handle *h);
 // size -- and the caller rebuilds)
 hipError_t append_grid(icp_handle *h, size_t m_old, size_t k, bool *done);
 hipError_t prepare_queries(icp_handle *h, const double *d_src, size_t n, const Pose &T);
-long grid_coop_max();
+// four lanes per query while one lane per query cannot fill the chip: the largest n that gets them
+constexpr long kGridCoopMaxN = 65536;
 hipError_t launch_unpermute_idx(icp_handle *h, const uint32_t *d_slot_idx, size_t n, uint32_t *d_out);
 hipError_t launch_nn_grid(icp_handle *h, const double *d_src, size_t n, const Pose *T, double *d_a,
                           double *d_b, uint32_t *d_idx);

@@ -276,10 +276,10 @@ __host__ __device__ __forceinline__ double combine_sum(const double *S, int k, c
 
 // src/lib.rs:238-255 (+ :45-50) over this thread's points g, g + G, ... in index order (the
 // first level of the fixed reduction tree); residuals come from the arrays the first launch wrote
-template <int kAccBatch = 4>
 __device__ __forceinline__ void accumulate_points(const double2 *__restrict__ a, const double *__restrict__ rx,
                                                   const double *__restrict__ ry, unsigned n, const Pose &T,
                                                   double (&acc)[kNSum]) {
+  constexpr int kAccBatch = 4;  // loads in flight per lane
   const unsigned G = gridDim.x * kReduceThreads;
   for (unsigned base = blockIdx.x * kReduceThreads + threadIdx.x; base < n; base += G * kAccBatch) {
     double2 s[kAccBatch];

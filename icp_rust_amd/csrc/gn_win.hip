@@ -120,16 +120,6 @@ __device__ __forceinline__ void win_hist_body(const double2 *__restrict__ a, con
   if (SUMS) block_reduce_finish<SUMS ? kNSum : 1, true>(s_wsum, partials + (size_t)blockIdx.x * (kNSum + 1));
 }
 
-#ifdef ICP_EXPERIMENTS  // (the histograms alone: first launch of the four-launch forms of rounds 1-3)
-__global__ __launch_bounds__(kWinThreads) void k_win_hist(const double2 *__restrict__ a,
-                                                          const double2 *__restrict__ b, Pose T,
-                                                          double *__restrict__ rx, double *__restrict__ ry,
-                                                          unsigned n, WinParams P, uint32_t *whist, WinState *st,
-                                                          GnScalars *scal) {
-  win_hist_body<false>(a, b, T, rx, ry, n, P, whist, st, scal, nullptr);
-}
-#endif
-
 // launched with reduce_geometry(n): workgroup i leaves block sum i of the fixed reduction tree in `partials`
 __global__ __launch_bounds__(kWinThreads) void k_win_hist_sums(const double2 *__restrict__ a,
                                                                const double2 *__restrict__ b, Pose T,
@@ -1507,170 +1497,6 @@ __global__ __launch_bounds__(kReduceThreads) void k_win_pick_shard(PickShardLaun
   win_pick_shard_body(s_n, s_gen, s_ahead != 0, s_P, s_outer, K, s_box, A.world, A.B, L);
 }
 
-#ifdef ICP_EXPERIMENTS  // ---- the four-launch forms of rounds 1-3 (W, C, selection, A): `make experiments` only ----
-// The order statistics of one evaluation from its candidate lists, one workgroup per dimension
-// (half the registers of doing both at once): the co-resident variant of the pipeline runs this
-// as its own tiny launch so that the accumulate kernel stays small.
-__global__ __launch_bounds__(kReduceThreads) void k_win_select(unsigned n, WinState *st,
-                                                               const double *__restrict__ wmed,
-                                                               const double *__restrict__ wring, GnScalars *scal) {
-  constexpr int PM = kWinCapMed / kReduceThreads, PR = kWinCapRing / kReduceThreads;
-  const unsigned tid = threadIdx.x;
-  const int d = blockIdx.x;
-  const unsigned klo = (n - 1) / 2, khi = n / 2;
-  double med = 0., sig = 0.;
-  bool fail = false;
-  if (st->fail == 0) {  // (written by k_win_compact; this kernel only ever raises it)
-    double vm[1][PM], vr[1][PR];
-#pragma unroll
-    for (int u = 0; u < PM; ++u) vm[0][u] = wmed[(size_t)d * kWinCapMed + tid + u * kReduceThreads];
-#pragma unroll
-    for (int u = 0; u < PR; ++u) vr[0][u] = wring[(size_t)d * kWinCapRing + tid + u * kReduceThreads];
-    const unsigned em[1] = {st->med_cnt[d]}, er[1] = {st->ring_cnt[d]};
-    // (the appended counts are cross-checked against the histogram: a mismatch is a miss)
-    fail = st->list_cnt[d][0] != em[0] || st->list_cnt[2 + d][0] != er[0];
-    const double m_lo[1] = {st->med_lo[d]}, m_hi[1] = {st->med_hi[d]};
-    const double r_lo[1] = {st->ring_lo[d]}, r_hi[1] = {st->ring_hi[d]};
-    const long long mlo[1] = {(long long)klo - st->med_base[d]}, mhi[1] = {(long long)khi - st->med_base[d]};
-    const long long dlo[1] = {(long long)klo - st->ring_inner[d]}, dhi[1] = {(long long)khi - st->ring_inner[d]};
-    unsigned long long key[1][2];
-    if (!fail) select_n<1, PM>(vm, em, m_lo, m_hi, mlo, mhi, key, fail);
-    if (!fail) {
-      med = middle_of(n, key[0][0], key[0][1]);
-#pragma unroll
-      for (int u = 0; u < PR; ++u) vr[0][u] = fabs(vr[0][u] - med);  // src/stats.rs:35
-      select_n<1, PR>(vr, er, r_lo, r_hi, dlo, dhi, key, fail);
-      if (!fail) sig = ICP_PPF34 * middle_of(n, key[0][0], key[0][1]);  // src/stats.rs:42-46
-    }
-  }
-  if (tid == 0) {  // the accumulate kernel is the next launch on this stream
-    scal->median[d] = med;
-    scal->sigma[d] = sig;
-    if (fail) atomicOr(&st->fail, 1u);
-  }
-}
-
-// INLINE_SELECT: every workgroup derives the order statistics itself (lowest latency: the
-// evaluation the host is waiting for).  Otherwise k_win_select has left them in `scal`, and this
-// kernel needs few enough registers (68) to be placed beside three search waves per SIMD.
-// n_total: the points of the whole evaluation (ranks of the order statistics); n: the points THIS launch
-// accumulates.  PUBLISH = false (sharded evaluation): the block sums are all this rank contributes -- no
-// ticket, no second stage; the statistics it selected go to `scal` for the kernel that folds every rank's
-// block sums (k_shard_fold).
-template <bool INLINE_SELECT, bool PUBLISH = true>
-__global__ __launch_bounds__(kReduceThreads) void k_win_accumulate(
-    const double2 *__restrict__ a, const double *__restrict__ rx, const double *__restrict__ ry, unsigned n,
-    unsigned n_total, Pose T, const WinState *__restrict__ st, const double *__restrict__ wmed,
-    const double *__restrict__ wring, GnScalars *scal, double *partials, uint32_t *whist, SelCtl *ctl, GnResult *res,
-    unsigned seq) {
-  if (!INLINE_SELECT) {
-    const bool failed = st->fail != 0;
-    const double med0[2] = {scal->median[0], scal->median[1]};
-    const double sig0[2] = {scal->sigma[0], scal->sigma[1]};
-    double acc[kNSum];
-#pragma unroll
-    for (int k = 0; k < kNSum; ++k) acc[k] = 0.;
-    if (!failed) accumulate_points<2>(a, rx, ry, n, T, acc);
-    block_reduce_store<kNSum, true>(acc, partials + (size_t)blockIdx.x * (kNSum + 1));
-    const unsigned G0 = gridDim.x * kReduceThreads;  // (write-through, see below)
-    for (unsigned i = blockIdx.x * kReduceThreads + threadIdx.x; i < 2u * kWinBins; i += G0)
-      __hip_atomic_store(&whist[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!last_block_arrives(&ctl->t[2])) return;
-    publish_result(partials, res, seq, sig0, med0, scal->nan_flag, failed ? 2 : 0);
-    return;
-  }
-  constexpr int PM = kWinCapMed / kReduceThreads, PR = kWinCapRing / kReduceThreads;
-  static_assert(kWinCapMed % kReduceThreads == 0 && kWinCapRing % kReduceThreads == 0, "candidates per thread");
-  const unsigned tid = threadIdx.x;
-#ifdef ICP_WIN_DEBUG
-  long long stamp[8];
-  int ns_ = 0;
-#define STAMP() stamp[ns_++] = wall_clock64()
-#else
-#define STAMP()
-#endif
-  STAMP();
-  // every global load of the prologue is issued before the first use: one round trip
-  double vm[2][PM], vr[2][PR];
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-#pragma unroll
-    for (int u = 0; u < PM; ++u) vm[d][u] = wmed[(size_t)d * kWinCapMed + tid + u * kReduceThreads];
-#pragma unroll
-    for (int u = 0; u < PR; ++u) vr[d][u] = wring[(size_t)d * kWinCapRing + tid + u * kReduceThreads];
-  }
-  const unsigned got[4] = {st->list_cnt[0][0], st->list_cnt[1][0], st->list_cnt[2][0], st->list_cnt[3][0]};
-  const unsigned em[2] = {st->med_cnt[0], st->med_cnt[1]}, er[2] = {st->ring_cnt[0], st->ring_cnt[1]};
-  const unsigned mbase[2] = {st->med_base[0], st->med_base[1]}, inner[2] = {st->ring_inner[0], st->ring_inner[1]};
-  const double m_lo[2] = {st->med_lo[0], st->med_lo[1]}, m_hi[2] = {st->med_hi[0], st->med_hi[1]};
-  const double r_lo[2] = {st->ring_lo[0], st->ring_lo[1]}, r_hi[2] = {st->ring_hi[0], st->ring_hi[1]};
-  // (the appended counts are cross-checked against the histogram: a mismatch is a miss)
-  bool fail = st->fail != 0 || got[0] != em[0] || got[1] != em[1] || got[2] != er[0] || got[3] != er[1];
-#ifdef ICP_WIN_DEBUG
-  if (blockIdx.x == 0 && tid == 0 && fail)
-    printf("[A] fail: st %u got %u %u %u %u want %u %u %u %u\n", st->fail, got[0], got[1], got[2], got[3], em[0], em[1], er[0], er[1]);
-#endif
-  STAMP();
-  const unsigned klo = (n_total - 1) / 2, khi = n_total / 2;
-  double med[2] = {0., 0.}, sig[2] = {0., 0.};
-  if (!fail) {
-    unsigned long long key[2][2];
-    const long long mlo[2] = {(long long)klo - mbase[0], (long long)klo - mbase[1]};
-    const long long mhi[2] = {(long long)khi - mbase[0], (long long)khi - mbase[1]};
-    select_n<2, PM>(vm, em, m_lo, m_hi, mlo, mhi, key, fail);
-    STAMP();
-    if (!fail) {
-#pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        med[d] = middle_of(n_total, key[d][0], key[d][1]);
-#pragma unroll
-        for (int u = 0; u < PR; ++u) vr[d][u] = fabs(vr[d][u] - med[d]);  // src/stats.rs:35
-      }
-      const long long dlo[2] = {(long long)klo - inner[0], (long long)klo - inner[1]};
-      const long long dhi[2] = {(long long)khi - inner[0], (long long)khi - inner[1]};
-      select_n<2, PR>(vr, er, r_lo, r_hi, dlo, dhi, key, fail);
-      STAMP();
-      if (!fail) {
-        sig[0] = ICP_PPF34 * middle_of(n_total, key[0][0], key[0][1]);  // src/stats.rs:42-46
-        sig[1] = ICP_PPF34 * middle_of(n_total, key[1][0], key[1][1]);
-      }
-    }
-  }
-  double acc[kNSum];
-#pragma unroll
-  for (int k = 0; k < kNSum; ++k) acc[k] = 0.;
-  if (!fail) accumulate_points<kWinAccBatch>(a, rx, ry, n, T, acc);
-  STAMP();
-  block_reduce_store<kNSum, true>(acc, partials + (size_t)blockIdx.x * (kNSum + 1));
-  // the histograms of the next evaluation start from zero (nobody reads them in this launch).
-  // Write-through stores: the next evaluation may run on the handle's other stream, handed over
-  // by the host as soon as it sees this kernel's result -- i.e. possibly before this kernel's
-  // end-of-kernel write-back, so nothing it must see may linger in an XCD's L2.
-  const unsigned G = gridDim.x * kReduceThreads;
-  for (unsigned i = blockIdx.x * kReduceThreads + threadIdx.x; i < 2u * kWinBins; i += G)
-    __hip_atomic_store(&whist[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  STAMP();
-#ifdef ICP_WIN_DEBUG
-  if (tid == 0 && (blockIdx.x == 0 || blockIdx.x == 200) && seq % 8 == 2)
-    printf("[A blk %d] loads %lld sel1 %lld sel2 %lld acc %lld red %lld (x10ns)\n", blockIdx.x, stamp[1] - stamp[0],
-           stamp[2] - stamp[1], stamp[3] - stamp[2], stamp[4] - stamp[3], stamp[5] - stamp[4]);
-#endif
-
-  if (!PUBLISH) {
-    if (blockIdx.x == 0 && tid == 0) {  // every rank selects the same statistics from the same candidates
-      scal->median[0] = med[0];
-      scal->median[1] = med[1];
-      scal->sigma[0] = sig[0];
-      scal->sigma[1] = sig[1];
-      scal->overflow = fail ? 2 : 0;
-    }
-    return;
-  }
-  if (!last_block_arrives(&ctl->t[2])) return;
-  publish_result(partials, res, seq, sig, med, scal->nan_flag, fail ? 2 : 0);
-}
-#endif  // ICP_EXPERIMENTS
-
 // the sharded evaluation (shard.hip) launches this one from another translation unit
 template __global__ void k_win_compact<false>(const double *__restrict__, const double *__restrict__, unsigned, unsigned,
                                               WinParams, const uint32_t *__restrict__, WinState *, double *, double *,
@@ -1828,11 +1654,10 @@ __global__ __launch_bounds__(kReduceThreads) void k_shard_finish(ShardPtrs srcs,
 
 // ---- host ---------------------------------------------------------------------------
 bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind, bool any_n, double f_override) {
-  static const bool off = exp_env("ICP_GN_NO_WIN") != nullptr;
   const Workspace &w = h->ws;
   // (any_n: the sharded evaluation, which refines a window that missed from that attempt's own counts
   // instead of giving up -- api.hip, shard_finish_common -- and so serves any number of points)
-  if (off || n < kWinMinN || (n > kWinMaxN && !any_n)) return false;
+  if (n < kWinMinN || (n > kWinMaxN && !any_n)) return false;
   // the evaluation's own kind first (common.hpp, Workspace::win_kind), else the most recent evaluation
   const bool own = Workspace::kind_has_slot(kind) && w.win_kind[kind].valid;
   if (!own && !w.win_valid) return false;
@@ -1845,15 +1670,14 @@ bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind, bool a
 
 // half-width of the fine windows in sigmas: the prediction may be off by about that much (4 x after a miss)
 double window_half_width(size_t n, bool wide) {
-  static const double hw_env = exp_env("ICP_WIN_HW") ? atof(exp_env("ICP_WIN_HW")) : 0.;
   // Clouds of up to 2^17 points (512 per workgroup of the tree): even the widest windows leave a handful of candidates in
   // a fine bin and a few hundred members for a workgroup to stage, so narrow windows save nothing there -- and they cost
   // a fresh handle (one per frame in examples/scan3d.rs) two evaluations through the seven-launch pipeline, when the first
   // evaluations of a kind are predicted from another kind's statistics and miss (0.18 ms of a 1.28-ms frame:
   // profiles/r05_frame_trace_fresh.txt).
-  if (hw_env <= 0. && n <= ((size_t)1 << 17)) return 0.2;
-  const double hw_sigmas = hw_env > 0. ? hw_env : 0.05;
-  double f = hw_sigmas * (wide ? 4. : 1.);
+  if (n <= ((size_t)1 << 17)) return 0.2;
+  constexpr double kHalfWidth = 0.05;
+  double f = kHalfWidth * (wide ? 4. : 1.);
   if (n > 1000000) f *= 1e6 / (double)n;  // candidates per fine bin grow with n
   return f > 0.2 ? 0.2 : f;               // the windows must not overlap (MAD = 0.6745 sigma)
 }
@@ -2010,18 +1834,8 @@ hipError_t launch_weighted_gn_win(icp_handle *h, const double *d_a, const double
   // Two launches either way.  Round 5: the first files the candidates, the second is ONE workgroup (k_win_hist_sums_bkt
   // / k_win_pick) wherever bkt_fits says so; windows too wide for that (after a miss) and handles whose files were not
   // usable recently take the second pass over the points (k_win_hist_sums / k_win_finish, round 3).
-#ifdef ICP_EXPERIMENTS
-  // ICP_WIN_BKT: 0 = never, 1 = wherever it fits (default), 2 = not beside a search, 3 = only there.  ICP_WIN_FUSE_MODE /
-  // ICP_WIN_NO_FUSE / ICP_WIN_NO_CORESIDENT: the four-launch forms of rounds 1-3 (experiments build only).
-  static const int bkt_mode = exp_env("ICP_WIN_BKT") ? atoi(exp_env("ICP_WIN_BKT")) : 1;
-  const bool on_eval_stream = w.spec_stream && s == w.spec_stream;
-  const bool beside_search = on_eval_stream && w.search_beside_eval;
-  const bool bkt_here = bkt_mode == 1 || (bkt_mode == 2 && !beside_search) || (bkt_mode == 3 && beside_search);
-#else
-  constexpr bool bkt_here = true;
-#endif
   if (w.bkt_off > 0) --w.bkt_off;
-  else if (bkt_here && bkt_fits(n_, P)) {
+  else if (bkt_fits(n_, P)) {
     ++w.bkt_evals;
     const HistBktArgs HA = bkt_hist_args(w, a, b, T, n, P);
     hipLaunchKernelGGL(k_win_hist_sums_bkt, dim3(tree_blocks(n_)), dim3(kWinThreads), 0, s, HA);
@@ -2030,31 +1844,6 @@ hipError_t launch_weighted_gn_win(icp_handle *h, const double *d_a, const double
   }
   int blocks, threads;
   reduce_geometry(n_, &blocks, &threads);
-#ifdef ICP_EXPERIMENTS
-  static const bool no_co = exp_env("ICP_WIN_NO_CORESIDENT") != nullptr;
-  static const bool no_fuse = exp_env("ICP_WIN_NO_FUSE") != nullptr;
-  static const int fuse_mode = exp_env("ICP_WIN_FUSE_MODE") ? atoi(exp_env("ICP_WIN_FUSE_MODE")) : 1;
-  if (no_fuse || !(fuse_mode == 1 || (fuse_mode == 2 && !beside_search) || (fuse_mode == 3 && beside_search) ||
-                   (fuse_mode == 4 && !on_eval_stream))) {
-    hipLaunchKernelGGL(k_win_hist, dim3(hb), dim3(kWinThreads), 0, s, a, b, T, w.d_rx, w.d_ry, n, P, w.d_whist,
-                       w.d_wstate, w.d_scal);
-    hipLaunchKernelGGL(k_win_compact<false>, dim3(hb), dim3(kWinThreads), 0, s, (const double *)w.d_rx,
-                       (const double *)w.d_ry, n, n, P, (const uint32_t *)w.d_whist, w.d_wstate, w.d_wmed,
-                       w.d_wring, (const unsigned *)nullptr, 0u);
-    if (!no_co) {
-      hipLaunchKernelGGL(k_win_select, dim3(2), dim3(kReduceThreads), 0, s, n, w.d_wstate, (const double *)w.d_wmed,
-                         (const double *)w.d_wring, w.d_scal);
-      hipLaunchKernelGGL(k_win_accumulate<false>, dim3(blocks), dim3(threads), 0, s, a, (const double *)w.d_rx,
-                         (const double *)w.d_ry, n, n, T, (const WinState *)w.d_wstate, (const double *)w.d_wmed,
-                         (const double *)w.d_wring, w.d_scal, w.d_partials, w.d_whist, w.d_ctl, w.h_res, ++w.seq);
-    } else {
-      hipLaunchKernelGGL(k_win_accumulate<true>, dim3(blocks), dim3(threads), 0, s, a, (const double *)w.d_rx,
-                         (const double *)w.d_ry, n, n, T, (const WinState *)w.d_wstate, (const double *)w.d_wmed,
-                         (const double *)w.d_wring, w.d_scal, w.d_partials, w.d_whist, w.d_ctl, w.h_res, ++w.seq);
-    }
-    return hipGetLastError();
-  }
-#endif
   hipLaunchKernelGGL(k_win_hist_sums, dim3(blocks), dim3(threads), 0, s, a, b, T, w.d_rx, w.d_ry, n, P, w.d_whist,
                      w.d_wstate, w.d_scal, w.d_partials, -1);
   hipLaunchKernelGGL(k_win_finish<false>, dim3(hb), dim3(kWinThreads), 0, s, (const double *)w.d_rx,
@@ -2074,7 +1863,7 @@ hipError_t launch_weighted_gn_win(icp_handle *h, const double *d_a, const double
 // resolved by the usual C and A launches -- which verify everything by exact counts, so a bad
 // sample can only cost a repeat with the radix pipeline, never a different result.
 bool refine_applies(size_t n) {
-  static const bool off = exp_env("ICP_GN_NO_WIN") != nullptr || getenv("ICP_GN_NO_REFINE") != nullptr;
+  static const bool off = getenv("ICP_GN_NO_REFINE") != nullptr;
   return !off && n > kWinMaxN && n / kRefineSample >= 1 && n < 0xffffffffull;
 }
 

@@ -9,7 +9,6 @@ namespace icp {
 
 constexpr int kWinThreads = 512;  // workgroups small enough to be placed beside the search kernel's waves
 constexpr int kWinBatch = 4;
-constexpr int kWinAccBatch = 4;  // loads in flight per lane in A (2 saves 16 VGPRs but loses more than the better placement gains)
 #ifndef ICP_SELECT_DIRECT
 #define ICP_SELECT_DIRECT 256  // select_n: lists up to this long are ranked directly (128 until round 5)
 #endif

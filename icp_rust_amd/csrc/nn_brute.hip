@@ -591,28 +591,21 @@ hipError_t build_target_soa(icp_handle *h) {
   return hipGetLastError();
 }
 
-static int env_int(const char *name, int dflt) {
-  const char *s = exp_env(name);
-  return s ? atoi(s) : dflt;
-}
-
 template <int DIM, int R, bool XFORM>
 static void launch_one(icp_handle *h, const double *d_src, unsigned n, const Pose &T, unsigned qblocks,
                        unsigned chunks, unsigned chunk) {
   const bool full = chunk % kNnTile == 0;
   const double *tx = h->d_dst_soa, *ty = tx + h->m_pad, *tz = ty + h->m_pad;
-  static const bool no_screen = exp_env("ICP_NN_NO_SCREEN") != nullptr;
-  if (h->screen_valid && !no_screen) {
+  if (h->screen_valid) {
     const float *fx = h->d_dst_f32, *fy = fx + h->m_pad, *fz = fy + h->m_pad;
     const GridParams &g = h->grid.p;
     const double cx = 0.5 * (g.lo[0] + g.hi[0]), cy = 0.5 * (g.lo[1] + g.hi[1]), cz = 0.5 * (g.lo[2] + g.hi[2]);
     // the dot-product screen (two queries per packed instruction) unless its cancellation margin would
-    // swamp the distances it has to tell apart; ICP_NN_OLD_SCREEN: the difference-based screen, for A/B
-    static const bool old_screen = exp_env("ICP_NN_OLD_SCREEN") != nullptr;
+    // swamp the distances it has to tell apart
     const double ex = g.hi[0] - g.lo[0], ey = g.hi[1] - g.lo[1], ez = g.hi[2] - g.lo[2];
     const double half_diag = 0.5 * sqrt((ex * ex + ey * ey) + ez * ez) * 1.000001;
     if constexpr (R >= 2) {
-      if (!old_screen && half_diag < 1e15 && half_diag > 0.) {
+      if (half_diag < 1e15 && half_diag > 0.) {
         if (full)
           hipLaunchKernelGGL((k_nn_brute_dot<DIM, R, XFORM, true>), dim3(qblocks, chunks), dim3(kNnThreads), 0, h->stream,
                              d_src, n, tx, ty, tz, fx, fy, fz, (unsigned)h->m_pad, chunk, T, cx, cy, cz, g.scale,
@@ -670,22 +663,18 @@ hipError_t launch_nn_brute(icp_handle *h, const double *d_src, size_t n_, const 
 
   // queries per lane: enough waves to cover 1024 SIMDs several times over, then as
   // many registers-resident queries as that allows (fewer LDS reads per pair)
-  static const int forced_r = env_int("ICP_NN_R", 0);
   int R = 1;
   if (n >= 900000u) R = 8;  // (with the packed screen 8 queries per lane win from ~1M: 143 vs 147 ms)
   else if (n >= 2u * 256u * 1024u) R = 4;
   else if (n >= 256u * 1024u) R = 2;
-  if (forced_r == 1 || forced_r == 2 || forced_r == 4 || forced_r == 8) R = forced_r;
   const unsigned qblocks = (n + kNnThreads * R - 1) / (kNnThreads * R);
   // split the targets when the query blocks alone cannot fill the chip: chunks of whole 64-target
   // granules (a tile is 16 of them), so that even a 650-point scan spreads over ~11 workgroups per
   // query block instead of one lane looping over a whole padded tile
-  static const int forced_chunks = env_int("ICP_NN_CHUNKS", 0);
   const unsigned granules = (unsigned)((h->m + 63) / 64);  // beyond them the SoA holds only +inf padding
   unsigned chunks = 1;
   const unsigned want_blocks = 2048;
   if (qblocks < want_blocks) chunks = (want_blocks + qblocks - 1) / qblocks;
-  if (forced_chunks > 0) chunks = (unsigned)forced_chunks;
   if (chunks > granules) chunks = granules;
   if (chunks > 64) chunks = 64;
   if (chunks < 1) chunks = 1;
@@ -694,8 +683,7 @@ hipError_t launch_nn_brute(icp_handle *h, const double *d_src, size_t n_, const 
   chunks = (granules + granules_per_chunk - 1) / granules_per_chunk;
   const unsigned chunk = granules_per_chunk * 64;
 
-  static const bool no_tiny = exp_env("ICP_NN_NO_TINY") != nullptr;
-  const bool tiny = !no_tiny && n <= 2048u && h->m <= 2048;
+  const bool tiny = n <= 2048u && h->m <= 2048;
   // partial buffers
   const size_t need = tiny ? 0 : (size_t)chunks * n;
   if (need > h->ws.cap_part) {

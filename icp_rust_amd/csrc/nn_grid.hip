@@ -193,15 +193,14 @@ hipError_t build_grid(icp_handle *h) {
       vol *= ext[d];
       ++k;
     }
-  // ICP_GRID_OCC: targets per cell the cell size aims at (tuning knob; any value is exact)
-  static const double occ = exp_env("ICP_GRID_OCC") ? atof(exp_env("ICP_GRID_OCC")) : 2.;
-  double hh = k > 0 ? pow(occ * vol / (double)m, 1. / k) : 1.;
+  constexpr double kOcc = 2.;  // targets per cell the cell size aims at (any value is exact)
+  double hh = k > 0 ? pow(kOcc * vol / (double)m, 1. / k) : 1.;
   if (!(hh > 0.) || !std::isfinite(hh)) hh = 1.;
-  // ICP_GRID_FX: cells are that many times finer along x.  A row of cells along x is one
+  // Cells are kFx times finer along x.  A row of cells along x is one
   // contiguous run of records, so finer x cells clip the runs tighter around [qx - r, qx + r]
   // without adding rows (dense surfaces put ~10 targets into a cubic cell of the average
   // occupancy; the search radius there is a fraction of the cell).
-  static const double fx = exp_env("ICP_GRID_FX") ? fmax(1., atof(exp_env("ICP_GRID_FX"))) : 4.;
+  constexpr double kFx = 4.;
   // The cell size grows until the cells fit BOTH the 2^24 total and the per-axis limits (16384 along
   // x, 4096 along y / z): an elongated cloud (a corridor map: 20000 x 50 x 5 m) must not collapse
   // everything beyond the capped axis into its last cell -- results would stay exact (edge cells are
@@ -210,7 +209,7 @@ hipError_t build_grid(icp_handle *h) {
   for (;;) {
     double cells = 1.;
     for (int d = 0; d < 3; ++d) {
-      g.h[d] = d == 0 ? hh / fx : hh;
+      g.h[d] = d == 0 ? hh / kFx : hh;
       const bool flat = !(d < h->dim && ext[d] > 1e-9 * emax);
       const double cap = d == 0 ? 16384. : 4096.;
       double nd = flat ? 1. : floor(ext[d] / g.h[d]) + 1.;
@@ -225,7 +224,7 @@ hipError_t build_grid(icp_handle *h) {
     hh *= 1.26;
   }
   for (int d = 0; d < 3; ++d) g.inv_h[d] = 1. / g.h[d];
-  g.fx = (int)fmin(fmax(floor(fx + 0.5), 1.), 64.);
+  g.fx = (int)kFx;
   g.scale = scale + hh;
   g.ext = (float)(emax + hh);
   // k_nn_grid_warm evaluates every pruning bound in f32, relative to the grid origin, with explicit
@@ -276,7 +275,7 @@ hipError_t build_grid(icp_handle *h) {
 // shift[c] = the number of NEW points in the cells before c -- a streaming copy, no atomics -- and the new records
 // fill the gap at the end of their cells.  Applicable while every new point lies inside the grid's box (the pruning
 // margins of the searches assume it) and the cloud has not outgrown the cell size chosen at the last full build
-// (ICP_GRID_REBUILD_GROWTH, default 1.5 x); otherwise the caller rebuilds.  Any grid gives the exact result.
+// (kRebuildGrowth = 1.5 x); otherwise the caller rebuilds.  Any grid gives the exact result.
 // "inside": within half a cell of the box.  The pruning margins of the searches are derived for grid-relative
 // coordinates of magnitude <= g.ext = the largest extent + ONE cell (build_grid), and cells at the rim of the grid
 // are unbounded outwards (targets are clamped into them), so a target up to half a cell outside the box is served
@@ -339,10 +338,9 @@ __global__ void k_grid_insert(const double *__restrict__ tail, unsigned k, unsig
 hipError_t append_grid(icp_handle *h, size_t m_old_, size_t k_, bool *done) {
   *done = false;
   Grid &G = h->grid;
-  static const bool off = exp_env("ICP_GRID_NO_APPEND") != nullptr;
-  static const double growth = exp_env("ICP_GRID_REBUILD_GROWTH") ? atof(exp_env("ICP_GRID_REBUILD_GROWTH")) : 1.5;
-  if (off || !G.built || m_old_ == 0 || k_ == 0 || G.m_full == 0) return hipSuccess;
-  if ((double)(m_old_ + k_) > growth * (double)G.m_full) return hipSuccess;  // the cell size is due for a re-tune
+  constexpr double kRebuildGrowth = 1.5;  // appended past this factor of the last full build: rebuild
+  if (!G.built || m_old_ == 0 || k_ == 0 || G.m_full == 0) return hipSuccess;
+  if ((double)(m_old_ + k_) > kRebuildGrowth * (double)G.m_full) return hipSuccess;  // the cell size is due for a re-tune
   const unsigned m_old = (unsigned)m_old_, k = (unsigned)k_, m_new = m_old + k;
   const GridParams g = G.p;
   hipStream_t s = h->stream;
@@ -402,22 +400,6 @@ hipError_t append_grid(icp_handle *h, size_t m_old_, size_t k_, bool *done) {
 }
 
 // ---------------------------------------------------------------- query ----------
-#ifdef ICP_NN_STATS
-// Diagnostic build only (make STATS=1 -> libicp_mi355x_stats.so, never the product library):
-// per-launch totals of what the search actually does.  [0] queries, [1] row-bound fetches,
-// [2] record batches, [3] exact evaluations, [4] sum over waves of wave-level loop steps,
-// [5] sum over waves of lifetime in shader cycles, [6] waves, [7] warm queries.
-__device__ unsigned long long g_nn_stats[8];
-__device__ unsigned long long g_nn_hist[2][32];  // [0]: lanes by record chunks, [1]: waves by loop steps
-// the warm walk: [0] wave-level row groups, [1] wave-level record chunks, [2] ... of them with an exact test in some lane,
-// [3] lane row groups, [4] lane chunks, [5] lane exact tests, [6] lifetime (cycles, summed over waves), [7] waves
-__device__ unsigned long long g_nn_warm[8];
-__device__ unsigned long long g_nn_warm_hist[2][32];  // waves by row groups; waves by record chunks
-#define NN_STAT(i, v) (st[i] += (v))
-#else
-#define NN_STAT(i, v) ((void)0)
-#endif
-
 // COLD: no previous matches exist (first search of a source snapshot, or unsorted queries).
 // Register budget of the warm 3-D instantiation: 120 VGPRs -- three of its waves plus two waves of an
 // evaluation kernel (<= 72) share a SIMD during the speculative overlap (tests/test_registers.py).
@@ -459,10 +441,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
                                                  double2 *__restrict__ a, double2 *__restrict__ b,
                                                  const PrevMatch *__restrict__ prev, PrevMatch *prev_out,
                                                  const AheadPose *__restrict__ ahead) {
-#ifdef ICP_NN_STATS
-  unsigned st[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
-#endif
   if (XFORM && ahead) {  // a search enqueued before the host knew its pose (launch_nn_grid_ahead)
     if (!ahead->valid) return;
     T = ahead->T;
@@ -514,7 +492,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
   float thr32 = __builtin_huge_valf();
   double bx = 0., by = 0., bz = 0.;  // the winner's exact coordinates (outputs + next warm start)
   auto eval = [&](uint32_t ti, double tx, double ty, double tz) {
-    NN_STAT(3, 1);
     const double ddx = q[0] - tx;
     const double ddy = q[1] - ty;
     double dd = ddx * ddx + ddy * ddy;
@@ -605,7 +582,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
       if (!(sc[u_] > thr32)) consider(t[u_].idx);                                 \
   } while (0)
   auto batch = [&](uint32_t p, uint32_t e) {
-    NN_STAT(2, 1);
     const uint32_t last = e - 1;
     GridPoint t[kBatch];
 #pragma unroll
@@ -677,7 +653,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
         ++nr;
       }
       if (nr == 0) break;
-      NN_STAT(1, nr);
       if (nr < 2) ra1 = ra0, rz1 = rz0;  // unused slots repeat row 0 (a cached address costs next to nothing)
       if (nr < 3) ra2 = ra0, rz2 = rz0;
       if (nr < 4) ra3 = ra0, rz3 = rz0;
@@ -690,13 +665,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
       const uint32_t o3 = o2 + (nr > 2 ? e2 - s2 : 0u);
       const uint32_t R = o3 + (nr > 3 ? e3 - s3 : 0u);
       for (uint32_t base = 0; base < R; base += kBatch) {
-#ifdef ICP_HACK_CAP
-        if (base >= 24) break;
-#endif
-#ifdef ICP_NN_STATS
-        if ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) st[4] += 1;
-#endif
-        NN_STAT(2, 1);
         GridPoint t[kBatch];
 #pragma unroll
         for (uint32_t u = 0; u < kBatch; ++u) {
@@ -728,7 +696,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
     const PrevMatch pm = prev[k];  // coalesced per-slot record (index + exact coordinates), not a gather
     prev_bi = pm.idx;
     if (pm.idx != 0xffffffffu) {
-      NN_STAT(7, 1);
       eval(pm.idx, pm.x, pm.y, pm.z);
       if (best < __builtin_huge_val()) {
         const double rad = sqrt(best) * (1. + 1e-9);
@@ -829,25 +796,6 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
       if (Lb > 0. && best < Lb * Lb) break;   // every unvisited target is strictly farther
     }
   }
-#ifdef ICP_NN_STATS
-  {
-    const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-    for (int j = 0; j < 5; ++j)
-      if (j != 4) atomicAdd(&g_nn_stats[j], (unsigned long long)st[j]);
-    atomicAdd(&g_nn_stats[4], (unsigned long long)st[4]);
-    atomicAdd(&g_nn_stats[7], (unsigned long long)st[7]);
-    atomicAdd(&g_nn_hist[0][st[2] < 31 ? st[2] : 31], 1ull);
-    {
-      unsigned mx = st[2];
-      for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off));
-      if ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) atomicAdd(&g_nn_hist[1][mx < 31 ? mx : 31], 1ull);
-    }
-    if ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) {
-      atomicAdd(&g_nn_stats[5], t_end - t_begin);
-      atomicAdd(&g_nn_stats[6], 1ull);
-    }
-  }
-#endif
   // prev and prev_out are the same per-slot array: a slot whose match did not change already
   // holds this record (32 B of write traffic per query saved once the registration settles)
   if (L > 1 && sub != 0) return;  // the group agrees (walk_box ends on share_best); one lane reports
@@ -872,7 +820,7 @@ __global__ __launch_bounds__(kGridThreads) void k_nn_grid(const double *__restri
 
 // ---------------------------------------------------------------- warm search ----
 // The search of the second and later outer iterations of one estimate call, one lane per query
-// (clouds beyond ICP_NN_COOP_MAX_N points), rewritten in round 2 after the counters showed what the
+// (clouds beyond kGridCoopMaxN points), rewritten in round 2 after the counters showed what the
 // kernel above is bound by: NOT memory latency but vector-instruction issue -- 2 600 VALU
 // instructions per wave, ~80 % of the SIMDs' issue slots (profiles/r02_nn_grid_sq_pmc.txt); f64
 // square roots (a 20-instruction sequence each: radius, per-row clip, every improvement), f64 floor /
@@ -919,11 +867,6 @@ __device__ __forceinline__ void warm_query(const unsigned k, const double *__res
                                            double2 *__restrict__ a, double2 *__restrict__ b, PrevMatch *prev,
                                            CertDecay cd = CertDecay{0.f, 0.f, 0.f, 0.f}, PrevMatch seed = PrevMatch{0., 0., 0., 0xffffffffu, 0u}) {
   const unsigned i = perm ? perm[k] : k;  // null: outputs in slot order
-#ifdef ICP_NN_STATS
-  unsigned ws[6] = {0, 0, 0, 0, 0, 0};
-  const unsigned long long wt0 = __builtin_amdgcn_s_memtime();
-#define WARM_LEADER() ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1))
-#endif
   double q[3];
   q[0] = src[(size_t)k * DIM + 0];
   q[1] = src[(size_t)k * DIM + 1];
@@ -1096,10 +1039,6 @@ __device__ __forceinline__ void warm_query(const unsigned k, const double *__res
       ++nr;
     }
     if (nr == 0) break;
-#ifdef ICP_NN_STATS
-    ws[3] += 1;
-    if (WARM_LEADER()) ws[0] += 1;
-#endif
     if (nr < 2) ra1 = ra0, rz1 = rz0;  // unused slots repeat row 0 (a cached address)
     if (nr < 3) ra2 = ra0, rz2 = rz0;
     if (nr < 4) ra3 = ra0, rz3 = rz0;
@@ -1148,16 +1087,6 @@ __device__ __forceinline__ void warm_query(const unsigned k, const double *__res
         }
         sc[u] = s2;
       }
-#ifdef ICP_NN_STATS
-      {
-        bool any = false;
-        for (uint32_t u = 0; u < kR; ++u)
-          if (!(sc[u] > thr32) && t[u].idx != bi) any = true, ws[5] += 1;
-        ws[4] += 1;
-        const bool wave_any = __ballot(any) != 0ull;
-        if (WARM_LEADER()) ws[1] += 1, ws[2] += wave_any ? 1u : 0u;
-      }
-#endif
 #pragma unroll
       for (uint32_t u = 0; u < kR; ++u)
         if (!(sc[u] > thr32) && t[u].idx != bi) consider(t[u].idx);
@@ -1167,30 +1096,6 @@ __device__ __forceinline__ void warm_query(const unsigned k, const double *__res
       }
     }
   }
-#ifdef ICP_NN_STATS
-  {
-    // (lanes leave the loops at different times: the wave-level counts belong to whichever lane led at the time)
-    unsigned w0 = ws[0], w1 = ws[1], w2 = ws[2];
-    for (int off = 32; off >= 1; off >>= 1) {
-      w0 += (unsigned)__shfl_xor((int)w0, off);
-      w1 += (unsigned)__shfl_xor((int)w1, off);
-      w2 += (unsigned)__shfl_xor((int)w2, off);
-    }
-    atomicAdd(&g_nn_warm[3], (unsigned long long)ws[3]);
-    atomicAdd(&g_nn_warm[4], (unsigned long long)ws[4]);
-    atomicAdd(&g_nn_warm[5], (unsigned long long)ws[5]);
-    if (WARM_LEADER()) {
-      atomicAdd(&g_nn_warm[0], (unsigned long long)w0);
-      atomicAdd(&g_nn_warm[1], (unsigned long long)w1);
-      atomicAdd(&g_nn_warm[2], (unsigned long long)w2);
-      atomicAdd(&g_nn_warm[6], __builtin_amdgcn_s_memtime() - wt0);
-      atomicAdd(&g_nn_warm[7], 1ull);
-      atomicAdd(&g_nn_warm_hist[0][w0 < 31 ? w0 : 31], 1ull);
-      atomicAdd(&g_nn_warm_hist[1][w1 < 31 ? w1 : 31], 1ull);
-    }
-  }
-#undef WARM_LEADER
-#endif
   uint32_t cert_bits = 0;
   if (CERT && !wide && bi != 0xffffffffu) {
     // distances from squared bounds: a screened square is within 4e-7 relative of |qf - pf|^2, and |q - p| is
@@ -1827,7 +1732,7 @@ __global__ __launch_bounds__(kGridThreads) ICP_WARM_ATTR void k_nn_walk_lists(
 // ---------------------------------------------------------------- seeds ----------
 // The FIRST search of a snapshot has no previous matches.  The general kernel above then starts every
 // query with an infinite radius and sweeps its whole 3 x 3 x 3 block before it can prune anything
-// (242 us at 1M x 1M against 86 us for a warm search).  Instead: this kernel hands every query SOME
+// (242 us at 1M x 1M against 86 us for a warm search).  Instead: seed_match hands every query SOME
 // nearby target -- the best-screened record of its own row segment, or of the smallest block of cells
 // around it that holds any record -- as if it were its previous match, and the warm kernel does the
 // search proper from that radius.  Nothing here needs to be exact or even good: the warm kernel's
@@ -1915,17 +1820,6 @@ __device__ __forceinline__ PrevMatch seed_match(const unsigned k, const double *
     }
   }
   return out;
-}
-
-template <int DIM>
-__global__ __launch_bounds__(kGridThreads) void k_nn_grid_seed(const double *__restrict__ src, unsigned n, Pose T,
-                                                               GridParams g, const uint32_t *__restrict__ start,
-                                                               const GridPoint *__restrict__ pts,
-                                                               const double *__restrict__ dst,
-                                                               PrevMatch *__restrict__ prev) {
-  const unsigned k = xcd_wave(blockIdx.x, gridDim.x, kXcdChunk) * kGridThreads + threadIdx.x;
-  if (k >= n) return;
-  prev[k] = seed_match<DIM>(k, src, T, g, start, pts, dst);
 }
 
 // The first search of a snapshot in ONE launch (round 4): the seed goes from registers straight into the warm walk --
@@ -2050,10 +1944,9 @@ hipError_t prepare_queries(icp_handle *h, const double *d_src, size_t n_, const 
   // Clouds that get four lanes per query (frames of a few tens of thousands of points) keep the caller's order: the
   // snapshot exists for the per-slot previous matches, and the sort (a cell pass, the sort's launches, a gather:
   // 50 us of a 1.26 ms registration of a 28k-point frame) buys such a search nothing measurable -- the targets it
-  // walks fit the L2 whatever order the queries come in.  ICP_QSORT_SMALL=1 sorts them all the same.
-  static const bool sort_small = exp_env("ICP_QSORT_SMALL") != nullptr;
+  // walks fit the L2 whatever order the queries come in.
   // (... and so does a cloud its owner declares sorted already: the slices icp_multi_estimate deals out of the sorted cloud)
-  Q.identity = ((long)n <= grid_coop_max() && !sort_small) || Q.presorted;
+  Q.identity = (long)n <= kGridCoopMaxN || Q.presorted;
   Q.presorted = false;
   if (Q.identity) {
     Q.have_prev = false;
@@ -2065,33 +1958,12 @@ hipError_t prepare_queries(icp_handle *h, const double *d_src, size_t n_, const 
     Q.valid = true;
     return hipSuccess;
   }
-  // ICP_QSORT_BLOCK: log2 of the row bundle's side (0: row after row); the key must fit 32 bits
-  // (row after row serves the gather walk best: 84.1 / 86.3 / 90.4 / 94.3 us per search for 0 / 1 / 2 / 3)
-  static const int blk_env = exp_env("ICP_QSORT_BLOCK") ? atoi(exp_env("ICP_QSORT_BLOCK")) : 0;
-  int blk = blk_env < 0 ? 0 : (blk_env > 3 ? 3 : blk_env);
-  unsigned long long keys;
-  for (;; --blk) {
-    const unsigned long long nyb = ((unsigned long long)G.p.n[1] + (1ull << blk) - 1) >> blk;
-    const unsigned long long nzb = ((unsigned long long)G.p.n[2] + (1ull << blk) - 1) >> blk;
-    keys = (nzb * nyb * (unsigned long long)G.p.n[0]) << (2 * blk);
-    if (keys <= (1ull << 32) || blk == 0) break;
-  }
-  // (experiments: ICP_QSORT_XSHIFT = s drops the s low bits of the x index from the sort key -- runs of 2^s x-cells share a
-  // key, and the benchmark's 21-bit keys sort in two radix passes instead of three with s = 5.  Measured: 42 us less per
-  // call, 3-4 us MORE per search (a wave's queries spread over a longer stretch of each row): 0.1513 against 0.1492 ms
-  // per step -- the finest key stays.)
-  static const int xshift_env = exp_env("ICP_QSORT_XSHIFT") ? atoi(exp_env("ICP_QSORT_XSHIFT")) : 0;
-  int xshift = 0;
-  if (blk == 0) {
-    unsigned kb = 1;
-    while (kb < 32 && (1ull << kb) < keys) ++kb;
-    (void)kb;
-    xshift = xshift_env > 0 ? xshift_env : 0;
-    while (xshift > 0 && ((unsigned)G.p.n[0] >> xshift) == 0) --xshift;
-    const unsigned nxk = ((unsigned)G.p.n[0] + (1u << xshift) - 1) >> xshift;
-    keys = (unsigned long long)G.p.n[2] * (unsigned long long)G.p.n[1] * (unsigned long long)nxk;
-  }
-  hipLaunchKernelGGL(k_query_cell, dim3((n + 255) / 256), dim3(256), 0, s, d_src, n, h->dim, T, G.p, blk, Q.d_cell_of, xshift);
+  // The key is the cell, row after row.  k_query_cell can also key bundles of 2^blk x 2^blk rows, or runs of 2^xshift
+  // x-cells; both were measured slower.  Row bundles: 84.1 / 86.3 / 90.4 / 94.3 us per search for blk = 0 / 1 / 2 / 3.
+  // xshift = 5 sorts the benchmark's 21-bit keys in two radix passes instead of three (42 us less per call) but costs
+  // 3-4 us MORE per search (a wave's queries spread over a longer stretch of each row): 0.1513 against 0.1492 ms per step.
+  const unsigned long long keys = (unsigned long long)G.p.n[2] * (unsigned long long)G.p.n[1] * (unsigned long long)G.p.n[0];
+  hipLaunchKernelGGL(k_query_cell, dim3((n + 255) / 256), dim3(256), 0, s, d_src, n, h->dim, T, G.p, 0, Q.d_cell_of, 0);
   unsigned bits = 1;
   while (bits < 32 && (1ull << bits) < keys) ++bits;
   if ((e = stable_sort_cells(Q.d_cell_of, Q.d_perm, n, bits, Q.d_tmp, Q.cap_tmp, s)) != hipSuccess) return e;
@@ -2117,12 +1989,6 @@ hipError_t prepare_queries(icp_handle *h, const double *d_src, size_t n_, const 
   return hipSuccess;
 }
 
-// four lanes per query while one lane per query cannot fill the chip (ICP_NN_COOP_MAX_N: largest n that gets them)
-long grid_coop_max() {
-  static const long coop_max = exp_env("ICP_NN_COOP_MAX_N") ? atol(exp_env("ICP_NN_COOP_MAX_N")) : 65536;
-  return coop_max;
-}
-
 // A warm search whose pose is not known to the host yet: it is read from `d_pose` on the device, where the launch in
 // front of this one on the stream leaves it (k_win_finish, AheadPose).  Only the plain shared walk qualifies (a
 // snapshot of this cloud with previous matches, one lane per query, f32 geometry); *launched = false otherwise and
@@ -2136,10 +2002,7 @@ hipError_t launch_nn_grid_ahead(icp_handle *h, const double *d_src, size_t n_, c
   if (n_ == 0 || n_ >= 0xffffffffull || !d_pose || h->m == 0 || !G.built || !G.p.f32_ok) return hipSuccess;
   const unsigned n = (unsigned)n_;
   if (!(Q.valid && Q.src == d_src && Q.n == n_ && Q.have_prev)) return hipSuccess;
-  const bool coop = (long)n <= grid_coop_max();  // four lanes per query: the general kernel, warm
-#ifdef ICP_EXPERIMENTS
-  if (!coop && exp_env("ICP_NN_WARM_COOP") && atoi(exp_env("ICP_NN_WARM_COOP")) == 0) return hipSuccess;
-#endif
+  const bool coop = (long)n <= kGridCoopMaxN;  // four lanes per query: the general kernel, warm
   const double *q_src = !Q.identity ? Q.d_sorted : d_src;
   const uint32_t *q_perm = (!Q.slot_order && !Q.identity) ? Q.d_perm : nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2206,33 +2069,17 @@ hipError_t launch_nn_grid(icp_handle *h, const double *d_src, size_t n_, const P
     } else if (hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess)
       (void)hipEventRecord(ev0, h->stream);
   }
-  // four lanes per query while one lane per query cannot fill the chip (8 lanes measured the same, 16
-  // slower; ICP_NN_COOP_MAX_N: largest n that gets them, 0 = never)
-  const bool coop = (long)n <= grid_coop_max();
+  // four lanes per query while one lane per query cannot fill the chip (8 lanes measured the same, 16 slower)
+  const bool coop = (long)n <= kGridCoopMaxN;
   const unsigned blocks = (unsigned)(((size_t)n * (coop ? 4 : 1) + kGridThreads - 1) / kGridThreads);
-  // the warm search beyond the four-lanes-per-query sizes: the f32-geometry kernel (ICP_NN_OLD_WARM: the
-  // round-1 kernel, for A/B runs; both return the same indices)
-  static const bool old_warm = exp_env("ICP_NN_OLD_WARM") != nullptr;
+  // the warm search beyond the four-lanes-per-query sizes: the f32-geometry kernel, in chunks of kXcdChunk waves per XCD
   // (84.2 us in launch order, 83.2 / 81.1 / 82.4 / 83.1 us with chunks of 4 / 16 / 64 / 256 waves: profiles/r04_search_xcd_chunk.txt)
-  static const unsigned xcd_chunk = exp_env("ICP_NN_XCD_CHUNK") ? (unsigned)atoi(exp_env("ICP_NN_XCD_CHUNK")) : kXcdChunk;
-  // the first search of a snapshot: seeds, then the same warm kernel (ICP_NN_OLD_COLD: the general kernel)
-  static const bool old_cold = exp_env("ICP_NN_OLD_COLD") != nullptr;
-  const bool seeded = sorted && !q_prev && !coop && xform && G.p.f32_ok && !old_warm && !old_cold && h->m > 0;
-  // (the seeds as a launch of their own: only where the warm search is not the plain one that takes them in registers)
-  auto launch_seeds = [&]() {
-    if (h->dim == 3)
-      hipLaunchKernelGGL(k_nn_grid_seed<3>, dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, n, T, G.p, G.d_start,
-                         G.d_pts, h->d_dst, Q.d_prev);
-    else
-      hipLaunchKernelGGL(k_nn_grid_seed<2>, dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, n, T, G.p, G.d_start,
-                         G.d_pts, h->d_dst, Q.d_prev);
-  };
-  if ((q_prev || seeded) && !coop && xform && G.p.f32_ok && !old_warm) {
-    // certificates (k_nn_cert above): ICP_NN_NO_CERT=1 searches every query every time, as rounds 1-2 did
-    static const bool no_cert = exp_env("ICP_NN_NO_CERT") != nullptr;
-    // a step so long that too few certificates survive it: skip the check (in smallest cell sides; at 0.006 a third
-    // of the certificates fail, at 0.2 six in seven, and the break-even is about one half)
-    static const double cert_max_step = exp_env("ICP_NN_CERT_MAX_STEP") ? atof(exp_env("ICP_NN_CERT_MAX_STEP")) : 0.01;
+  // the first search of a snapshot: the same warm walk, seeded in registers
+  const bool seeded = sorted && !q_prev && !coop && xform && G.p.f32_ok && h->m > 0;
+  if ((q_prev || seeded) && !coop && xform && G.p.f32_ok) {
+    // certificates (k_nn_cert above); a step so long that too few certificates survive it skips the check (in smallest
+    // cell sides; at 0.006 a third of the certificates fail, at 0.2 six in seven, and the break-even is about one half)
+    constexpr double kCertMaxStep = 0.01;
     QuerySort &QW = h->qsort;
     double step = 0.;
     QW.have_pose_before = QW.have_pose;
@@ -2267,15 +2114,10 @@ hipError_t launch_nn_grid(icp_handle *h, const double *d_src, size_t n_, const P
     // iteration on, 33 % at the fourth); while the pose still moves by a tenth of a cell per iteration they do not
     // (benchmark pair: 85 % fail, and a walk that leaves certificates costs 30 % more than one that does not): such
     // searches run as rounds 1-2 had them.  Certificates already in the records stay valid either way.
-    const bool certs = !no_cert && decay_ok && QW.d_cert_lists != nullptr && QW.have_pose_before && step <= cert_max_step * hmin;
+    const bool certs = decay_ok && QW.d_cert_lists != nullptr && QW.have_pose_before && step <= kCertMaxStep * hmin;
     const bool check = certs && q_prev && QW.have_certs;
-    // the first search of a snapshot: ONE launch, the seed handed to the walk in registers (k_nn_grid_seeded)
-    static const bool no_fuse = exp_env("ICP_NN_SEED_SEPARATE") != nullptr;
-#ifdef ICP_EXPERIMENTS
-    static const bool warm_coop = exp_env("ICP_NN_WARM_COOP") ? atoi(exp_env("ICP_NN_WARM_COOP")) != 0 : true;
-#endif
-    const bool fused_seed = seeded && !check && !certs && !no_fuse;
-    if (seeded && !fused_seed) launch_seeds();
+    // The first search of a snapshot is ONE launch, the seed handed to the walk in registers (k_nn_grid_seeded).  It
+    // never has certificates: every path that makes a snapshot valid clears have_pose, so have_pose_before is false.
     if (check) {
       const unsigned cblocks = (n + kCertThreads - 1) / kCertThreads;
       const unsigned list_cap = ((cblocks + kCertLists - 1) / kCertLists) * kCertThreads;
@@ -2304,34 +2146,25 @@ hipError_t launch_nn_grid(icp_handle *h, const double *d_src, size_t n_, const P
       QW.have_certs = true;
       if (h->dim == 3)
         hipLaunchKernelGGL((k_nn_grid_warm<3, true>), dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T,
-                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, cd, xcd_chunk);
+                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, cd, kXcdChunk);
       else
         hipLaunchKernelGGL((k_nn_grid_warm<2, true>), dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T,
-                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, cd, xcd_chunk);
-    } else if (fused_seed) {
+                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, cd, kXcdChunk);
+    } else if (seeded) {
       if (h->dim == 3)
         hipLaunchKernelGGL(k_nn_grid_seeded<3>, dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T, G.p,
                            G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev);
       else
         hipLaunchKernelGGL(k_nn_grid_seeded<2>, dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T, G.p,
                            G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev);
-#ifdef ICP_EXPERIMENTS
-    } else if (!warm_coop) {  // ICP_NN_WARM_COOP=0: a lane per query from end to end (rounds 2-3; same indices)
-      if (h->dim == 3)
-        hipLaunchKernelGGL((k_nn_grid_warm<3, false>), dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T,
-                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, cd, xcd_chunk);
-      else
-        hipLaunchKernelGGL((k_nn_grid_warm<2, false>), dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T,
-                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, cd, xcd_chunk);
-#endif
     } else {
       if (h->dim == 3)
         hipLaunchKernelGGL(k_nn_grid_warm_coop<3>, dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T,
-                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, xcd_chunk,
+                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, kXcdChunk,
                            (const AheadPose *)nullptr);
       else
         hipLaunchKernelGGL(k_nn_grid_warm_coop<2>, dim3(blocks), dim3(kGridThreads), 0, h->stream, q_src, q_perm, n, T,
-                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, xcd_chunk,
+                           G.p, G.d_start, G.d_pts, h->d_dst, d_idx, (double2 *)d_a, (double2 *)d_b, Q.d_prev, kXcdChunk,
                            (const AheadPose *)nullptr);
     }
     hipError_t we = hipGetLastError();
@@ -2377,17 +2210,6 @@ hipError_t launch_nn_grid(icp_handle *h, const double *d_src, size_t n_, const P
   return e;
 }
 
-#ifdef ICP_NN_STATS
-extern "C" int icp_debug_nn_hist(unsigned long long out[64], int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_hist), 64 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  if (reset) {
-    unsigned long long z[64] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_nn_hist), z, sizeof(z)) != hipSuccess) return 1;
-  }
-  return 0;
-}
-
-#endif
 #ifdef ICP_COOP_PROFILE
 extern "C" int icp_debug_coop_rows(unsigned long long out[32], int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_coop_rows), 32 * sizeof(unsigned long long)) != hipSuccess) return 1;
@@ -2410,27 +2232,6 @@ extern "C" int icp_debug_coop_profile(unsigned long long out[12], int reset) {
   if (reset) {
     memset(all, 0, sizeof(all));
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_coop_prof), all, sizeof(all)) != hipSuccess) return 1;
-  }
-  return 0;
-}
-#endif
-#ifdef ICP_NN_STATS
-extern "C" int icp_debug_nn_warm(unsigned long long out[8 + 64], int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_warm), 8 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  if (hipMemcpyFromSymbol(out + 8, HIP_SYMBOL(g_nn_warm_hist), 64 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  if (reset) {
-    unsigned long long z[64] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_nn_warm), z, 8 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_nn_warm_hist), z, sizeof(z)) != hipSuccess) return 1;
-  }
-  return 0;
-}
-
-extern "C" int icp_debug_nn_stats(unsigned long long out[8], int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_stats), 8 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  if (reset) {
-    const unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_nn_stats), z, sizeof(z)) != hipSuccess) return 1;
   }
   return 0;
 }

@@ -285,10 +285,7 @@ int pipe_run(PipeRank *rk, int nranks, int world, size_t n_total, Pose *T_io, si
       ev[1].T = T1;
       ev[1].P = W2.P;
       const int bufs[2] = {nxt, cur};
-      for (int j = 0; j < nranks; ++j) {
-        ++rk[j].h->ws.win_tried;
-        ++rk[j].h->ws.pre_evals;
-      }
+      for (int j = 0; j < nranks; ++j) ++rk[j].h->ws.win_tried;
       ICP_TRY_RC(launch_evals(ev, 2, bufs));
       ahead_issued = false;
       if (it + 2 < max_iter) ICP_TRY_RC(ahead_all(nxt2, it + 2, &ahead_issued));

@@ -43,8 +43,7 @@ int icp_run_ahead_counters(icp_handle *h, uint64_t out[2]);
  * a query whose previous match is provably still its nearest neighbour -- it has moved less than the margin the
  * last walk left it -- is not searched again).  out[0] = searches that checked certificates
  * since the handle was created, out[1] = queries whose certificate failed in the last of them (searched as ever).
- * (ICP_NN_NO_CERT=1 searches every query every time -- in the development build libicp_mi355x_exp.so only: the product
- * library reads no tuning variables) */
+ * (The library reads no tuning variables) */
 int icp_nn_cert_counters(icp_handle *h, uint64_t out[2]);
 
 int icp_single_launch_counters(icp_handle *h, uint64_t out[3]);

@@ -1,5 +1,5 @@
 """Lines of icp_rust_amd/csrc that the DEFAULT build (libicp_mi355x.so: none of the development macros defined) compiles,
-next to the lines of the files: what `make experiments` / the profiling variants add is behind #ifdef.  VERDICT r4 item 7
+next to the lines of the files: what the profiling variants add is behind #ifdef.  VERDICT r4 item 7
 asked for the default library to shed device code; this is the count that says by how much.
 usage: python profiles/default_lines.py [git-rev]   (a revision: count that tree instead of the working copy)"""
 import os
@@ -9,8 +9,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "icp_rust_amd/csrc"
-DEV = {"ICP_EXPERIMENTS", "ICP_NN_STATS", "ICP_COOP_PROFILE", "ICP_WIN_DEBUG", "ICP_LOOP_PROFILE", "ICP_TILE_PROFILE",
-       "ICP_HACK_CAP", "ICP_TINY_PROFILE", "ICP_QS_DEBUG", "ICP_FAST_PROFILE", "ICP_PICK_PROFILE"}
+DEV = {"ICP_COOP_PROFILE", "ICP_WIN_DEBUG", "ICP_LOOP_PROFILE", "ICP_TILE_PROFILE", "ICP_TINY_PROFILE", "ICP_QS_DEBUG",
+       "ICP_FAST_PROFILE", "ICP_PICK_PROFILE"}
 
 
 def default_lines(text):

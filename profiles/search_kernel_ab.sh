@@ -1,6 +1,6 @@
 #!/bin/bash
 # average duration of the steady-state search kernel for a list of library builds (names after icp_rust_amd/lib/libicp_), one box:
-#   bash profiles/search_kernel_ab.sh mi355x ab_heads mi355x_exp:ICP_GRID_FX=8 ...   (name[:ENV=value]...)
+#   bash profiles/search_kernel_ab.sh mi355x ab_heads ...   (name[:ENV=value]...)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 B="--brute-steps 0 --cpu-iters 0 --gn-points 0 --nn-points 0 --converging-calls 0 --rotating-calls 0"
 for round in 1 2; do
