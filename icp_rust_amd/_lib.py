@@ -26,6 +26,13 @@ class Pose(C.Structure):
         return (self.r00, self.r10, self.r01, self.r11, self.tx, self.ty)
 
 
+class BatchItem(C.Structure):
+    """`icp_batch_item`: one registration of a batch call -- ranges of the call's src / dst arrays and a pose."""
+
+    _fields_ = [("src_first", C.c_uint64), ("n", C.c_uint64), ("dst_first", C.c_uint64), ("m", C.c_uint64),
+                ("init", Pose)]
+
+
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)]
@@ -171,6 +178,11 @@ SIGNATURES = {
     "icp_multi_compute_target_normals": (C.c_int, [_vp, C.c_int]),
     "icp_multi_update_target_normals": (C.c_int, [_vp, C.c_int]),
     "icp_multi_estimate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _pp, _sz, _pp, _vp, _vp]),
+    "icp_batch_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
+    "icp_batch_destroy": (None, [_vp]),
+    "icp_batch_estimate": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "icp_batch_estimate_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "icp_batch_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

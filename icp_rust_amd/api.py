@@ -696,3 +696,140 @@ class IcpMulti:
             self.close()
         except Exception:
             pass
+
+
+class IcpBatch:
+    """Many small registrations in one call (icp_batch_*, include/icp_mi355x.h section 8) -- an extension beyond the
+    reference, which registers one pair per Icp{2,3}d::estimate.  Item i's result is what
+    Icp{2,3}d(dst_i).estimate(src_i, init_i, max_iter) returns on its own handle, bit for bit; items of up to 1024
+    source and 2048 target points run as one workgroup each of a single launch, larger ones one by one.  One call in
+    flight per object."""
+
+    def __init__(self, dim, device=-1):
+        if dim not in (2, 3):
+            raise ValueError("dim must be 2 or 3")
+        self.DIM = dim
+        self._device = device if device >= 0 else None
+        self._b = C.c_void_p()
+        check(lib().icp_batch_create(C.byref(self._b), dim, device), "icp_batch_create")
+
+    def _pack(self, clouds, what):
+        """one array for all clouds; an entry that is the same object as an earlier one is packed once and shared"""
+        seen, parts, firsts, counts, at = {}, [], [], [], 0
+        for c in clouds:
+            if id(c) not in seen:
+                a = _host(c, self.DIM)
+                seen[id(c)] = (at, a.shape[0])
+                parts.append(a)
+                at += a.shape[0]
+            f, k = seen[id(c)]
+            firsts.append(f)
+            counts.append(k)
+        packed = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, self.DIM))
+        return packed, firsts, counts
+
+    @staticmethod
+    def _inits(inits, count):
+        if inits is None:
+            return [Transform() for _ in range(count)]
+        if isinstance(inits, Transform):
+            return [inits] * count
+        inits = list(inits)
+        if len(inits) != count:
+            raise ValueError(f"{len(inits)} initial transforms for {count} items")
+        return inits
+
+    def estimate(self, srcs, dsts, inits, max_iter, return_info=False, allow_failures=False):
+        """Register srcs[i] against dsts[i] from inits[i] (a list, one Transform for all, or None: identity).  Returns
+        the list of Transforms; with return_info also the per-item indices, the inner counts (count x max_iter) and the
+        statuses.  A failed item raises IcpError naming it, unless allow_failures=True (its Transform is then None)."""
+        srcs, dsts = list(srcs), list(dsts)
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
+        src, sf, sn = self._pack(srcs, "src")
+        dst, df, dm = self._pack(dsts, "dst")
+        items = list(zip(sf, sn, df, dm, self._inits(inits, len(srcs))))
+        return self.estimate_packed(src, dst, items, max_iter, return_info, allow_failures)
+
+    def estimate_packed(self, src, dst, items, max_iter, return_info=False, allow_failures=False):
+        """The same over pre-packed clouds: `items` = [(src_first, n, dst_first, m, init Transform), ...] ranges of
+        `src` / `dst` (ranges may overlap).  numpy arrays go through icp_batch_estimate; contiguous float64 CUDA tensors
+        through icp_batch_estimate_device, in place."""
+        count = len(items)
+        arr = (_lib.BatchItem * max(count, 1))()
+        for i, (f, n, g, m, T) in enumerate(items):
+            arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
+            C.memmove(C.byref(arr[i].init), C.byref(T.pose), C.sizeof(Pose))
+        out = (Pose * max(count, 1))()
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        inner = np.zeros(max(count * max_iter, 1), dtype=np.uint32)
+        total = sum(int(it[1]) for it in items)
+        want_idx = bool(return_info)
+        if _is_device_tensor(src) or _is_device_tensor(dst):
+            import torch
+
+            if self._device is None:
+                self._device = src.device.index
+            _dev_points(src, self.DIM, self._device, "src")
+            _dev_points(dst, self.DIM, self._device, "dst")
+            for t in (src, dst):  # (the batch's own stream is not ordered against the producer's)
+                torch.cuda.current_stream(t.device).synchronize()
+            idx = torch.zeros(max(total, 1), dtype=torch.int32, device=src.device) if want_idx else None
+            check(lib().icp_batch_estimate_device(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
+                                                  C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count, max_iter, out,
+                                                  C.c_void_p(status.ctypes.data),
+                                                  C.c_void_p(idx.data_ptr()) if want_idx else None,
+                                                  C.c_void_p(inner.ctypes.data)), "icp_batch_estimate_device")
+            idx = idx.cpu().numpy().view(np.uint32) if want_idx else None
+        else:
+            s, d = _host(src, self.DIM), _host(dst, self.DIM)
+            idx = np.zeros(max(total, 1), dtype=np.uint32) if want_idx else None
+            check(lib().icp_batch_estimate(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, max_iter,
+                                           out, C.c_void_p(status.ctypes.data),
+                                           C.c_void_p(idx.ctypes.data) if want_idx else None,
+                                           C.c_void_p(inner.ctypes.data)), "icp_batch_estimate")
+        status = status[:count]
+        Ts = []
+        for i in range(count):
+            if status[i] != _lib.OK:
+                if not allow_failures:
+                    raise IcpError(int(status[i]), f"icp_batch_estimate item {i}")
+                Ts.append(None)
+            else:
+                Ts.append(Transform.from_pose(out[i]))
+        if not return_info:
+            return Ts
+        idxs, at = [], 0
+        for it in items:
+            idxs.append(idx[at:at + int(it[1])])
+            at += int(it[1])
+        return Ts, idxs, inner[:count * max_iter].reshape(count, max_iter), status
+
+    def estimate_hypotheses(self, src, dst, inits, max_iter):
+        """One scan against one map from K initial poses (one shared src range and dst range: nothing is copied per
+        hypothesis).  Returns (Transforms, errors): errors[k] is huber_error of the k-th result on its last
+        correspondences (src/lib.rs:45-50, xy of the points), so that the caller can keep the best hypothesis."""
+        s, d = _host(src, self.DIM), _host(dst, self.DIM)
+        inits = self._inits(inits, len(inits) if not isinstance(inits, Transform) else 1)
+        items = [(0, s.shape[0], 0, d.shape[0], T) for T in inits]
+        Ts, idxs, _, _ = self.estimate_packed(s, d, items, max_iter, return_info=True)
+        a = np.ascontiguousarray(s[:, :2])
+        errs = [huber_error(T, a, np.ascontiguousarray(d[ix.astype(np.int64), :2])) for T, ix in zip(Ts, idxs)]
+        return Ts, np.array(errs)
+
+    def counters(self):
+        """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_counters(self._b, out), "icp_batch_counters")
+        return tuple(int(x) for x in out)
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b.value:
+            lib().icp_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

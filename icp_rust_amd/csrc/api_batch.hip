@@ -1,0 +1,264 @@
+// C ABI, EXTENSION beyond the reference (include/icp_mi355x.h section 8): many small registrations in one call.
+// The items that fit one workgroup run as k_tiny_estimate_batch (gn_fast.hip), one workgroup each, in at most three
+// launches (one per workgroup size); the rest go one by one through a handle of the pool, exactly as a single call would
+// serve them.  Every item's bits are those of icp_create + icp_estimate on its own ranges.
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/icp_mi355x_debug.h"
+#include "api_internal.hpp"
+
+using namespace icp;
+using namespace icp::api;
+
+struct icp_batch {
+  int dim = 2, device = 0;
+  hipStream_t stream = nullptr;
+  // staged copies of the host entry's clouds, and the indices the host entry reads back
+  double *d_src = nullptr, *d_dst = nullptr;
+  size_t cap_src = 0, cap_dst = 0;
+  uint32_t *d_idx = nullptr;
+  size_t cap_idx = 0;
+  // the launches' item lists: built in pinned memory, copied once per call
+  TinyBatchItem *d_items = nullptr, *h_items = nullptr;
+  size_t cap_items = 0, cap_h_items = 0;
+  TinyResult *h_res = nullptr;  // pinned: the workgroups write their results here, one per item of the call
+  size_t cap_res = 0;
+  uint32_t *h_inner = nullptr;  // pinned: count x max_iter inner counts
+  size_t cap_inner = 0;
+  uint64_t ctr[4] = {0, 0, 0, 0};  // icp_batch_counters
+};
+
+namespace {
+
+template <typename Tp>
+hipError_t reserve_pinned(Tp *&p, size_t &cap, size_t need) {
+  if (need <= cap && p) return hipSuccess;
+  if (p) {
+    (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  const size_t want = need + need / 8 + 1;
+  const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), want * sizeof(Tp), hipHostMallocDefault);
+  if (e == hipSuccess) cap = want;
+  return e;
+}
+
+bool in_range(uint64_t first, uint64_t count, size_t points) { return first <= points && count <= points - first; }
+
+// every argument, before anything touches the device
+int check_args(const icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+               const icp_batch_item *items, size_t count, size_t max_iter, const icp_pose *out, const int *status,
+               const uint32_t *inner_iters) {
+  if (!b) return ICP_BAD_ARGUMENT;
+  if (count == 0) return ICP_OK;
+  if (!items || !out || !status || count > 0x7fffffffu) return ICP_BAD_ARGUMENT;  // (one workgroup per item)
+  const size_t point_bytes = (size_t)b->dim * sizeof(double);
+  if ((src_points > 0 && !src) || (dst_points > 0 && !dst) || src_points > SIZE_MAX / point_bytes ||
+      dst_points > SIZE_MAX / point_bytes)
+    return ICP_BAD_ARGUMENT;
+  if (inner_iters && max_iter > 0 && count > SIZE_MAX / sizeof(uint32_t) / max_iter) return ICP_BAD_ARGUMENT;
+  for (size_t i = 0; i < count; ++i) {
+    const icp_batch_item &it = items[i];
+    if (!in_range(it.src_first, it.n, src_points) || !in_range(it.dst_first, it.m, dst_points)) return ICP_BAD_ARGUMENT;
+    if (it.n >= 0xffffffffull || it.m >= 0xffffffffull) return ICP_BAD_ARGUMENT;  // (as icp_create / icp_estimate)
+  }
+  return ICP_OK;
+}
+
+bool tiny_fits(const icp_batch_item &it, size_t max_iter) {
+  return it.n >= 1 && it.n <= kTinyMaxN && it.m >= 1 && it.m <= kTinyMaxM && max_iter >= 1 && max_iter <= kTinyMaxIter;
+}
+
+// Item i the way a single call serves it: a handle of the pool on the item's targets, icp_estimate_device on its
+// sources.  Per-item outcomes land in *status; anything else (HIP, memory, device) is the call's failure.
+int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter,
+              icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner) {
+  icp_handle *h = nullptr;
+  int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
+  if (rc == ICP_OK) {
+    rc = icp_estimate_device(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr, (size_t)it.n, &it.init, max_iter, out,
+                             d_idx, inner);
+    icp_destroy(h);
+  }
+  if (rc == ICP_OK || rc == ICP_NONE || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT) {
+    *status = rc;
+    return ICP_OK;
+  }
+  return rc;
+}
+
+int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
+        size_t max_iter, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
+  // where each item's indices go, and which items a workgroup may serve, by workgroup size
+  std::vector<uint64_t> idx_first(count);
+  std::vector<size_t> cls[3], one_by_one;
+  uint64_t at = 0;
+  for (size_t i = 0; i < count; ++i) {
+    idx_first[i] = at;
+    at += items[i].n;
+    if (tiny_fits(items[i], max_iter)) {
+      const unsigned t = tiny_threads(items[i].n);
+      cls[t == 512u ? 0 : (t == 768u ? 1 : 2)].push_back(i);
+    } else {
+      one_by_one.push_back(i);
+    }
+  }
+  const size_t n_tiny = cls[0].size() + cls[1].size() + cls[2].size();
+  std::vector<size_t> handed_back;
+  if (n_tiny > 0) {
+    HIP_TRY(reserve_pinned(b->h_items, b->cap_h_items, n_tiny));
+    HIP_TRY(reserve(b->d_items, b->cap_items, n_tiny));
+    HIP_TRY(reserve_pinned(b->h_res, b->cap_res, count));
+    if (inner_iters) HIP_TRY(reserve_pinned(b->h_inner, b->cap_inner, count * max_iter));
+    size_t k = 0;
+    unsigned m_max[3] = {0, 0, 0};
+    for (int c = 0; c < 3; ++c)
+      for (size_t i : cls[c]) {
+        TinyBatchItem &d = b->h_items[k++];
+        d.src_first = items[i].src_first;
+        d.dst_first = items[i].dst_first;
+        d.idx_first = idx_first[i];
+        d.n = (unsigned)items[i].n;
+        d.m = (unsigned)items[i].m;
+        d.slot = (unsigned)i;
+        d.pad = 0;
+        d.init = items[i].init;
+        if (d.m > m_max[c]) m_max[c] = d.m;
+        b->h_res[i].status = -1;
+      }
+    HIP_TRY(hipMemcpyAsync(b->d_items, b->h_items, n_tiny * sizeof(TinyBatchItem), hipMemcpyHostToDevice, b->stream));
+    static const unsigned kThreads[3] = {512u, 768u, 1024u};
+    size_t first = 0;
+    bool granted = true;
+    for (int c = 0; c < 3; ++c) {
+      if (cls[c].empty()) continue;
+      HIP_TRY(launch_tiny_estimate_batch(b->dim, kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
+                                         (unsigned)cls[c].size(), (unsigned)max_iter, b->h_res,
+                                         inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
+      ++b->ctr[granted ? 2 : 3];
+      first += cls[c].size();
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (int c = 0; c < 3; ++c)
+      for (size_t i : cls[c]) {
+        const TinyResult &r = b->h_res[i];
+        if (!granted || r.status == -1) {
+          handed_back.push_back(i);
+          continue;
+        }
+        ++b->ctr[0];
+        if (r.status == 3) {
+          status[i] = ICP_NAN_INPUT;
+          continue;
+        }
+        status[i] = ICP_OK;
+        out[i] = r.pose;
+        if (inner_iters) std::memcpy(inner_iters + i * max_iter, b->h_inner + i * max_iter, max_iter * sizeof(uint32_t));
+      }
+  }
+  one_by_one.insert(one_by_one.end(), handed_back.begin(), handed_back.end());
+  for (size_t i : one_by_one) {
+    ICP_TRY_RC(serve_one(b, d_src, d_dst, items[i], max_iter, &out[i], &status[i], d_idx ? d_idx + idx_first[i] : nullptr,
+                         inner_iters ? inner_iters + i * max_iter : nullptr));
+    ++b->ctr[1];
+  }
+  return ICP_OK;
+}
+
+}  // namespace
+
+// The device is not touched here: the first call that computes resolves it and creates the stream (so that a batch, and
+// every argument check of its calls, exists without a GPU).
+extern "C" int icp_batch_create(icp_batch **out, int dim, int device) {
+  if (!out || (dim != 2 && dim != 3) || device < -1) return ICP_BAD_ARGUMENT;
+  *out = nullptr;
+  icp_batch *b = new (std::nothrow) icp_batch();
+  if (!b) return ICP_OUT_OF_MEMORY;
+  b->dim = dim;
+  b->device = device;
+  *out = b;
+  return ICP_OK;
+}
+
+namespace {
+
+int ensure_device(icp_batch *b) {
+  if (b->stream) return hipSetDevice(b->device) == hipSuccess ? ICP_OK : ICP_HIP_ERROR;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return ICP_NO_DEVICE;
+  int device = b->device;
+  if (device < 0) HIP_TRY(hipGetDevice(&device));
+  if (device >= count) return ICP_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  b->device = device;
+  return ICP_OK;
+}
+
+}  // namespace
+
+extern "C" void icp_batch_destroy(icp_batch *b) {
+  if (!b) return;
+  if (b->stream) {
+    (void)hipSetDevice(b->device);
+    (void)hipStreamSynchronize(b->stream);
+    (void)hipFree(b->d_src);
+    (void)hipFree(b->d_dst);
+    (void)hipFree(b->d_idx);
+    (void)hipFree(b->d_items);
+    if (b->h_items) (void)hipHostFree(b->h_items);
+    if (b->h_res) (void)hipHostFree(b->h_res);
+    if (b->h_inner) (void)hipHostFree(b->h_inner);
+    (void)hipStreamDestroy(b->stream);
+  }
+  delete b;
+}
+
+extern "C" int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                         size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
+                                         icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
+  ICP_TRY_RC(check_args(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, out, status, inner_iters));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  return run(b, d_src, d_dst, items, count, max_iter, out, status, d_last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                                  const icp_batch_item *items, size_t count, size_t max_iter, icp_pose *out, int *status,
+                                  uint32_t *last_idx, uint32_t *inner_iters) {
+  ICP_TRY_RC(check_args(b, src, src_points, dst, dst_points, items, count, max_iter, out, status, inner_iters));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  size_t total_n = 0;
+  for (size_t i = 0; i < count; ++i) total_n += items[i].n;
+  if (src_points > 0) {
+    HIP_TRY(reserve(b->d_src, b->cap_src, src_points * b->dim));
+    HIP_TRY(hipMemcpyAsync(b->d_src, src, src_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
+  if (dst_points > 0) {
+    HIP_TRY(reserve(b->d_dst, b->cap_dst, dst_points * b->dim));
+    HIP_TRY(hipMemcpyAsync(b->d_dst, dst, dst_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
+  // (as icp_estimate: no outer iteration, no correspondences -- last_idx is left as it was)
+  const bool want_idx = last_idx && total_n > 0 && max_iter > 0;
+  if (want_idx) HIP_TRY(reserve(b->d_idx, b->cap_idx, total_n));
+  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const int rc = run(b, src_points > 0 ? b->d_src : nullptr, dst_points > 0 ? b->d_dst : nullptr, items, count, max_iter,
+                     out, status, want_idx ? b->d_idx : nullptr, inner_iters);
+  if (rc != ICP_OK) return rc;
+  if (want_idx) {
+    HIP_TRY(hipMemcpyAsync(last_idx, b->d_idx, total_n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+  }
+  return ICP_OK;
+}
+
+extern "C" int icp_batch_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->ctr[q];
+  return ICP_OK;
+}

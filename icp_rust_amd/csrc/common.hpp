@@ -483,8 +483,37 @@ hipError_t launch_weighted_gn_fast(icp_handle *h, const double *d_a, const doubl
 hipError_t launch_weighted_gn_pull(icp_handle *h, const double *d_a, const double *d_b, size_t n,
                                    const Pose &T);
 // the whole Icp::estimate of a small cloud in one launch (gn_fast.hip); *status = -1: not served
+struct TinyResult {  // pinned host memory
+  Pose pose;
+  int status;       // 0 ok, 3 NaN residual (ICP_NAN_INPUT), -1 hand the call to the host-driven path
+  unsigned evals;   // Gauss-Newton evaluations run, in all
+  unsigned sorted;  // ... of which by the sorting path
+  unsigned pad;
+  unsigned long long t[6];  // ICP_TINY_PROFILE builds: shader cycles in {setup, search, selections, sums, step, all}
+  unsigned long long ts[8]; // ... and inside the selections, per phase
+};
+constexpr unsigned kTinyMaxN = 1024, kTinyMaxM = 2048, kTinyMaxIter = 1024;
 hipError_t launch_tiny_estimate(icp_handle *h, const double *d_src, size_t n, const Pose &T0, size_t max_iter,
                                 Pose *out, uint32_t *d_last_idx, uint32_t *inner_iters, int *status);
+// Many such registrations in one launch, one workgroup per item (gn_fast.hip: k_tiny_estimate_batch; api_batch.hip
+// drives it).  An item's points are ranges of the launch's src / dst arrays (ranges may overlap); it writes
+// res[slot], inner[slot * max_iter ...] (nullable) and idx[idx_first ...] (n entries, nullable).
+struct TinyBatchItem {
+  unsigned long long src_first, dst_first, idx_first;  // first source point, first target point, first index slot
+  unsigned n, m;                                       // 1 <= n <= kTinyMaxN, 1 <= m <= kTinyMaxM
+  unsigned slot, pad;                                  // the item's position in the call
+  Pose init;
+};
+// workgroup size of an item with n source points (a thread per point; the smallest of 512 / 768 / 1024 that holds it)
+inline unsigned tiny_threads(size_t n) { return n <= 512 ? 512u : (n <= 768 ? 768u : 1024u); }
+// dynamic LDS of one workgroup whose targets number at most m
+size_t tiny_lds_bytes_of(int dim, unsigned m);
+// one launch over `count` items that all take `threads` threads, with the dynamic LDS of the largest m among them.
+// *granted = false: the runtime refused the kernels their 160 KB of LDS (asked once per process) -- nothing was launched
+// and the caller serves the items otherwise.
+hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                      const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
+                                      uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
 // three launches around a predicted window (gn_win.hip); h_res->overflow == 2 when it missed
 bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind = 2, bool any_n = false,
                    double f_override = 0.);

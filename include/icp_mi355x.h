@@ -58,7 +58,9 @@ extern "C" {
 /* 7: additions only (section 5c: icp_shard_pipe_run_device, the pipelined sharded registration; icp_pipe_counters,
  * icp_multi_pipe_iterations in icp_mi355x_debug.h).  Behavioural note: icp_multi_estimate and the sharded drivers serve
  * the steady state of a registration through it (same bits) */
-#define ICP_ABI_VERSION 7
+/* 8: additions only (section 8: icp_batch_*, many small registrations in one launch; icp_batch_counters in
+ * icp_mi355x_debug.h).  Everything of version 7 is unchanged */
+#define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
   ICP_OK = 0,
@@ -495,6 +497,41 @@ int icp_multi_compute_target_normals(icp_multi *M, int k);
 int icp_multi_update_target_normals(icp_multi *M, int k);
 int icp_multi_estimate_point_to_plane(icp_multi *M, const double *src, size_t n, const icp_pose *init, size_t max_iter,
                                       icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters);
+
+/* ================================================================================
+ * 8. EXTENSION (not in the reference): many small registrations in one call
+ * ==============================================================================
+ * Loop-closure candidates, K initial poses of one scan against one map, a recorded sequence against fixed keyframes:
+ * independent registrations of small clouds.  One call runs every item whose clouds fit one workgroup (n <= 1024
+ * source points, 1 <= m <= 2048 targets, 1 <= max_iter <= 1024) as one workgroup of ONE launch per workgroup size
+ * (at most three launches), the other items -- and those a workgroup hands back -- through icp_create_device +
+ * icp_estimate_device on the item's ranges, one after another.  Item i's out[i], status[i], indices and inner counts
+ * are what icp_create(dim, dst + dst_first, m) + icp_estimate(src + src_first, n, &init, max_iter) return on a fresh
+ * handle, bit for bit.  out[i] is meaningful when status[i] == ICP_OK; per-item statuses are ICP_OK, ICP_EMPTY_DST and
+ * ICP_NAN_INPUT.  The call's own return value is ICP_OK or a whole-call failure: ICP_BAD_ARGUMENT (a bad dim, an item
+ * range outside its array, NULL where a pointer is required -- all checked before the device is touched),
+ * ICP_NO_DEVICE, ICP_HIP_ERROR, ICP_OUT_OF_MEMORY.  count == 0 is a successful no-op.
+ * Ranges may overlap (K hypotheses of one scan against one map share one src range and one dst range: no copies).
+ * last_idx (nullable): each item's final correspondences (indices into its own dst range), concatenated in item
+ * order, sum(n) entries; inner_iters (nullable): count x max_iter, item-major.
+ * An icp_batch keeps a stream, pinned result buffers and the device item lists between calls; one call in flight per
+ * icp_batch (as for handles).  icp_batch_create does not touch the device (device < 0: the current one, resolved by
+ * the first call that computes); every argument of a call is checked before the device is.  The _device entry reads src / dst from device memory that must be complete when the
+ * call is made, and writes d_last_idx on the device; out / status / inner_iters are host memory in both entries. */
+typedef struct icp_batch icp_batch;
+typedef struct icp_batch_item {
+  uint64_t src_first, n; /* source points [src_first, src_first + n) of the call's src array */
+  uint64_t dst_first, m; /* target points [dst_first, dst_first + m) of the call's dst array */
+  icp_pose init;
+} icp_batch_item;
+int icp_batch_create(icp_batch **out, int dim, int device);
+void icp_batch_destroy(icp_batch *b);
+int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                       const icp_batch_item *items, size_t count, size_t max_iter, icp_pose *out, int *status,
+                       uint32_t *last_idx, uint32_t *inner_iters);
+int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                              size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
+                              icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters);
 
 #ifdef __cplusplus
 }

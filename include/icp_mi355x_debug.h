@@ -80,6 +80,12 @@ int icp_set_fixed_point_exit(icp_handle *h, int enable);
  * ascending index -- the order icp_last_fold_order documents.  bits: the keys' significant bits (1 .. 32). */
 int icp_debug_sort_cells(const uint32_t *keys, size_t n, unsigned bits, uint32_t *keys_out, uint32_t *perm_out);
 
+/* Batched small registrations (icp_mi355x.h section 8), since icp_batch_create: out[0] items served inside a batch
+ * launch, out[1] items served one by one through icp_create_device + icp_estimate_device (too large, handed back by
+ * their workgroup, or no LDS grant), out[2] batch launches, out[3] launches not made because the runtime refused the
+ * kernels their LDS (every item of those went one by one). */
+int icp_batch_counters(icp_batch *b, uint64_t out[4]);
+
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
  * costs a few us of stream time, so the benchmark samples instead of timing every launch);
