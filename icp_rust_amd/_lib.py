@@ -33,6 +33,14 @@ class BatchItem(C.Structure):
                 ("init", Pose)]
 
 
+class QualityStruct(C.Structure):
+    """`icp_quality` (include/icp_mi355x.h section 9): the quality of a pose; icp_rust_amd.Quality wraps it."""
+
+    _fields_ = [("n", C.c_uint64), ("inliers", C.c_uint64), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("inlier_sum_d2", C.c_double), ("error", C.c_double), ("huber_error", C.c_double),
+                ("information", C.c_double * 9)]
+
+
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)]
@@ -183,6 +191,11 @@ SIGNATURES = {
     "icp_batch_estimate": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "icp_batch_estimate_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "icp_batch_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_evaluate": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
+    "icp_evaluate_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
+    "icp_batch_evaluate": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_double, _vp, _vp]),
+    "icp_batch_evaluate_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_double, _vp, _vp]),
+    "icp_batch_evaluate_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

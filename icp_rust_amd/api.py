@@ -316,6 +316,32 @@ def nn_cert_counters(icp):
     return int(out[0]), int(out[1])
 
 
+class Quality:
+    """The quality of a pose (`icp_quality`, include/icp_mi355x.h section 9) -- an extension beyond the reference.
+    n source points; inliers, those whose nearest target lies within the distance bound; fitness = inliers / n;
+    inlier_rmse and inlier_sum_d2 of the inliers' squared distances; error and huber_error, the reference's icp::error /
+    huber_error of the correspondences at the pose (src/lib.rs:38-50); information, the 3 x 3 SE(2) information matrix
+    of the inlier pairs in (x, y, theta) (the jtj of gauss_newton_update at identity, src/lib.rs:191-216)."""
+
+    __slots__ = ("n", "inliers", "fitness", "inlier_rmse", "inlier_sum_d2", "error", "huber_error", "information")
+
+    def __init__(self, q):
+        self.n, self.inliers = int(q.n), int(q.inliers)
+        self.fitness, self.inlier_rmse, self.inlier_sum_d2 = q.fitness, q.inlier_rmse, q.inlier_sum_d2
+        self.error, self.huber_error = q.error, q.huber_error
+        self.information = np.array(q.information[:], dtype=np.float64).reshape(3, 3)
+
+    def as_array(self):
+        """the float fields in struct order (fitness, inlier_rmse, inlier_sum_d2, error, huber_error, information
+        row-major): what a bit-for-bit comparison compares, next to n and inliers"""
+        return np.array([self.fitness, self.inlier_rmse, self.inlier_sum_d2, self.error, self.huber_error,
+                         *self.information.ravel()])
+
+    def __repr__(self):
+        return (f"Quality(n={self.n}, inliers={self.inliers}, fitness={self.fitness:.6g}, "
+                f"inlier_rmse={self.inlier_rmse:.6g}, error={self.error:.6g}, huber_error={self.huber_error:.6g})")
+
+
 class _Icp:
     DIM = 0
 
@@ -427,6 +453,31 @@ class _Icp:
         if return_info:
             return o, idx[:n], inner[:max_iter]
         return o
+
+    # -- EXTENSION (not in the reference): the quality of a pose, include/icp_mi355x.h section 9 --
+    def evaluate(self, src, transform, max_correspondence_distance=float("inf"), return_indices=False):
+        """The Quality of `transform` (icp_evaluate[_device]): the handle's exact correspondences at that pose, the
+        inliers within max_correspondence_distance, the reference's error / huber_error and the SE(2) information
+        matrix.  The handle's registration state is left as it was.  return_indices=True also returns the
+        correspondences (caller order).  numpy arrays or contiguous float64 CUDA tensors (used in place)."""
+        q = _lib.QualityStruct()
+        r = float(max_correspondence_distance)
+        if _is_device_tensor(src):
+            import torch
+
+            self._dev(src, "src")
+            n = src.shape[0]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_indices else None
+            check(lib().icp_evaluate_device(self._h, C.c_void_p(src.data_ptr()), n, C.byref(transform.pose), r,
+                                            C.byref(q), C.c_void_p(idx.data_ptr()) if return_indices else None),
+                  "icp_evaluate_device")
+            return (Quality(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else Quality(q)
+        s = _host(src, self.DIM)
+        n = s.shape[0]
+        idx = np.zeros(max(n, 1), dtype=np.uint32) if return_indices else None
+        check(lib().icp_evaluate(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
+                                 C.c_void_p(idx.ctypes.data) if return_indices else None), "icp_evaluate")
+        return (Quality(q), idx[:n]) if return_indices else Quality(q)
 
     def set_single_launch(self, enable=True):
         """small clouds: whole estimate in one launch (default on); off = the general host-driven path"""
@@ -808,7 +859,8 @@ class IcpBatch:
     def estimate_hypotheses(self, src, dst, inits, max_iter):
         """One scan against one map from K initial poses (one shared src range and dst range: nothing is copied per
         hypothesis).  Returns (Transforms, errors): errors[k] is huber_error of the k-th result on its last
-        correspondences (src/lib.rs:45-50, xy of the points), so that the caller can keep the best hypothesis."""
+        correspondences (src/lib.rs:45-50, xy of the points), so that the caller can keep the best hypothesis.
+        (evaluate() scores poses on the device instead, on the correspondences AT each returned pose.)"""
         s, d = _host(src, self.DIM), _host(dst, self.DIM)
         inits = self._inits(inits, len(inits) if not isinstance(inits, Transform) else 1)
         items = [(0, s.shape[0], 0, d.shape[0], T) for T in inits]
@@ -816,6 +868,67 @@ class IcpBatch:
         a = np.ascontiguousarray(s[:, :2])
         errs = [huber_error(T, a, np.ascontiguousarray(d[ix.astype(np.int64), :2])) for T, ix in zip(Ts, idxs)]
         return Ts, np.array(errs)
+
+    # -- the quality of many poses in one call (icp_batch_evaluate*, include/icp_mi355x.h section 9) --
+    def evaluate(self, srcs, dsts, transforms, max_correspondence_distance=float("inf"), allow_failures=False,
+                 return_status=False):
+        """The Quality of transforms[i] for srcs[i] against dsts[i] (a list, one Transform for all, or None: identity):
+        item i equals Icp{2,3}d(dsts[i]).evaluate(srcs[i], transforms[i], max_correspondence_distance), bit for bit.
+        A failed item raises IcpError naming it, unless allow_failures=True (its Quality is then None);
+        return_status=True also returns the statuses."""
+        srcs, dsts = list(srcs), list(dsts)
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
+        src, sf, sn = self._pack(srcs, "src")
+        dst, df, dm = self._pack(dsts, "dst")
+        items = list(zip(sf, sn, df, dm, self._inits(transforms, len(srcs))))
+        return self.evaluate_packed(src, dst, items, max_correspondence_distance, allow_failures, return_status)
+
+    def evaluate_packed(self, src, dst, items, max_correspondence_distance=float("inf"), allow_failures=False,
+                        return_status=False):
+        """The same over pre-packed clouds: `items` = [(src_first, n, dst_first, m, Transform), ...] ranges of `src` /
+        `dst` (ranges may overlap).  numpy arrays go through icp_batch_evaluate; contiguous float64 CUDA tensors through
+        icp_batch_evaluate_device, in place."""
+        count = len(items)
+        arr = (_lib.BatchItem * max(count, 1))()
+        for i, (f, n, g, m, T) in enumerate(items):
+            arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
+            C.memmove(C.byref(arr[i].init), C.byref(T.pose), C.sizeof(Pose))
+        out = (_lib.QualityStruct * max(count, 1))()
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        r = float(max_correspondence_distance)
+        if _is_device_tensor(src) or _is_device_tensor(dst):
+            import torch
+
+            if self._device is None:
+                self._device = src.device.index
+            _dev_points(src, self.DIM, self._device, "src")
+            _dev_points(dst, self.DIM, self._device, "dst")
+            for t in (src, dst):  # (the batch's own stream is not ordered against the producer's)
+                torch.cuda.current_stream(t.device).synchronize()
+            check(lib().icp_batch_evaluate_device(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
+                                                  C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count, r, out,
+                                                  C.c_void_p(status.ctypes.data)), "icp_batch_evaluate_device")
+        else:
+            s, d = _host(src, self.DIM), _host(dst, self.DIM)
+            check(lib().icp_batch_evaluate(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, r, out,
+                                           C.c_void_p(status.ctypes.data)), "icp_batch_evaluate")
+        status = status[:count]
+        qs = []
+        for i in range(count):
+            if status[i] != _lib.OK:
+                if not allow_failures:
+                    raise IcpError(int(status[i]), f"icp_batch_evaluate item {i}")
+                qs.append(None)
+            else:
+                qs.append(Quality(out[i]))
+        return (qs, status) if return_status else qs
+
+    def evaluate_counters(self):
+        """(items evaluated in a batch launch, items evaluated one by one, launches)"""
+        out = (C.c_uint64 * 3)()
+        check(lib().icp_batch_evaluate_counters(self._b, out), "icp_batch_evaluate_counters")
+        return tuple(int(x) for x in out)
 
     def counters(self):
         """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS)"""

@@ -28,6 +28,12 @@ struct icp_batch {
   uint32_t *h_inner = nullptr;  // pinned: count x max_iter inner counts
   size_t cap_inner = 0;
   uint64_t ctr[4] = {0, 0, 0, 0};  // icp_batch_counters
+  // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
+  QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
+  size_t cap_qitems = 0, cap_h_qitems = 0;
+  QualityPart *h_qres = nullptr;
+  size_t cap_qres = 0;
+  uint64_t qctr[3] = {0, 0, 0};  // icp_batch_evaluate_counters
 };
 
 namespace {
@@ -50,7 +56,7 @@ bool in_range(uint64_t first, uint64_t count, size_t points) { return first <= p
 
 // every argument, before anything touches the device
 int check_args(const icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
-               const icp_batch_item *items, size_t count, size_t max_iter, const icp_pose *out, const int *status,
+               const icp_batch_item *items, size_t count, size_t max_iter, const void *out, const int *status,
                const uint32_t *inner_iters) {
   if (!b) return ICP_BAD_ARGUMENT;
   if (count == 0) return ICP_OK;
@@ -212,6 +218,9 @@ extern "C" void icp_batch_destroy(icp_batch *b) {
     if (b->h_items) (void)hipHostFree(b->h_items);
     if (b->h_res) (void)hipHostFree(b->h_res);
     if (b->h_inner) (void)hipHostFree(b->h_inner);
+    (void)hipFree(b->d_qitems);
+    if (b->h_qitems) (void)hipHostFree(b->h_qitems);
+    if (b->h_qres) (void)hipHostFree(b->h_qres);
     (void)hipStreamDestroy(b->stream);
   }
   delete b;
@@ -260,5 +269,120 @@ extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_po
 extern "C" int icp_batch_counters(icp_batch *b, uint64_t out[4]) {
   if (!b || !out) return ICP_BAD_ARGUMENT;
   for (int q = 0; q < 4; ++q) out[q] = b->ctr[q];
+  return ICP_OK;
+}
+
+// ---- icp_batch_evaluate (include/icp_mi355x.h section 9): the quality of many poses in one launch ----
+// The items that fit one workgroup run as k_quality_batch (quality.hip), one workgroup each, in one launch; the rest go
+// one by one through a handle of the pool and icp_evaluate_device, exactly as a single call serves them.
+namespace {
+
+int check_quality_args(const icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                       const icp_batch_item *items, size_t count, double max_dist, const icp_quality *out,
+                       const int *status) {
+  if (!b || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, nullptr);
+}
+
+bool quality_fits(const icp_batch_item &it) {
+  return it.n >= 1 && it.n <= kQualityMaxN && it.m >= 1 && it.m <= kQualityMaxM;
+}
+
+int serve_quality_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, double max_dist,
+                      icp_quality *out, int *status) {
+  icp_handle *h = nullptr;
+  int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
+  if (rc == ICP_OK) {
+    rc = icp_evaluate_device(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr, (size_t)it.n, &it.init, max_dist,
+                             out, nullptr);
+    icp_destroy(h);
+  }
+  if (rc == ICP_OK || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT) {
+    *status = rc;
+    return ICP_OK;
+  }
+  return rc;
+}
+
+int run_quality(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
+                double max_dist, icp_quality *out, int *status) {
+  std::vector<size_t> fit, one_by_one;
+  unsigned m_max = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if (quality_fits(items[i])) {
+      fit.push_back(i);
+      if (items[i].m > m_max) m_max = (unsigned)items[i].m;
+    } else {
+      one_by_one.push_back(i);
+    }
+  }
+  if (!fit.empty()) {
+    HIP_TRY(reserve_pinned(b->h_qitems, b->cap_h_qitems, fit.size()));
+    HIP_TRY(reserve(b->d_qitems, b->cap_qitems, fit.size()));
+    HIP_TRY(reserve_pinned(b->h_qres, b->cap_qres, count));
+    for (size_t k = 0; k < fit.size(); ++k) {
+      const icp_batch_item &it = items[fit[k]];
+      QualityBatchItem &d = b->h_qitems[k];
+      d.src_first = it.src_first;
+      d.dst_first = it.dst_first;
+      d.n = (unsigned)it.n;
+      d.m = (unsigned)it.m;
+      d.slot = (unsigned)fit[k];
+      d.pad = 0;
+      d.T = it.init;
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_qitems, b->h_qitems, fit.size() * sizeof(QualityBatchItem), hipMemcpyHostToDevice,
+                           b->stream));
+    // (r * r in f64 on the host, as icp_evaluate_device forms it)
+    HIP_TRY(launch_quality_batch(b->dim, m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist,
+                                 b->h_qres, b->stream));
+    ++b->qctr[2];
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (size_t i : fit) {
+      status[i] = quality_result((size_t)items[i].n, b->h_qres[i], &out[i]);
+      ++b->qctr[0];
+    }
+  }
+  for (size_t i : one_by_one) {
+    ICP_TRY_RC(serve_quality_one(b, d_src, d_dst, items[i], max_dist, &out[i], &status[i]));
+    ++b->qctr[1];
+  }
+  return ICP_OK;
+}
+
+}  // namespace
+
+extern "C" int icp_batch_evaluate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                         size_t dst_points, const icp_batch_item *items, size_t count, double max_dist,
+                                         icp_quality *out, int *status) {
+  ICP_TRY_RC(check_quality_args(b, d_src, src_points, d_dst, dst_points, items, count, max_dist, out, status));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  return run_quality(b, d_src, d_dst, items, count, max_dist, out, status);
+}
+
+extern "C" int icp_batch_evaluate(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                  size_t dst_points, const icp_batch_item *items, size_t count, double max_dist,
+                                  icp_quality *out, int *status) {
+  ICP_TRY_RC(check_quality_args(b, src, src_points, dst, dst_points, items, count, max_dist, out, status));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  if (src_points > 0) {
+    HIP_TRY(reserve(b->d_src, b->cap_src, src_points * b->dim));
+    HIP_TRY(hipMemcpyAsync(b->d_src, src, src_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
+  if (dst_points > 0) {
+    HIP_TRY(reserve(b->d_dst, b->cap_dst, dst_points * b->dim));
+    HIP_TRY(hipMemcpyAsync(b->d_dst, dst, dst_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
+  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return run_quality(b, src_points > 0 ? b->d_src : nullptr, dst_points > 0 ? b->d_dst : nullptr, items, count, max_dist,
+                     out, status);
+}
+
+extern "C" int icp_batch_evaluate_counters(icp_batch *b, uint64_t out[3]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 3; ++q) out[q] = b->qctr[q];
   return ICP_OK;
 }

@@ -514,6 +514,30 @@ size_t tiny_lds_bytes_of(int dim, unsigned m);
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
+// EXTENSION: the quality of a pose (quality.hip; include/icp_mi355x.h section 9).  A record of its fold tree: the six
+// sums that are doubles -- inlier d2, e2, rho(e2), inlier qx, qy, qx qx + qy qy -- the inlier count and whether some e2
+// was NaN.
+constexpr int kQualitySums = 6;
+struct QualityPart {
+  double v[kQualitySums];
+  unsigned long long inliers;
+  unsigned nan, pad;
+};
+// host: n and zeros; the fields of section 9 from the root record (ICP_NAN_INPUT where it carries the flag)
+void quality_clear(size_t n, icp_quality *q);
+int quality_result(size_t n, const QualityPart &p, icp_quality *q);
+// icp_batch_evaluate (api_batch.hip): items of up to kQualityMaxN source and kQualityMaxM target points run as one
+// workgroup of kQualityBatchThreads each (k_quality_batch), which writes res[slot]
+constexpr unsigned kQualityMaxN = 1024, kQualityMaxM = 2048, kQualityBatchThreads = 1024;
+struct QualityBatchItem {
+  unsigned long long src_first, dst_first;
+  unsigned n, m;     // 1 <= n <= kQualityMaxN, 1 <= m <= kQualityMaxM
+  unsigned slot, pad;
+  Pose T;
+};
+hipError_t launch_quality_batch(int dim, unsigned m_max, const double *d_src, const double *d_dst,
+                                const QualityBatchItem *d_items, unsigned count, double r2, QualityPart *res,
+                                hipStream_t stream);
 // three launches around a predicted window (gn_win.hip); h_res->overflow == 2 when it missed
 bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind = 2, bool any_n = false,
                    double f_override = 0.);

@@ -59,7 +59,9 @@ extern "C" {
  * icp_multi_pipe_iterations in icp_mi355x_debug.h).  Behavioural note: icp_multi_estimate and the sharded drivers serve
  * the steady state of a registration through it (same bits) */
 /* 8: additions only (section 8: icp_batch_*, many small registrations in one launch; icp_batch_counters in
- * icp_mi355x_debug.h).  Everything of version 7 is unchanged */
+ * icp_mi355x_debug.h).  Everything of version 7 is unchanged.  Section 9 (icp_quality, icp_evaluate*,
+ * icp_batch_evaluate*; icp_batch_evaluate_counters in icp_mi355x_debug.h) was added later without a bump: an addition
+ * detectable by symbol */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -532,6 +534,61 @@ int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const
 int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
                               size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
                               icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters);
+
+/* ================================================================================
+ * 9. EXTENSION (not in the reference): the quality of a pose
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  What a caller bases an accept / reject or a
+ * best-hypothesis decision on, and the information matrix a pose-graph edge needs: scored on the device at the pose
+ * given, with the handle's own exact correspondence search.  DESIGN.md section 9d restates the definition.
+ *
+ * For a handle with targets dst (m points), a source cloud src (n points, caller order), a pose T and max_dist r
+ * (r >= 0, or +inf), for every source point i:
+ *   qx = (r00 px + r01 py) + tx, qy = (r10 px + r11 py) + ty, qz = pz     (transform_xy, no FMA)
+ *   j  = the handle's exact nearest neighbour of q (d2 = ((dx dx + dy dy) + dz dz), ties -> lowest index), b = dst[j]
+ *   ex = qx - bx, ey = qy - by, e2 = ex ex + ey ey, h = rho(e2)          (huber.rs, k = ICP_HUBER_K)
+ *   inlier = d2 <= r * r (r * r in f64; d2 in the handle's dimension; a NaN d2 is never an inlier)
+ *   inlier terms: 1, d2, qx, qy, qx qx + qy qy; a point that is not an inlier adds +0.0 to each sum.
+ * fold(v), over the n values in caller order: n == 0 -> +0.0; n == 1 -> v[0]; otherwise, while more than one value is
+ * left: pad with +0.0 to a multiple of 256, run g[i] += g[i + s] for s = 128, 64, ..., 1 in each group of 256, and keep
+ * each group's g[0].  The order is fixed: it does not depend on how the work is launched.
+ *   inliers        the count (exact)                  fitness      inliers / n (0 when n == 0)
+ *   inlier_sum_d2  fold(d2 terms)                     inlier_rmse  sqrt(inlier_sum_d2 / inliers) (0 without inliers)
+ *   error          fold(e2)                           huber_error  fold(h)  (icp::error / huber_error, src/lib.rs:38-50,
+ *                                                                           of the pairs (xy(T src), xy(dst[idx])))
+ *   information    row-major [[c, 0, -Sy], [0, c, Sx], [-Sy, Sx, Srr]], c = (double)inliers, Sx / Sy / Srr the folds
+ *                  of the qx / qy / qx qx + qy qy terms: the jtj that gauss_newton_update (src/lib.rs:191-216) forms at
+ *                  identity on the inlier pairs -- the SE(2) Hessian in (x, y, theta).
+ * Statuses: ICP_BAD_ARGUMENT (r NaN or negative, a required pointer NULL; checked before any device use); n == 0 ->
+ * ICP_OK and zeros; ICP_EMPTY_DST (no targets); ICP_NAN_INPUT (some e2 is NaN, the estimator's rule).  *out is the
+ * result when the call returns ICP_OK; otherwise it holds n and zeros.
+ *
+ * icp_evaluate[_device]: any handle (a map handle after appends, either search engine); idx / d_idx (nullable): the n
+ * correspondences at T, caller order.  The handle's registration state is not touched: an estimate after an evaluate
+ * gives the bits it gives without one.
+ * icp_batch_evaluate[_device]: item i (its `init` is the pose to evaluate) gets the status and quality of
+ * icp_create(dst range) + icp_evaluate(src range, init), bit for bit; items of 1 <= n <= 1024 and 1 <= m <= 2048 run as
+ * one workgroup each of one launch, the others one by one.  Argument checks and whole-call errors as
+ * icp_batch_estimate's, plus r; ranges may overlap; out and status are host memory in both entries. */
+typedef struct icp_quality {
+  uint64_t n;              /* source points                                   */
+  uint64_t inliers;        /* points with d2 <= max_dist^2                     */
+  double fitness;          /* inliers / n                                      */
+  double inlier_rmse;      /* sqrt(inlier_sum_d2 / inliers)                    */
+  double inlier_sum_d2;    /* fold of the inliers' squared distances           */
+  double error;            /* fold of e2 over all points                       */
+  double huber_error;      /* fold of rho(e2) over all points                  */
+  double information[9];   /* row-major SE(2) information of the inlier pairs  */
+} icp_quality;
+int icp_evaluate(icp_handle *h, const double *src, size_t n, const icp_pose *T, double max_dist, icp_quality *out,
+                 uint32_t *idx);
+int icp_evaluate_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, double max_dist,
+                        icp_quality *out, uint32_t *d_idx);
+int icp_batch_evaluate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                       const icp_batch_item *items, size_t count, double max_dist, icp_quality *out, int *status);
+int icp_batch_evaluate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                              size_t dst_points, const icp_batch_item *items, size_t count, double max_dist,
+                              icp_quality *out, int *status);
 
 #ifdef __cplusplus
 }
