@@ -167,6 +167,7 @@ SIGNATURES = {
     "icp_last_fold_order": (C.c_int, [_vp, _sz, _vp, _vp]),
     "icp_sort_source_device": (C.c_int, [_vp, _vp, _sz, _pp, _vp, _vp]),
     "icp_gn_path_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_gn_filed_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_gn_loop_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_gn_loop_timeouts": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_fixed_point_skips": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

@@ -281,6 +281,14 @@ def gn_path_counters(icp=None):
     return tuple(int(x) for x in out)
 
 
+def gn_filed_counters(icp=None):
+    """(evaluations with filed candidates -- finished by k_win_pick / k_win_pick2 --, window evaluations still to take
+    the second pass) of a handle (default: the scratch handle behind the free functions)."""
+    out = (C.c_uint64 * 2)()
+    check(lib().icp_gn_filed_counters(icp._h if icp is not None else None, out), "icp_gn_filed_counters")
+    return tuple(int(x) for x in out)
+
+
 def gn_loop_counters(icp=None):
     """(launches, evaluations served, launches that handed an evaluation back) of the one-launch inner loop"""
     out = (C.c_uint64 * 3)()

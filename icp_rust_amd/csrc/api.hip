@@ -65,6 +65,7 @@ void free_ctx(GnCtx &c) {
   (void)hipFree(c.d_wring);
   (void)hipFree(c.d_bkt);
   (void)hipFree(c.d_bkt_dir);
+  (void)hipFree(c.d_wjoin);
   if (c.h_res) (void)hipHostFree(c.h_res);
 }
 
@@ -123,6 +124,8 @@ hipError_t alloc_ctx(GnCtx &c, hipStream_t s) {
   if ((e = hipMalloc(&c.d_wring, (size_t)2 * kWinCapRing * sizeof(double))) != hipSuccess) return e;
   if ((e = hipMalloc(&c.d_bkt, (size_t)kReduceMaxBlocks * kBktStage * sizeof(double))) != hipSuccess) return e;
   if ((e = hipMalloc(&c.d_bkt_dir, (size_t)kReduceMaxBlocks * kBktDir * sizeof(unsigned short))) != hipSuccess) return e;
+  if ((e = hipMalloc(&c.d_wjoin, sizeof(WinJoin))) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(c.d_wjoin, 0, sizeof(WinJoin), s)) != hipSuccess) return e;
   if ((e = hipHostMalloc(&c.h_res, sizeof(GnResult), hipHostMallocCoherent)) != hipSuccess) return e;
   memset(c.h_res, 0, sizeof(GnResult));
   return hipSuccess;
@@ -1442,6 +1445,18 @@ extern "C" int icp_gn_path_counters(icp_handle *h, uint64_t out[6]) {
   out[3] = h->ws.radix_evals;
   out[4] = h->ws.spec_hits;
   out[5] = h->ws.spec_misses;
+  return ICP_OK;
+}
+
+extern "C" int icp_gn_filed_counters(icp_handle *h, uint64_t out[2]) {
+  if (!out) return ICP_BAD_ARGUMENT;
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  if (!h) {
+    const int rc = scratch_handle(&h);
+    if (rc != ICP_OK) return rc;
+  }
+  out[0] = h->ws.bkt_evals;
+  out[1] = h->ws.bkt_off;
   return ICP_OK;
 }
 

@@ -135,6 +135,23 @@ struct WinState {
   unsigned list_cnt[4][32];       // appended so far {med x, med y, ring x, ring y}, a 128-B line each
 };
 
+// Where the two workgroups that finish one evaluation (gn_win.hip: k_win_pick / k_win_pick2, one per dimension) meet:
+// each leaves what the other needs -- its statistics, its flags, its half of the folded block sums -- write-through on
+// lines of its own, and takes a ticket; the one that draws the second ticket of the pair finishes the evaluation.
+// The ticket counts arrivals modulo 2 and is never reset (zero at allocation, even between launches).
+struct WinJoinDim {
+  double med, sig;
+  double tot[10];   // folded block sums, columns [10 h, 10 h + 10) of the workgroup with column half h
+  unsigned flags;   // bit 0: the window missed, bit 1: the filed candidates were unusable, bit 2: a selection failed
+  unsigned pad[7];
+};
+static_assert(sizeof(WinJoinDim) == 128, "a line per dimension");
+struct WinJoin {
+  unsigned ticket;
+  unsigned pad[31];
+  WinJoinDim dim[2];
+};
+
 // What the last kernel of an inner iteration hands to the host (pinned, mapped).
 struct GnResult {
   double acc[kNAcc + 1];  // jtj[9], jtr[3], huber error, (plain) error
@@ -188,6 +205,7 @@ struct GnCtx {
   double *d_wring = nullptr;    // 2 x kWinCapRing residuals
   double *d_bkt = nullptr;      // kReduceMaxBlocks segments of kBktStage residuals: a workgroup's fine-window members, by bin
   unsigned short *d_bkt_dir = nullptr;  // kReduceMaxBlocks x kBktDir: where each fine bin's members start in the segment
+  WinJoin *d_wjoin = nullptr;   // the hand-off between the two workgroups of a finishing launch (zero at allocation)
   bool bkt_pair_launched = false;  // this context's evaluation is in flight on the search stream (launch_bkt_pair): only its result is awaited
 };
 

@@ -386,6 +386,46 @@ __device__ __forceinline__ void fold256_reduce(const double (&x)[kFoldH], int bl
     s_tot[t] = s + 0.;
   }
 }
+// ONE of those two column halves (h), folded exactly as fold256_reduce folds it, by a workgroup of 512 threads: thread t
+// takes sums [10 h + 5 g, 10 h + 5 g + 5) of row t % 256, g = t / 256, so every row is in the lane and the wave (of
+// waves 0-3 or 4-7) it has there -- the two workgroups that finish an evaluation fold one half each (gn_win.hip).
+// out[k] = the total of column 10 h + k (LDS; valid after the next barrier).
+constexpr int kFoldQ = kFoldH / 2;
+template <int SCOPE = __HIP_MEMORY_SCOPE_AGENT>
+__device__ __forceinline__ void fold256_half_load(const double *partials, int blocks, int h, double (&x)[kFoldQ]) {
+  static_assert(kFoldQ * 2 == kFoldH, "two quarters per half");
+  const int t = threadIdx.x, row = t & 255, c0 = h * kFoldH + (t >> 8) * kFoldQ;
+#pragma unroll
+  for (int k = 0; k < kFoldQ; ++k)
+    x[k] = (row < blocks && c0 + k < kNSum)
+               ? __hip_atomic_load(&partials[(size_t)row * (kNSum + 1) + c0 + k], __ATOMIC_RELAXED, SCOPE)
+               : 0.;
+}
+__device__ __forceinline__ void fold256_half_reduce(const double (&x)[kFoldQ], int blocks, double *out) {
+  constexpr int Q = kFoldQ;
+  __shared__ double sm[8][Q];
+  const int t = threadIdx.x, row = t & 255, lane = t & 63, wave = t >> 6;
+  double v[Q];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) v[k] = 0.;
+  if (row < blocks) {
+#pragma unroll
+    for (int k = 0; k < Q; ++k) v[k] = v[k] + x[k];
+  }
+  wave_tree<Q>(v);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < Q; ++k) sm[wave][k] = v[k];
+  }
+  __syncthreads();
+  if (t < kFoldH) {
+    const int g = t / Q, k = t % Q;
+    double s = sm[4 * g][k];
+    for (int w = 1; w < 4; ++w) s = s + sm[4 * g + w][k];
+    out[t] = s + 0.;
+  }
+}
+
 template <int SCOPE = __HIP_MEMORY_SCOPE_AGENT>
 __device__ __forceinline__ void fold_block_sums_256(const double *partials, int blocks, double *s_tot) {
   double x[kFoldH];

@@ -939,7 +939,8 @@ __global__ __launch_bounds__(kWinThreads) void k_win_finish(const double *__rest
 // order does not matter to a selection -- -> every thread loads the candidates of its slots straight into registers
 // -> the two exact selections -> the fold of the block sums (the tree's second stage, loaded before anything else)
 // -> the solve for the run-ahead search -> the result.  No ticket, no second pass: a chain of dependent steps on one
-// CU while the rest of the chip works on something else.
+// CU while the rest of the chip works on something else.  (Round 7: k_win_pick / k_win_pick2 split that chain per
+// dimension, below; the one-workgroup form lives on in k_win_pick_shard, whose LDS this is.)
 struct PickLds {  // (the descriptor lists are dead when the selections start: their LDS is overlaid)
   union {
     struct {
@@ -949,6 +950,131 @@ struct PickLds {  // (the descriptor lists are dead when the selections start: t
     SelectLds<2> sel;
   };
 };
+
+// ---- P, one workgroup per dimension (round 7) -----------------------------------------------------------------------
+// x and y do not meet before the 3 x 3 solve: their bins, candidate lists, medians, MADs and -- the sums being laid out
+// S_x | S_y | huber -- nothing of the fold either.  So an evaluation is finished by TWO workgroups side by side, one per
+// dimension d, each on its own CU: its histogram row -> the candidate bins (win_resolve_dim) -> thread (w, part) reads
+// the directory of segment w for the median run (part 0) or the ring's two arcs (part 1) and lists their members ->
+// the candidates into registers -> the two exact selections -> column half d of the block sums' fold.  Each stores
+// what the other needs write-through (WinJoin), drains, and takes the evaluation's ticket; the one that draws the
+// second ticket of the pair reads the other's part (sc1 loads), solves for the run-ahead search and releases the result.
+// Nobody waits for anybody: a workgroup that arrives first simply leaves.
+struct PickDimLds {  // (the descriptor lists are dead when the selections start: their LDS is overlaid)
+  union {
+    struct {
+      uint32_t cum[kWinBins];
+      uint32_t med[kWinCapMed], ring[kWinCapRing];
+    } g;
+    SelectLds<1> sel;
+  };
+};
+
+// what the histogram row of one dimension resolves to (win_resolve's per-dimension half)
+struct WinBins1 {
+  unsigned mlo, mhi, a0, b1, i0, i1;
+  bool fail;
+};
+struct WinSel1 {
+  unsigned med_base, med_cnt, inner, ring_cnt;
+  double range[4];
+};
+
+// win_resolve<true, true> for ONE dimension, by a workgroup of 512 threads (four barriers): the row -> `cum` -> the
+// bracket (waves 0 and 1 side by side) -> the candidate bins (wave 0).  st != nullptr: dimension d's part of the state
+// is left there.
+__device__ __forceinline__ WinBins1 win_resolve_dim(const uint32_t *__restrict__ row, unsigned n, const WinDim &w,
+                                                    WinState *st, int d, uint32_t *cum, WinSel1 &sel) {
+  __shared__ unsigned s_wtot[kReduceThreads / 64];
+  __shared__ int s_j[2], s_t[2], s_rng[7];
+  __shared__ unsigned s_selu[4];
+  __shared__ double s_seld[4];
+  constexpr int PER = kWinBins / kReduceThreads, NW = kReduceThreads / 64;
+  static_assert(PER == 4, "one 16-byte load per thread");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned klo = (n - 1) / 2, khi = n / 2;  // src/stats.rs:18-27
+  if (tid < 2) s_j[tid] = -1;
+  const uint4 x = reinterpret_cast<const uint4 *>(row)[tid];
+  const unsigned v[PER] = {x.x, x.y, x.z, x.w};
+  const unsigned tot = (x.x + x.y) + (x.z + x.w);
+  const unsigned inc = wave_scan_inclusive(tot);
+  if (lane == 63) s_wtot[wave] = inc;
+  __syncthreads();
+  {
+    unsigned wbase = 0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) wbase += (q < wave) ? s_wtot[q] : 0u;
+    unsigned run = wbase + inc - tot;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      cum[PER * tid + i] = run;
+      if (run <= klo && klo < run + v[i]) s_j[0] = PER * tid + i;
+      if (run <= khi && khi < run + v[i]) s_j[1] = PER * tid + i;
+      run += v[i];
+    }
+  }
+  __syncthreads();
+  WinGeom geo = {};
+  if (wave < 2) {  // wave 0: t1, wave 1: t2 -- the two halves of the bracket side by side
+    geo = window_geometry(cum, n, w, s_j[0], s_j[1]);
+    const int t = geo.ok ? bracket_search(cum, n, w, geo, wave) : -1;
+    if (lane == 0) s_t[wave] = t;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    WinRanges R = {};
+    unsigned med_base = 0, med_cnt = 0, inner = 0, ring_cnt = 0;
+    double range[4] = {0., 0., 0., 0.};
+    unsigned counted = 0;  // every point is in exactly one bin: anything else means the histogram is not this evaluation's
+#pragma unroll
+    for (int q = 0; q < NW; ++q) counted += s_wtot[q];
+    bool ok = counted == n && resolve_window(cum, n, w, geo, s_t[0], s_t[1], R, med_base, med_cnt, inner, ring_cnt, range);
+    if (ok)  // the median bins in the middle window, the two arcs of the ring in the outer ones (where the files are)
+      ok = R.mlo >= kF1 && R.mhi < kC1 && R.i0 <= R.i1 && R.a0 >= kF0 && R.i0 - 1 < kC0 && R.i1 + 1 >= kF2 &&
+           R.b1 <= kWinBins - 2;
+    if (lane == 0) {
+      s_rng[0] = R.mlo;
+      s_rng[1] = R.mhi;
+      s_rng[2] = R.a0;
+      s_rng[3] = R.b1;
+      s_rng[4] = R.i0;
+      s_rng[5] = R.i1;
+      s_rng[6] = ok ? 0 : 1;
+      s_selu[0] = med_base;
+      s_selu[1] = med_cnt;
+      s_selu[2] = inner;
+      s_selu[3] = ring_cnt;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s_seld[k] = range[k];
+      if (st) {
+        st->med_base[d] = med_base;
+        st->med_cnt[d] = med_cnt;
+        st->ring_inner[d] = inner;
+        st->ring_cnt[d] = ring_cnt;
+        st->med_lo[d] = range[0];
+        st->med_hi[d] = range[1];
+        st->ring_lo[d] = range[2];
+        st->ring_hi[d] = range[3];
+      }
+    }
+  }
+  __syncthreads();
+  WinBins1 B;
+  B.mlo = (unsigned)s_rng[0];
+  B.mhi = (unsigned)s_rng[1];
+  B.a0 = (unsigned)s_rng[2];
+  B.b1 = (unsigned)s_rng[3];
+  B.i0 = (unsigned)s_rng[4];
+  B.i1 = (unsigned)s_rng[5];
+  B.fail = s_rng[6] != 0;
+  sel.med_base = s_selu[0];
+  sel.med_cnt = s_selu[1];
+  sel.inner = s_selu[2];
+  sel.ring_cnt = s_selu[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) sel.range[k] = s_seld[k];
+  return B;
+}
 
 struct PickArgs {
   unsigned n;
@@ -965,185 +1091,216 @@ struct PickArgs {
   unsigned seq;
   AheadPose *ahead;
   Pose outer;
+  WinJoin *join;
 };
 
-// (by the workgroup with blockIdx.x == 0 of its launch: win_resolve leaves the state in `st` from there)
-__device__ __forceinline__ void win_pick_body(const PickArgs &A, PickLds &L) {
+// Dimension d of the evaluation A.  primary: this launch keeps the evaluation's state in A.st (k_win_pick2's second
+// evaluation does not: nothing reads it on that path).
+__device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d, const bool primary, PickDimLds &L) {
   const unsigned n = A.n;
-  const WinParams &P = A.P;
-  uint32_t *const whist = A.whist;
   WinState *const st = A.st;
   const double *__restrict__ seg_all = A.seg_all;
   const unsigned short *__restrict__ dir_all = A.dir_all;
-  const int segments = A.segments;
-  GnScalars *const scal = A.scal;
-  const double *const partials = A.partials;
-  const int sum_blocks = A.sum_blocks;
-  GnResult *const res = A.res;
-  const unsigned seq = A.seq;
-  AheadPose *const ahead = A.ahead;
-  const Pose outer = A.outer;
+  WinJoin *const J = A.join;
   constexpr int PM = kWinCapMed / kReduceThreads, PR = kWinCapRing / kReduceThreads;
-  static_assert(kReduceMaxBlocks * 2 == kReduceThreads, "one thread per segment and dimension");
+  static_assert(kReduceMaxBlocks * 2 == kReduceThreads, "two threads per segment");
   static_assert(kBktStage <= (1 << 12), "descriptor: segment << 12 | position");
   __shared__ double s_tot[kNSum + 1];
-  __shared__ unsigned s_cnt[4];
+  __shared__ unsigned s_cnt[2];
+  __shared__ int s_last;
+  __shared__ unsigned s_pflags;
+  __shared__ double s_pms[2];
   const unsigned tid = threadIdx.x;
 #ifdef ICP_WIN_DEBUG
   long long pst[10];
   pst[0] = wall_clock64();
+  for (int k = 1; k < 10; ++k) pst[k] = pst[0];
 #define PSTAMP(k) pst[k] = wall_clock64()
 #else
 #define PSTAMP(k)
 #endif
-  if (tid < 4) s_cnt[tid] = 0;
-  // (the two flags of the launch in front of this one are asked for FIRST: read after the resolve they were a round trip
-  // of their own -- 3 us between the resolve's last stamp and the lists, r05_pick_phases.txt -- because the lists'
-  // branch needs them at once)
-  const int nan_flag = __hip_atomic_load(&scal->nan_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid < 2) s_cnt[tid] = 0;
+  // (the two flags of the launch in front of this one are asked for first: the lists' branch needs them at once)
+  const int nan_flag = __hip_atomic_load(&A.scal->nan_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned stage_overflow = __hip_atomic_load(&st->stage_overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  WinSel sel;
-  const WinBins R = win_resolve<true, true>(whist, n, P, st, nullptr, 0u, L.g.cum, sel);
-  // (the block sums travel while the candidates are listed: the histograms went first)
-  double fx[kFoldH];
-  fold256_load(partials, sum_blocks, fx);
+  WinSel1 sel;
+  const WinBins1 R = win_resolve_dim(A.whist + (size_t)d * kWinBins, n, A.P.d[d], primary ? st : nullptr, d, L.g.cum, sel);
+  // (the block sums travel while the candidates are listed: the histogram went first)
+  double fx[kFoldQ];
+  fold256_half_load(A.partials, A.sum_blocks, d, fx);
   PSTAMP(1);
-  bool fail = R.fail;
-  bool bucket_miss = stage_overflow != 0;
-  double med[2] = {0., 0.}, sig[2] = {0., 0.};
+  const bool fail = R.fail;
+  bool bucket_miss = stage_overflow != 0, sel_fail = false;
+  double med = 0., sig = 0.;
   {
-    // the runs of candidate bins of this thread's dimension, in directory order: the median's, the ring's two arcs
-    const unsigned w = tid & (unsigned)(kReduceMaxBlocks - 1), d = tid / (unsigned)kReduceMaxBlocks;
     const bool usable = !fail && !bucket_miss;  // (uniform)
-    // (this thread's dimension by selects: a run-time index into the arrays of R would put them into scratch memory)
-    const unsigned mlo_d = d ? R.mlo[1] : R.mlo[0], mhi_d = d ? R.mhi[1] : R.mhi[0], a0_d = d ? R.a0[1] : R.a0[0];
-    const unsigned b1_d = d ? R.b1[1] : R.b1[0], i0_d = d ? R.i0[1] : R.i0[0], i1_d = d ? R.i1[1] : R.i1[0];
-    const unsigned len_m = usable ? mhi_d - mlo_d + 1u : 0u;
-    const unsigned len_a = usable ? i0_d - a0_d : 0u, len_b = usable ? b1_d - i1_d : 0u;
-    __syncthreads();  // (s_cnt's zeros)
-    if (usable && !bucket_miss && (int)w < segments) {
+    const unsigned w = tid & (unsigned)(kReduceMaxBlocks - 1), part = tid / (unsigned)kReduceMaxBlocks;
+    if (usable && (int)w < A.segments) {
       const unsigned short *dir = dir_all + (size_t)w * kBktDir;
-      const unsigned fm = word_to_fine(d, mlo_d), fa = word_to_fine(d, a0_d), fb = word_to_fine(d, i1_d + 1u);
       // (the members of a run of consecutive bins are contiguous in the segment: the run's first offset .. the offset
-      // behind its last bin -- six directory entries per thread, one trip)
-      const unsigned short q0 = dir[fm], q1 = dir[fm + len_m], q2 = dir[fa], q3 = dir[fa + len_a], q4 = dir[fb],
-                           q5 = dir[fb + len_b];
-      const unsigned m0 = q0, m_end = q1, a_beg = q2, a_end = q3, b_beg = q4, b_end = q5;
-      const unsigned cm = m_end - m0, cr = (a_end - a_beg) + (b_end - b_beg);
-      if (cm) {
-        const unsigned pos = atomicAdd(&s_cnt[d], cm);
-        for (unsigned k = 0; k < cm; ++k)
-          if (pos + k < (unsigned)kWinCapMed) L.g.med[d][pos + k] = (w << 12) | (m0 + k);
-      }
-      if (cr) {
-        unsigned pos = atomicAdd(&s_cnt[2 + d], cr);
-        for (unsigned k = a_beg; k < a_end; ++k, ++pos)
-          if (pos < (unsigned)kWinCapRing) L.g.ring[d][pos] = (w << 12) | k;
-        for (unsigned k = b_beg; k < b_end; ++k, ++pos)
-          if (pos < (unsigned)kWinCapRing) L.g.ring[d][pos] = (w << 12) | k;
+      // behind its last bin)
+      if (part == 0) {
+        const unsigned fm = word_to_fine(d, R.mlo), len_m = R.mhi - R.mlo + 1u;
+        const unsigned m0 = dir[fm], m_end = dir[fm + len_m];
+        const unsigned cm = m_end - m0;
+        if (cm) {
+          const unsigned pos = atomicAdd(&s_cnt[0], cm);
+          for (unsigned k = 0; k < cm; ++k)
+            if (pos + k < (unsigned)kWinCapMed) L.g.med[pos + k] = (w << 12) | (m0 + k);
+        }
+      } else {
+        const unsigned fa = word_to_fine(d, R.a0), fb = word_to_fine(d, R.i1 + 1u);
+        const unsigned len_a = R.i0 - R.a0, len_b = R.b1 - R.i1;
+        const unsigned a_beg = dir[fa], a_end = dir[fa + len_a], b_beg = dir[fb], b_end = dir[fb + len_b];
+        const unsigned cr = (a_end - a_beg) + (b_end - b_beg);
+        if (cr) {
+          unsigned pos = atomicAdd(&s_cnt[1], cr);
+          for (unsigned k = a_beg; k < a_end; ++k, ++pos)
+            if (pos < (unsigned)kWinCapRing) L.g.ring[pos] = (w << 12) | k;
+          for (unsigned k = b_beg; k < b_end; ++k, ++pos)
+            if (pos < (unsigned)kWinCapRing) L.g.ring[pos] = (w << 12) | k;
+        }
       }
     }
     __syncthreads();
     PSTAMP(2);
     // (the listed counts are cross-checked against the histogram: a mismatch is a miss)
-    if (usable && !bucket_miss)
-      bucket_miss = s_cnt[0] != sel.med_cnt[0] || s_cnt[1] != sel.med_cnt[1] || s_cnt[2] != sel.ring_cnt[0] ||
-                    s_cnt[3] != sel.ring_cnt[1];
-    double vm[2][PM], vr[2][PR];
+    if (usable) bucket_miss = s_cnt[0] != sel.med_cnt || s_cnt[1] != sel.ring_cnt;
+    const bool go = usable && !bucket_miss;
+    double vm[1][PM], vr[1][PR];
 #pragma unroll
-    for (int dd = 0; dd < 2; ++dd) {
-#pragma unroll
-      for (int u = 0; u < PM; ++u) {
-        const unsigned e = tid + u * kReduceThreads;
-        vm[dd][u] = 0.;
-        if (usable && !bucket_miss && e < sel.med_cnt[dd]) {
-          const uint32_t x = L.g.med[dd][e];
-          vm[dd][u] = seg_all[(size_t)(x >> 12) * kBktStage + (x & 0xfffu)];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < PR; ++u) {
-        const unsigned e = tid + u * kReduceThreads;
-        vr[dd][u] = 0.;
-        if (usable && !bucket_miss && e < sel.ring_cnt[dd]) {
-          const uint32_t x = L.g.ring[dd][e];
-          vr[dd][u] = seg_all[(size_t)(x >> 12) * kBktStage + (x & 0xfffu)];
-        }
+    for (int u = 0; u < PM; ++u) {
+      const unsigned e = tid + u * kReduceThreads;
+      vm[0][u] = 0.;
+      if (go && e < sel.med_cnt) {
+        const uint32_t x = L.g.med[e];
+        vm[0][u] = seg_all[(size_t)(x >> 12) * kBktStage + (x & 0xfffu)];
       }
     }
-    // the histograms of the next evaluation start from zero (write-through, drained before the release below: the
-    // host may hand the next evaluation to the handle's other stream as soon as it sees this result)
-    for (unsigned i = tid; i < 2u * kWinBins; i += kReduceThreads)
-      __hip_atomic_store(&whist[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0 && stage_overflow) __hip_atomic_store(&st->stage_overflow, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    fold256_reduce(fx, sum_blocks, s_tot);  // (a barrier inside)
-    __syncthreads();                        // (the descriptor lists are read: the selections may overlay them)
+#pragma unroll
+    for (int u = 0; u < PR; ++u) {
+      const unsigned e = tid + u * kReduceThreads;
+      vr[0][u] = 0.;
+      if (go && e < sel.ring_cnt) {
+        const uint32_t x = L.g.ring[e];
+        vr[0][u] = seg_all[(size_t)(x >> 12) * kBktStage + (x & 0xfffu)];
+      }
+    }
+    // this dimension's histogram row starts from zero for the next evaluation (write-through, drained before the
+    // ticket: the host may hand the next evaluation to the handle's other stream as soon as it sees the result)
+    {
+      unsigned long long *row = reinterpret_cast<unsigned long long *>(A.whist + (size_t)d * kWinBins);
+#pragma unroll
+      for (int u = 0; u < kWinBins / 2 / kReduceThreads; ++u)
+        __hip_atomic_store(&row[tid + u * kReduceThreads], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    fold256_half_reduce(fx, A.sum_blocks, s_tot + d * kFoldH);  // (a barrier inside)
+    __syncthreads();  // (the descriptor lists are read: the selections may overlay them)
     PSTAMP(3);
     const unsigned klo = (n - 1) / 2, khi = n / 2;
-    if (!fail && !bucket_miss) {
-      unsigned long long key[2][2];
-      const double m_lo[2] = {sel.range[0][0], sel.range[1][0]}, m_hi[2] = {sel.range[0][1], sel.range[1][1]};
-      const long long mlo[2] = {(long long)klo - sel.med_base[0], (long long)klo - sel.med_base[1]};
-      const long long mhi[2] = {(long long)khi - sel.med_base[0], (long long)khi - sel.med_base[1]};
-      select_n_lds<2, PM>(vm, sel.med_cnt, m_lo, m_hi, mlo, mhi, key, fail, L.sel);
+    if (go) {
+      unsigned long long key[1][2];
+      const unsigned cm[1] = {sel.med_cnt}, cr[1] = {sel.ring_cnt};
+      const double m_lo[1] = {sel.range[0]}, m_hi[1] = {sel.range[1]};
+      const long long mlo[1] = {(long long)klo - sel.med_base}, mhi[1] = {(long long)khi - sel.med_base};
+      select_n_lds<1, PM>(vm, cm, m_lo, m_hi, mlo, mhi, key, sel_fail, L.sel);
       PSTAMP(4);
-      if (!fail) {
+      if (!sel_fail) {
+        med = middle_of(n, key[0][0], key[0][1]);
 #pragma unroll
-        for (int dd = 0; dd < 2; ++dd) {
-          med[dd] = middle_of(n, key[dd][0], key[dd][1]);
-#pragma unroll
-          for (int u = 0; u < PR; ++u) vr[dd][u] = fabs(vr[dd][u] - med[dd]);  // src/stats.rs:35
-        }
-        const double r_lo[2] = {sel.range[0][2], sel.range[1][2]}, r_hi[2] = {sel.range[0][3], sel.range[1][3]};
-        const long long dlo[2] = {(long long)klo - sel.inner[0], (long long)klo - sel.inner[1]};
-        const long long dhi[2] = {(long long)khi - sel.inner[0], (long long)khi - sel.inner[1]};
-        select_n_lds<2, PR>(vr, sel.ring_cnt, r_lo, r_hi, dlo, dhi, key, fail, L.sel);
+        for (int u = 0; u < PR; ++u) vr[0][u] = fabs(vr[0][u] - med);  // src/stats.rs:35
+        const double r_lo[1] = {sel.range[2]}, r_hi[1] = {sel.range[3]};
+        const long long dlo[1] = {(long long)klo - sel.inner}, dhi[1] = {(long long)khi - sel.inner};
+        select_n_lds<1, PR>(vr, cr, r_lo, r_hi, dlo, dhi, key, sel_fail, L.sel);
         PSTAMP(5);
-        if (!fail) {
-          sig[0] = ICP_PPF34 * middle_of(n, key[0][0], key[0][1]);  // src/stats.rs:42-46
-          sig[1] = ICP_PPF34 * middle_of(n, key[1][0], key[1][1]);
-        } else {
-          med[0] = med[1] = 0.;
-        }
+        if (!sel_fail) sig = ICP_PPF34 * middle_of(n, key[0][0], key[0][1]);  // src/stats.rs:42-46
       }
     }
   }
-  const bool missed = fail || bucket_miss;
-  if (tid == 0 && missed) st->fail = 1u;
+  // the hand-off: this workgroup's part, write-through; every wave drains; one lane takes the ticket
+  const unsigned flags = (fail ? 1u : 0u) | (bucket_miss ? 2u : 0u) | (sel_fail ? 4u : 0u);
+  WinJoinDim *const mine = &J->dim[d];
+  if (tid < (unsigned)kFoldH) __hip_atomic_store(&mine->tot[tid], s_tot[d * kFoldH + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 64) {
+    __hip_atomic_store(&mine->med, med, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&mine->sig, sig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&mine->flags, flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   PSTAMP(6);
+  if (tid == 0)  // (arrivals counted modulo 2: an odd ticket is the pair's second)
+    s_last = (int)(__hip_atomic_fetch_add(&J->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u);
+  __syncthreads();
+  if (!s_last) {
+#ifdef ICP_WIN_DEBUG
+    if (tid == 0 && A.seq % 16 == 5)
+      printf("[P%d first] resolve %lld list %lld load+fold %lld sel1 %lld sel2 %lld store %lld (x10ns) cnt %u %u\n", d,
+             pst[1] - pst[0], pst[2] - pst[1], pst[3] - pst[2], pst[4] - pst[3], pst[5] - pst[4], pst[6] - pst[5],
+             sel.med_cnt, sel.ring_cnt);
+#endif
+    return;
+  }
+  // the last arriver: the other dimension's part (sc1 loads, after the ticket's return / the barrier behind it)
+  const int o = 1 - d;
+  const WinJoinDim *const other = &J->dim[o];
+  static_assert(offsetof(WinJoinDim, tot) == 16 && offsetof(WinJoinDim, flags) == 96, "words of the record");
+  if (tid < 13) {  // (its first thirteen 8-byte words, one per lane: ONE round trip)
+    const unsigned long long x =
+        __hip_atomic_load(reinterpret_cast<const unsigned long long *>(other) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < 2) s_pms[tid] = __longlong_as_double((long long)x);
+    else if (tid < 12) s_tot[o * kFoldH + (tid - 2)] = __longlong_as_double((long long)x);
+    else s_pflags = (unsigned)x;
+  }
+  __syncthreads();
+  PSTAMP(7);
+  // the two dimensions' outcomes combined as the one-workgroup finish combined them: a window missed anywhere -> 2; else
+  // unusable files anywhere -> 3 (no selection counts then); else a failed selection anywhere -> 2
+  const unsigned all = flags | s_pflags;
+  const bool any_fail = (all & 1u) != 0, any_bucket = (all & 2u) != 0;
+  const bool failed = any_fail || (!any_bucket && (all & 4u) != 0);
+  const bool missed = failed || any_bucket;
+  // (by selects: a run-time index into the arrays would put them into scratch memory)
+  const double m_me = missed ? 0. : med, s_me = missed ? 0. : sig, m_ot = missed ? 0. : s_pms[0], s_ot = missed ? 0. : s_pms[1];
+  const double med2[2] = {d ? m_ot : m_me, d ? m_me : m_ot}, sig2[2] = {d ? s_ot : s_me, d ? s_me : s_ot};
+  if (tid == 0) {
+    if (missed) st->fail = 1u;
+    else if (primary) st->fail = 0u;
+    if (stage_overflow) __hip_atomic_store(&st->stage_overflow, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   // overflow 3: the window may have been right, the FILES were not usable (the host steps back to the second pass)
-  const int overflow = missed ? (fail ? 2 : 3) : 0;
-  if (ahead) {  // (uniform) lane 0 derives the next outer pose while wave 1 stores the result; wave 0 releases both
-    if (tid == 0) fill_ahead_pose(s_tot, sig, !missed && !nan_flag, outer, ahead, res);
-    publish_values<1>(s_tot, res, sig, med, nan_flag, overflow);
-    PSTAMP(7);
+  const int overflow = missed ? (failed ? 2 : 3) : 0;
+  GnResult *const res = A.res;
+  if (A.ahead) {  // (uniform) lane 0 derives the next outer pose while wave 1 stores the result; wave 0 releases both
+    if (tid == 0) fill_ahead_pose(s_tot, sig2, !missed && !nan_flag, A.outer, A.ahead, res);
+    publish_values<1>(s_tot, res, sig2, med2, nan_flag, overflow);
+    PSTAMP(8);
     __syncthreads();
-    publish_seq(res, seq);
+    publish_seq(res, A.seq);
   } else {
-    PSTAMP(7);
-    publish_folded(s_tot, res, seq, sig, med, nan_flag, overflow);
+    PSTAMP(8);
+    publish_folded(s_tot, res, A.seq, sig2, med2, nan_flag, overflow);
   }
 #ifdef ICP_WIN_DEBUG
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  PSTAMP(8);
-  if (tid == 0 && seq % 16 == 5)
-    printf("[P] resolve %lld list %lld load+fold %lld sel1 %lld sel2 %lld drain %lld ahead %lld publish %lld (x10ns) cnt %u %u %u %u\n",
-           pst[1] - pst[0], pst[2] - pst[1], pst[3] - pst[2], pst[4] - pst[3], pst[5] - pst[4], pst[6] - pst[5],
-           pst[7] - pst[6], pst[8] - pst[7], sel.med_cnt[0], sel.med_cnt[1], sel.ring_cnt[0], sel.ring_cnt[1]);
+  PSTAMP(9);
+  if (tid == 0 && A.seq % 16 == 5)
+    printf("[P%d last] resolve %lld list %lld load+fold %lld sel1 %lld sel2 %lld store %lld ticket+loads %lld ahead %lld "
+           "publish %lld (x10ns) cnt %u %u\n", d, pst[1] - pst[0], pst[2] - pst[1], pst[3] - pst[2], pst[4] - pst[3],
+           pst[5] - pst[4], pst[6] - pst[5], pst[7] - pst[6], pst[8] - pst[7], pst[9] - pst[8], sel.med_cnt, sel.ring_cnt);
 #endif
 #undef PSTAMP
 }
 
+// one evaluation: workgroup d finishes dimension d
 __global__ __launch_bounds__(kReduceThreads) void k_win_pick(PickArgs A) {
-  __shared__ PickLds L;
-  win_pick_body(A, L);
+  __shared__ PickDimLds L;
+  win_pick_dim_body(A, (int)blockIdx.x, true, L);
 }
 
 // Two evaluations side by side (icp_estimate_device with a bet in flight: the next outer iteration's first evaluation
 // and the deciding evaluation of the current one): ONE launch files the candidates of both (2 B workgroups: two per
-// CU, four waves per SIMD instead of two hide each other's latencies), ONE launch of two workgroups finishes both.
+// CU, four waves per SIMD instead of two hide each other's latencies), ONE launch of four workgroups finishes both.
 // The deciding evaluation then neither shares the CUs with the search nor needs a stream of its own.
 __global__ __launch_bounds__(kWinThreads, 4) void k_win_hist_sums_bkt2(HistBktArgs A, HistBktArgs B) {
   __shared__ HistBktLds S;
@@ -1151,12 +1308,12 @@ __global__ __launch_bounds__(kWinThreads, 4) void k_win_hist_sums_bkt2(HistBktAr
   if (blockIdx.x < half) win_hist_sums_bkt_body(A, blockIdx.x, half, S);
   else win_hist_sums_bkt_body(B, blockIdx.x - half, half, S);
 }
-// (win_resolve leaves the state in `st` from the workgroup with blockIdx.x == 0: the second evaluation's `st` is not
-// maintained -- nothing reads it on this path)
+// four workgroups: 0 and 1 finish dimensions x and y of A, 2 and 3 those of B (whose `st` is not maintained -- nothing
+// reads it on this path)
 __global__ __launch_bounds__(kReduceThreads) void k_win_pick2(PickArgs A, PickArgs B) {
-  __shared__ PickLds L;
-  if (blockIdx.x == 0) win_pick_body(A, L);
-  else win_pick_body(B, L);
+  __shared__ PickDimLds L;
+  if (blockIdx.x < 2u) win_pick_dim_body(A, (int)blockIdx.x, true, L);
+  else win_pick_dim_body(B, (int)blockIdx.x - 2, false, L);
 }
 
 // ---- P across ranks (round 6): the finishing workgroup of an evaluation whose points are SHARDED -----------------
@@ -1313,7 +1470,7 @@ __device__ __forceinline__ void win_pick_shard_body(const unsigned n, const unsi
   bool fail = R.fail;
   double med[2] = {0., 0.}, sig[2] = {0., 0.};
   {
-    // ---- this rank's candidates of the resolved bins, out of its own segments (win_pick_body has the comments) -------
+    // ---- this rank's candidates of the resolved bins, out of its own segments (as win_pick_dim_body lists them) -----
     const unsigned w = tid & (unsigned)(kReduceMaxBlocks - 1), d = tid / (unsigned)kReduceMaxBlocks;
     const bool usable = alive && !fail && !bucket_miss;  // (uniform, and the same on every rank)
     const unsigned mlo_d = d ? R.mlo[1] : R.mlo[0], mhi_d = d ? R.mhi[1] : R.mhi[0], a0_d = d ? R.a0[1] : R.a0[0];
@@ -1738,6 +1895,7 @@ static PickArgs bkt_pick_args(GnCtx &c, unsigned n, const WinParams &P, bool ahe
   A.seq = ++c.seq;
   A.ahead = ahead_on ? d_ahead : nullptr;
   A.outer = ahead_on ? ahead_outer : transform_identity();
+  A.join = c.d_wjoin;
   return A;
 }
 
@@ -1755,7 +1913,7 @@ hipError_t launch_bkt_pair(icp_handle *h, hipStream_t s, GnCtx &first, const dou
   hipLaunchKernelGGL(k_win_hist_sums_bkt2, dim3(2 * blocks), dim3(kWinThreads), 0, s,
                      bkt_hist_args(first, (const double2 *)a1, (const double2 *)b1, transform_identity(), n, P1),
                      bkt_hist_args(second, (const double2 *)a2, (const double2 *)b2, T2, n, P2));
-  hipLaunchKernelGGL(k_win_pick2, dim3(2), dim3(kReduceThreads), 0, s,
+  hipLaunchKernelGGL(k_win_pick2, dim3(4), dim3(kReduceThreads), 0, s,
                      bkt_pick_args(first, n, P1, ahead_on, ahead_outer, w.d_ahead),
                      bkt_pick_args(second, n, P2, false, transform_identity()));
   second.bkt_pair_launched = true;
@@ -1839,7 +1997,7 @@ hipError_t launch_weighted_gn_win(icp_handle *h, const double *d_a, const double
     ++w.bkt_evals;
     const HistBktArgs HA = bkt_hist_args(w, a, b, T, n, P);
     hipLaunchKernelGGL(k_win_hist_sums_bkt, dim3(tree_blocks(n_)), dim3(kWinThreads), 0, s, HA);
-    hipLaunchKernelGGL(k_win_pick, dim3(1), dim3(kReduceThreads), 0, s, bkt_pick_args(w, n, P, w.ahead_on, w.ahead_outer, w.d_ahead));
+    hipLaunchKernelGGL(k_win_pick, dim3(2), dim3(kReduceThreads), 0, s, bkt_pick_args(w, n, P, w.ahead_on, w.ahead_outer, w.d_ahead));
     return hipGetLastError();
   }
   int blocks, threads;

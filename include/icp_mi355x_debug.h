@@ -39,6 +39,12 @@ int icp_fixed_point_skips(icp_handle *h, uint64_t *out);
  * evaluation that missed its window finds no pose on the device, does not run and is counted in neither. */
 int icp_run_ahead_counters(icp_handle *h, uint64_t out[2]);
 
+/* Observability: evaluations with filed candidates (gn_win.hip: k_win_hist_sums_bkt / _bkt2 and the finishing launches
+ * k_win_pick / k_win_pick2, one workgroup per dimension; the sharded finish counts too).  out[0] = such evaluations
+ * launched since the handle was created, out[1] = window evaluations still to take the second pass over the points
+ * after files that were not usable (they count down to 0).  h = NULL: the scratch handle behind the free functions. */
+int icp_gn_filed_counters(icp_handle *h, uint64_t out[2]);
+
 /* Observability: certified matches (the searches of an estimate call after the first, beyond 65 536 source points:
  * a query whose previous match is provably still its nearest neighbour -- it has moved less than the margin the
  * last walk left it -- is not searched again).  out[0] = searches that checked certificates
