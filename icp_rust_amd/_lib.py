@@ -197,6 +197,9 @@ SIGNATURES = {
     "icp_batch_evaluate": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_double, _vp, _vp]),
     "icp_batch_evaluate_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_double, _vp, _vp]),
     "icp_batch_evaluate_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_estimate_gated": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
+    "icp_estimate_gated_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
+    "icp_gate_pairs_device": (C.c_int, [_vp, _vp, _sz, _pp, _vp, C.c_double, _vp, _vp, _vp, C.POINTER(_sz)]),
 }
 
 _lib = None

@@ -425,10 +425,17 @@ class _Icp:
         return out, perm[:d_src.shape[0]]
 
     # -- the reference's method ------------------------------------------------------
-    def estimate(self, src, initial_transform, max_iter, return_info=False):
+    def estimate(self, src, initial_transform, max_iter, return_info=False, max_correspondence_distance=None):
         """Icp2d::estimate / Icp3d::estimate (src/lib.rs:105-130, 148-173).  return_info=True also
         returns the last correspondence indices and the inner-iteration counts; "inner" only the
-        counts (no index buffer, no device-to-host copy)."""
+        counts (no index buffer, no device-to-host copy).
+        EXTENSION (include/icp_mi355x.h section 10): with max_correspondence_distance = r the estimator of every
+        outer iteration sees only the pairs with d2 <= r * r (icp_estimate_gated[_device]; evaluate()'s inlier
+        rule), and return_info also returns the per-iteration inlier counts, after the inner counts.  None calls
+        what it always called and returns what it always returned."""
+        if max_correspondence_distance is not None:
+            return self._estimate_gated(src, initial_transform, max_iter, return_info,
+                                        float(max_correspondence_distance))
         o = Transform()
         inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
         if _is_device_tensor(src):
@@ -461,6 +468,64 @@ class _Icp:
         if return_info:
             return o, idx[:n], inner[:max_iter]
         return o
+
+    def _estimate_gated(self, src, initial_transform, max_iter, return_info, r):
+        """estimate() with a maximum correspondence distance: icp_estimate_gated[_device]."""
+        if not r >= 0.0:  # (also a NaN)
+            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {r}")
+        o = Transform()
+        inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        inl = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        want_idx = bool(return_info) and return_info != "inner"
+        if _is_device_tensor(src):
+            import torch
+
+            self._dev(src, "src")
+            n = src.shape[0]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if want_idx else None
+            check(lib().icp_estimate_gated_device(self._h, C.c_void_p(src.data_ptr()), n,
+                                                  C.byref(initial_transform.pose), max_iter, r, C.byref(o.pose),
+                                                  C.c_void_p(idx.data_ptr()) if want_idx else None,
+                                                  C.c_void_p(inner.ctypes.data), C.c_void_p(inl.ctypes.data)),
+                  "icp_estimate_gated_device")
+            if want_idx:
+                idx = idx[:n].cpu().numpy().view(np.uint32)
+        else:
+            s = _host(src, self.DIM)
+            n = s.shape[0]
+            idx = np.zeros(max(n, 1), dtype=np.uint32) if want_idx else None
+            check(lib().icp_estimate_gated(self._h, _ptr(s), n, C.byref(initial_transform.pose), max_iter, r,
+                                           C.byref(o.pose), C.c_void_p(idx.ctypes.data) if want_idx else None,
+                                           C.c_void_p(inner.ctypes.data), C.c_void_p(inl.ctypes.data)),
+                  "icp_estimate_gated")
+            if want_idx:
+                idx = idx[:n]
+        if return_info == "inner":
+            return o, inner[:max_iter], inl[:max_iter]
+        if return_info:
+            return o, idx, inner[:max_iter], inl[:max_iter]
+        return o
+
+    def gate_pairs_device(self, d_src, transform, d_idx, max_correspondence_distance, d_a, d_b, d_kept=None):
+        """The gate alone (icp_gate_pairs_device): the pairs of the points with d2 <= r * r, dense and in the
+        order of d_src, into d_a / d_b (n x 2); d_kept (optional, n words) receives their positions.  Returns
+        their number."""
+        self._dev(d_src, "src")
+        n = d_src.shape[0]
+        _dev_index(d_idx, n, self._device, "d_idx")
+        for t, what in ((d_a, "d_a"), (d_b, "d_b")):
+            _dev_points(t, 2, self._device, what)
+            if t.shape[0] < n:
+                raise ValueError(f"{what}: holds {t.shape[0]} pairs, {n} are needed")
+        if d_kept is not None:
+            _dev_index(d_kept, n, self._device, "d_kept")
+        kept = C.c_size_t(0)
+        check(lib().icp_gate_pairs_device(self._h, C.c_void_p(d_src.data_ptr()), n, C.byref(transform.pose),
+                                          C.c_void_p(d_idx.data_ptr()), float(max_correspondence_distance),
+                                          C.c_void_p(d_a.data_ptr()), C.c_void_p(d_b.data_ptr()),
+                                          C.c_void_p(d_kept.data_ptr()) if d_kept is not None else None,
+                                          C.byref(kept)), "icp_gate_pairs_device")
+        return int(kept.value)
 
     # -- EXTENSION (not in the reference): the quality of a pose, include/icp_mi355x.h section 9 --
     def evaluate(self, src, transform, max_correspondence_distance=float("inf"), return_indices=False):

@@ -1139,6 +1139,13 @@ extern "C" int icp_estimate_transform_device(icp_handle *h, const double *d_a, c
   return estimate_transform_loop(h, d_a, d_b, n, out, inner_iters, [](const Pose &) { return hipSuccess; });
 }
 
+// the same loop for the other translation units of the ABI (api_gate.hip)
+int icp::api::estimate_transform_on_pairs(icp_handle *h, const double *d_a, const double *d_b, size_t n, Pose *out,
+                                          uint32_t *inner_iters, int first_kind, int second_kind) {
+  return estimate_transform_loop(h, d_a, d_b, n, out, inner_iters, [](const Pose &) { return hipSuccess; }, nullptr,
+                                 false, false, first_kind, second_kind);
+}
+
 // Icp{2,3}d::estimate (src/lib.rs:105-130, 148-173) on a device-resident source cloud.
 //
 // Speculative search: once the inner loop has needed exactly one update in the previous outer

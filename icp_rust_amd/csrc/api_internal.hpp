@@ -55,6 +55,17 @@ void loop_timed_out(Workspace &w);
 void free_loop_inbox(Workspace &w);  // (api_shard.hip)
 void free_loop_plan(void *p);
 
+// estimate_transform (src/lib.rs:59-84) on device pairs as the library's own loops run it (api.hip:
+// estimate_transform_loop, everything on h->stream, no hook); first_kind / second_kind name the window predictions of
+// its first two evaluations (common.hpp: Workspace::win_kind)
+int estimate_transform_on_pairs(icp_handle *h, const double *d_a, const double *d_b, size_t n, Pose *out,
+                                uint32_t *inner_iters, int first_kind, int second_kind);
+// the gate of a registration with a maximum correspondence distance (gate.hip): enqueues the stable compaction of the
+// pairs with d2 <= r2 on h->stream; gate_count is the survivors' number once that stream has been waited for
+hipError_t launch_gate(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
+                       double *d_a, double *d_b, uint32_t *d_kept);
+size_t gate_count(const icp_handle *h);
+
 }  // namespace api
 hipError_t launch_sel_init(icp_handle *h, size_t n);  // (gn.hip)
 hipError_t launch_stddevs(icp_handle *h, const double *d_a, const double *d_b, size_t n, const Pose &T);

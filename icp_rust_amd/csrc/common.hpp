@@ -160,7 +160,7 @@ struct GnResult {
   int nan_flag;
   int overflow;  // 1: too many candidates (radix path needed), 2: the window missed (gn_pull.hip needed)
   unsigned seq;  // written last, system scope: the host polls it instead of waiting for the stream
-  unsigned pad;
+  unsigned pad;  // no evaluation touches it: gate.hip leaves the survivors' count of a gate here (k_gate_place; api::gate_count)
   // sharded evaluations: how many ranks answered {OK, RETRY_REPLICATED, NONE, anything else} in the hist stage
   // (the status words behind the histograms, summed over the ranks with them; shard.hip:k_shard_fold)
   unsigned status[4];

@@ -114,7 +114,7 @@ def run_scan3d(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, p
 
 
 def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, max_frames=None,
-                    point_to_plane=None):
+                    point_to_plane=None, max_correspondence_distance=None):
     """EXTENSION, not in the reference (BASELINE.json configs[4]): the
     scan3d frames registered against a map that grows.  The map starts as frame 0 (filtered as
     examples/scan3d.rs:63-69 does); every later frame is registered against the whole map with
@@ -126,7 +126,12 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
     point-to-plane residual instead (Icp3d.estimate_point_to_plane, the other labelled extension); every
     map point carries the normal of its k nearest map points AT THE TIME IT WAS INSERTED
     (compute_normals for frame 0, update_normals after every append).
+    `max_correspondence_distance=r` (point-to-point only): every frame holds points the map has not seen yet, so
+    the frames are registered on the pairs within r of the map (estimate(..., max_correspondence_distance=r),
+    include/icp_mi355x.h section 10); None registers as before.
     Returns (transforms, path_xy, map_handle)."""
+    if point_to_plane and max_correspondence_distance is not None:
+        raise ValueError("max_correspondence_distance applies to the point-to-point registration only")
     icp_factory = icp_factory or Icp3d
     packets = np.asarray(packets, dtype=np.float64)
     world = icp_factory(remove_invalid_values(packets[0:step]))
@@ -140,6 +145,9 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
         index += step
         if point_to_plane:
             transform = world.estimate_point_to_plane(scan, transform, max_iter)
+        elif max_correspondence_distance is not None:
+            transform = world.estimate(scan, transform, max_iter,
+                                       max_correspondence_distance=max_correspondence_distance)
         else:
             transform = world.estimate(scan, transform, max_iter)
         world.append(scan, transform)

@@ -61,7 +61,7 @@ extern "C" {
 /* 8: additions only (section 8: icp_batch_*, many small registrations in one launch; icp_batch_counters in
  * icp_mi355x_debug.h).  Everything of version 7 is unchanged.  Section 9 (icp_quality, icp_evaluate*,
  * icp_batch_evaluate*; icp_batch_evaluate_counters in icp_mi355x_debug.h) was added later without a bump: an addition
- * detectable by symbol */
+ * detectable by symbol; so was section 10 (icp_estimate_gated*, icp_gate_pairs_device) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -589,6 +589,52 @@ int icp_batch_evaluate(icp_batch *b, const double *src, size_t src_points, const
 int icp_batch_evaluate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
                               size_t dst_points, const icp_batch_item *items, size_t count, double max_dist,
                               icp_quality *out, int *status);
+
+/* ================================================================================
+ * 10. EXTENSION (not in the reference): registration with a maximum correspondence distance
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  icp_estimate lets every source point pull on
+ * the pose; only the Huber / MAD weights stand between an object the target does not hold and the result.  Here the
+ * estimator sees the INLIERS of each outer iteration only -- section 9's inlier rule, so a caller registers on the
+ * pairs it scores a pose by.  The reference has no gate: no parity claim; DESIGN.md section 9e restates the definition.
+ *
+ * icp_estimate_gated[_device] runs the outer loop of Icp2d / Icp3d::estimate (src/lib.rs:105-130, 148-173).  For
+ * outer iteration `it` at pose T, for every source point i:
+ *   q, j, b = dst[j] and d2 exactly as section 9 defines them (transform_xy without FMA, the handle's exact nearest
+ *   neighbour, d2 = ((dx dx + dy dy) + dz dz) in the handle's dimension);
+ *   inlier = d2 <= r * r (r = max_dist, r * r in f64; a NaN d2 is never an inlier).
+ * The pairs (xy(q), xy(b)) of the inliers, IN FOLD ORDER WITH THE OTHERS REMOVED AND THE ORDER KEPT, go to
+ * estimate_transform (src/lib.rs:59-84); the update is composed as src/lib.rs:127, 170 do.  The fold order over all n
+ * points is the one icp_estimate_device would use (the caller's order up to 65 536 points and on the sweep engine, the
+ * snapshot order above that); icp_last_fold_order reports it for a gated call too.  The sums of an evaluation are
+ * folded in the tree of icp_reduce_geometry(number of inliers).
+ *   fewer than two inliers: the iteration applies no update (check_input_size, src/lib.rs:186-189), inner_iters[it] = 0;
+ *   inliers[it] (nullable, max_iter words): the number of inliers of that iteration;
+ *   last_idx / d_last_idx (nullable): the correspondences of ALL n points at the last iteration, caller order, as
+ *   icp_estimate returns them;
+ *   the fixed-point exit of icp_estimate applies unchanged: the iterations it skips report inner_iters = 0 and the
+ *   inlier count of the iteration that found the fixed point (same pose, hence the same count).
+ * Statuses: ICP_BAD_ARGUMENT (max_dist NaN or negative, a required pointer NULL: checked before any device use; +inf
+ * and 0.0 are valid bounds); ICP_EMPTY_DST (no targets); ICP_NAN_INPUT (an inlier pair with a NaN residual); n == 0
+ * and max_iter == 0 behave as in icp_estimate.
+ * Consequence: for inputs without a NaN d2, max_dist = +inf returns the pose, the indices and the inner counts of
+ * icp_estimate[_device], bit for bit, at every size and on both engines (every evaluation pipeline returns the same
+ * bits for the same pairs in the same order).  With a finite bound a source point with a NaN coordinate is dropped
+ * like any other outlier.  A call takes the general path at every size: clouds of the one-launch registration
+ * (section 2) are served by several launches per iteration here.
+ *
+ * icp_gate_pairs_device: the gate alone, in the style of section 4 (device buffers; synchronises the stream).  From
+ * the source cloud, a pose and the indices of a search at that pose (icp_correspond_device, icp_nn_search_device) it
+ * writes the inliers' pairs densely, in the order of d_src: d_a_xy[k] = xy(T src[i_k]), d_b_xy[k] = xy(dst[idx[i_k]])
+ * for the k-th inlier i_k; d_kept[k] = i_k (nullable); *kept = their number.  d_a_xy, d_b_xy (and d_kept) hold n
+ * entries. */
+int icp_estimate_gated(icp_handle *h, const double *src, size_t n, const icp_pose *init, size_t max_iter,
+                       double max_dist, icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters, uint32_t *inliers);
+int icp_estimate_gated_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init, size_t max_iter,
+                              double max_dist, icp_pose *out, uint32_t *d_last_idx, uint32_t *inner_iters,
+                              uint32_t *inliers);
+int icp_gate_pairs_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                          double max_dist, double *d_a_xy, double *d_b_xy, uint32_t *d_kept, size_t *kept);
 
 #ifdef __cplusplus
 }
