@@ -648,6 +648,33 @@ class _Icp:
         check(lib().icp_grid_append_counters(self._h, out), "icp_grid_append_counters")
         return int(out[0]), int(out[1])
 
+    def crop(self, center, radius, return_index=False):
+        """Keep the targets inside the xy disc of `radius` around `center` (two values: a caller crops around
+        transform.t) and remove the others (icp_crop_targets, include/icp_mi355x.h section 11): target i is kept iff
+        (x - cx)^2 + (y - cy)^2 <= radius^2.  The kept targets keep their order and their normals; afterwards the
+        handle behaves like a fresh Icp*::new on the kept cloud.  Returns the number of targets removed; with
+        return_index=True also new_index (uint32, one per old target: its new index, 0xffffffff if removed)."""
+        c = _vec(center, 2)
+        r = float(radius)
+        if not r >= 0.0 or np.isnan(c).any():  # (also a NaN radius)
+            raise ValueError(f"crop needs a centre without NaN and a radius >= 0 (or +inf), got {c.tolist()}, {r}")
+        m_before = self.target_count
+        index = np.zeros(max(m_before, 1), dtype=np.uint32) if return_index else None
+        removed = C.c_size_t(0)
+        check(lib().icp_crop_targets(self._h, c.ctypes.data_as(_dp), r,
+                                     C.c_void_p(index.ctypes.data) if return_index else None, C.byref(removed)),
+              "icp_crop_targets")
+        if removed.value:
+            self._keep = None  # the kept cloud lives in the handle's own storage
+        self.m = self.target_count
+        return (int(removed.value), index[:m_before]) if return_index else int(removed.value)
+
+    def crop_counters(self):
+        """(crops served by moving the search grid's sorted records, crops that rebuilt the grid)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().icp_grid_crop_counters(self._h, out), "icp_grid_crop_counters")
+        return int(out[0]), int(out[1])
+
     def reserve(self, capacity):
         check(lib().icp_reserve_targets(self._h, int(capacity)), "icp_reserve_targets")
         self._keep = None if capacity > self.m else self._keep
@@ -769,6 +796,15 @@ class IcpMulti:
         check(lib().icp_multi_append_targets(self._h, _ptr(p), p.shape[0],
                                              C.byref(transform.pose) if transform is not None else None),
               "icp_multi_append_targets")
+
+    def crop(self, center, radius):
+        """EXTENSION (icp_multi_crop_targets): every rank crops its replica of the target cloud to the xy disc;
+        returns the number of targets removed"""
+        c = _vec(center, 2)
+        removed = C.c_size_t(0)
+        check(lib().icp_multi_crop_targets(self._h, c.ctypes.data_as(_dp), float(radius), C.byref(removed)),
+              "icp_multi_crop_targets")
+        return int(removed.value)
 
     @property
     def target_count(self):

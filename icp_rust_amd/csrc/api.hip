@@ -403,6 +403,8 @@ void free_handle(icp_handle *h) {  // really release everything
   (void)hipFree(h->qsort.d_prev);
   (void)hipFree(h->shard.d_ordered);
   (void)hipFree(h->d_normals);
+  (void)hipFree(h->d_dst_alt);
+  (void)hipFree(h->d_normals_alt);
   (void)hipFree(h->d_plane_pairs);
   (void)hipFree(h->d_plane_fa);
   (void)hipFree(h->d_plane_fb);
@@ -463,6 +465,7 @@ extern "C" void icp_destroy(icp_handle *h) {
     h->prof_seen = 0;
     h->grid.built = false;
     h->grid.appends_moved = h->grid.appends_rebuilt = 0;
+    h->grid.crops_moved = h->grid.crops_rebuilt = 0;
     h->qsort.valid = false;
     h->qsort.have_prev = false;
     h->qsort.slot_order = false;

@@ -338,6 +338,7 @@ struct Grid {
   size_t m_full = 0;            // targets at the last full build (the cell size was chosen for that many)
   bool rcell_valid = false;     // d_rcell describes the current records
   unsigned long long appends_moved = 0, appends_rebuilt = 0;  // observability (icp_grid_append_counters)
+  unsigned long long crops_moved = 0, crops_rebuilt = 0;      // ... and of icp_crop_targets (icp_grid_crop_counters)
   uint32_t *d_flag = nullptr;   // one word: a new point outside the grid's box (or not finite)
 };
 
@@ -444,6 +445,10 @@ struct icp_handle {
   unsigned prof_seen = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_free;  // event pairs read out, kept for the next samples
+  // EXTENSION (crop.hip): the second set of the cloud's buffers -- icp_crop_targets compacts the points and the normals
+  // out of place into them and swaps the sets on success (a map cropped every frame allocates once)
+  double *d_dst_alt = nullptr, *d_normals_alt = nullptr;
+  size_t cap_dst_alt = 0, cap_normals_alt = 0;
 };
 
 namespace icp {

@@ -1,0 +1,407 @@
+// EXTENSION beyond the reference (include/icp_mi355x.h section 11): the sliding-window map -- icp_crop_targets keeps the
+// targets of a handle that lie in a disc of the xy plane and lets go of the others; the counterpart of
+// icp_append_targets (section 6).  Two STABLE compactions, each in the shape of the gate (gate.hip): a mark launch that
+// counts the survivors of every tile of 1 024 consecutive elements (ballot + lane rank per wave), a chunk-sum launch
+// (always run here: its sums are also how the host learns the total) and a place launch in which a workgroup per tile
+// adds up the counts in front of it and moves its survivors there.
+//   targets   k_crop_mark<DIM>      w[i] = kept ? 0 : kCropGone by the keep rule, cnt[tile]
+//             k_crop_place<DIM>     w[i] = the new index of target i (or kCropGone): the new_index table; the points, and
+//                                   the normals where present, move to their new index in a second buffer
+//   records   k_crop_rec_mark       the grid's records are cell-sorted and removing records keeps them sorted: the
+//             k_crop_rec_place      record at sorted position p survives iff new_index[pts[p].idx] is valid and moves to
+//                                   the number of survivors in front of it, its idx rewritten; that number is left in
+//                                   w[p] for EVERY p, so that
+//             k_crop_starts         start2[c] = w[start[c]] (one gather), and the sentinel records follow the last one
+// Every position counts survivors that come EARLIER in the input: the order is kept and a position is a pure function
+// of the inputs.  No atomics, no float reductions, no workgroup waits for another.  The grid keeps the box and the cell
+// size of its last full build (upper bounds of the kept cloud's: exact, like the grid of an incremental append).
+#include <cmath>
+#include <utility>
+
+#include "api_internal.hpp"
+
+using namespace icp;
+using namespace icp::api;
+
+namespace icp {
+namespace {
+
+constexpr unsigned kCropThreads = 256, kCropWaves = kCropThreads / 64;
+constexpr unsigned kCropRounds = 4;
+constexpr unsigned kCropTile = kCropThreads * kCropRounds;  // elements per workgroup
+constexpr unsigned kCropChunk = 8192;                       // tiles whose counts one workgroup adds up itself (2^23 elements)
+constexpr uint32_t kCropGone = 0xffffffffu;
+// The kept cloud has fallen below 1 / kRebuildShrink of the cloud the grid's cell size was chosen for: rebuild (the
+// mirror of append_grid's kRebuildGrowth)
+constexpr double kRebuildShrink = 1.5;
+
+// the sum of v over the workgroup (every thread calls it; every thread gets it)
+__device__ __forceinline__ unsigned crop_block_sum(unsigned v, unsigned *lds) {
+  const unsigned tid = threadIdx.x;
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+  __syncthreads();  // (lds may still be read from an earlier call)
+  if ((tid & 63u) == 0) lds[tid >> 6] = v;
+  __syncthreads();
+  unsigned t = 0;
+#pragma unroll
+  for (unsigned w = 0; w < kCropWaves; ++w) t += lds[w];
+  return t;
+}
+
+// in[k]: the flag of the thread's element of round k (element k * kCropThreads + tid of the tile).  rank[k] = the
+// tile's survivors in front of that element (whether it survives or not); returns the tile's survivors.
+__device__ __forceinline__ unsigned crop_tile_ranks(const bool (&in)[kCropRounds], unsigned (&rank)[kCropRounds],
+                                                    unsigned (*wcnt)[kCropWaves]) {
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const unsigned long long mask = __ballot(in[k]);
+    rank[k] = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) wcnt[k][wave] = __popcll(mask);
+  }
+  __syncthreads();
+  unsigned total = 0;
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+#pragma unroll
+    for (unsigned w = 0; w < kCropWaves; ++w) {
+      if (w == wave) rank[k] += total;
+      total += wcnt[k][w];
+    }
+  }
+  return total;
+}
+
+// the survivors of the tiles in front of `tile`: the chunk sums in front of its chunk + the counts in front of it there
+__device__ __forceinline__ unsigned crop_tile_base(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ sums,
+                                                   unsigned tile, unsigned *lds) {
+  const unsigned tid = threadIdx.x, chunk = tile / kCropChunk;
+  unsigned s = 0;
+  for (unsigned c = tid; c < chunk; c += kCropThreads) s += sums[c];
+  for (size_t t = (size_t)chunk * kCropChunk + tid; t < tile; t += kCropThreads) s += cnt[t];
+  return crop_block_sum(s, lds);
+}
+
+}  // namespace
+
+// The keep rule (include/icp_mi355x.h section 11): dx = x - cx, dy = y - cy, d2 = dx dx + dy dy (no FMA: the library is
+// compiled with -ffp-contract=off), kept iff d2 <= r2 (false for a NaN d2).  z takes no part.
+template <int DIM>
+__global__ __launch_bounds__(kCropThreads) void k_crop_mark(const double *__restrict__ dst, unsigned m, double cx, double cy,
+                                                            double r2, uint32_t *__restrict__ w,
+                                                            uint32_t *__restrict__ cnt) {
+  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
+  const size_t first = (size_t)blockIdx.x * kCropTile;
+  bool in[kCropRounds];
+  unsigned rank[kCropRounds];
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const size_t i = first + k * kCropThreads + threadIdx.x;
+    in[k] = false;
+    if (i < m) {
+      const double dx = dst[i * DIM] - cx, dy = dst[i * DIM + 1] - cy;
+      const double d2 = dx * dx + dy * dy;
+      in[k] = d2 <= r2;
+      w[i] = in[k] ? 0u : kCropGone;
+    }
+  }
+  const unsigned total = crop_tile_ranks(in, rank, wcnt);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+// sums[c] = the survivors of tiles [kCropChunk c, kCropChunk (c + 1))
+__global__ __launch_bounds__(kCropThreads) void k_crop_chunks(const uint32_t *__restrict__ cnt, unsigned tiles,
+                                                              uint32_t *__restrict__ sums) {
+  __shared__ unsigned lds[kCropWaves];
+  const size_t t0 = (size_t)blockIdx.x * kCropChunk;
+  const size_t t1 = t0 + kCropChunk < tiles ? t0 + kCropChunk : tiles;
+  unsigned s = 0;
+  for (size_t t = t0 + threadIdx.x; t < t1; t += kCropThreads) s += cnt[t];
+  s = crop_block_sum(s, lds);
+  if (threadIdx.x == 0) sums[blockIdx.x] = s;
+}
+
+// w: in, the marks; out, the new_index table.  *normals_kept (nullable) receives the survivors among the first
+// normals_m targets when normals_m < m (the host knows it otherwise: all of them).
+template <int DIM>
+__global__ __launch_bounds__(kCropThreads) void k_crop_place(const double *__restrict__ dst,
+                                                             const double *__restrict__ normals, unsigned normals_m,
+                                                             unsigned m, uint32_t *__restrict__ w,
+                                                             const uint32_t *__restrict__ cnt,
+                                                             const uint32_t *__restrict__ sums, double *__restrict__ out,
+                                                             double *__restrict__ out_normals,
+                                                             uint32_t *__restrict__ normals_kept) {
+  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
+  __shared__ unsigned lds[kCropWaves];
+  const unsigned base = crop_tile_base(cnt, sums, blockIdx.x, lds);
+  const size_t first = (size_t)blockIdx.x * kCropTile;
+  bool in[kCropRounds];
+  unsigned rank[kCropRounds];
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const size_t i = first + k * kCropThreads + threadIdx.x;
+    in[k] = i < m && w[i] != kCropGone;
+  }
+  (void)crop_tile_ranks(in, rank, wcnt);
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const size_t i = first + k * kCropThreads + threadIdx.x;
+    if (i >= m) continue;
+    const size_t at = (size_t)base + rank[k];  // (< the survivors in all: inside a buffer that holds them)
+    if (normals_kept && i == normals_m) *normals_kept = (uint32_t)at;
+    if (!in[k]) continue;
+    w[i] = (uint32_t)at;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) out[at * DIM + d] = dst[i * DIM + d];
+    if (out_normals && i < normals_m) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) out_normals[at * 3 + d] = normals[i * 3 + d];
+    }
+  }
+}
+
+// w[p] = the new index of the target behind the record at sorted position p (kCropGone: removed)
+__global__ __launch_bounds__(kCropThreads) void k_crop_rec_mark(const GridPoint *__restrict__ pts, unsigned m,
+                                                                const uint32_t *__restrict__ new_index,
+                                                                uint32_t *__restrict__ w, uint32_t *__restrict__ cnt) {
+  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
+  const size_t first = (size_t)blockIdx.x * kCropTile;
+  bool in[kCropRounds];
+  unsigned rank[kCropRounds];
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const size_t p = first + k * kCropThreads + threadIdx.x;
+    in[k] = false;
+    if (p < m) {
+      const uint32_t j = pts[p].idx;
+      const uint32_t to = j < m ? new_index[j] : kCropGone;  // (a record's idx is always < m: this only keeps the read in bounds)
+      w[p] = to;
+      in[k] = to != kCropGone;
+    }
+  }
+  const unsigned total = crop_tile_ranks(in, rank, wcnt);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+// w: in, the records' new indices; out, for EVERY sorted position p the survivors in front of it
+__global__ __launch_bounds__(kCropThreads) void k_crop_rec_place(const GridPoint *__restrict__ pts, unsigned m,
+                                                                 uint32_t *__restrict__ w, const uint32_t *__restrict__ cnt,
+                                                                 const uint32_t *__restrict__ sums,
+                                                                 GridPoint *__restrict__ pts2) {
+  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
+  __shared__ unsigned lds[kCropWaves];
+  const unsigned base = crop_tile_base(cnt, sums, blockIdx.x, lds);
+  const size_t first = (size_t)blockIdx.x * kCropTile;
+  bool in[kCropRounds];
+  unsigned rank[kCropRounds];
+  uint32_t to[kCropRounds];
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const size_t p = first + k * kCropThreads + threadIdx.x;
+    to[k] = p < m ? w[p] : kCropGone;
+    in[k] = to[k] != kCropGone;
+  }
+  (void)crop_tile_ranks(in, rank, wcnt);
+#pragma unroll
+  for (unsigned k = 0; k < kCropRounds; ++k) {
+    const size_t p = first + k * kCropThreads + threadIdx.x;
+    if (p >= m) continue;
+    const size_t at = (size_t)base + rank[k];
+    w[p] = (uint32_t)at;
+    if (!in[k]) continue;
+    GridPoint r = pts[p];
+    r.idx = to[k];
+    pts2[at] = r;
+  }
+}
+
+// start2[c] = the survivors in front of sorted position start[c] (pos[] of k_crop_rec_place; start[c] == m: all of
+// them); the threads behind the cell offsets write the sentinel records behind the last survivor
+__global__ void k_crop_starts(const uint32_t *__restrict__ start, unsigned nscan, const uint32_t *__restrict__ pos,
+                              unsigned m, unsigned kept, uint32_t *__restrict__ start2, GridPoint *__restrict__ pts2) {
+  const unsigned c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < nscan) {
+    const uint32_t s = start[c];
+    start2[c] = s < m ? pos[s] : kept;
+  } else if (c < nscan + kGridPad) {
+    pts2[(size_t)kept + (c - nscan)] = GridPoint{__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf(), 0u};
+  }
+}
+
+namespace {
+
+unsigned crop_tiles(size_t n) { return (unsigned)((n + kCropTile - 1) / kCropTile); }
+unsigned crop_chunks(unsigned tiles) { return (tiles + kCropChunk - 1) / kCropChunk; }
+
+int crop_quiesce(icp_handle *h) {
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->own_stream) HIP_TRY(hipStreamSynchronize(h->own_stream));
+  if (h->stream != h->own_stream) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->ws.spec_stream) HIP_TRY(hipStreamSynchronize(h->ws.spec_stream));
+  return ICP_OK;
+}
+
+// the second compaction: the grid's records into the second set of the sorted arrays (nothing of the handle changes
+// here; the caller swaps the sets on success)
+hipError_t crop_move_records(icp_handle *h, unsigned m_old, unsigned kept, const uint32_t *new_index, uint32_t *cnt) {
+  Grid &G = h->grid;
+  hipStream_t s = h->stream;
+  hipError_t e;
+  const unsigned nscan = G.ncell + 1, tiles = crop_tiles(m_old), chunks = crop_chunks(tiles);
+  uint32_t *sums = cnt + tiles;
+  if ((e = reserve(G.d_pts2, G.cap_pts2, (size_t)kept + kGridPad)) != hipSuccess) return e;
+  if ((e = reserve(G.d_start2, G.cap_start2, (size_t)nscan)) != hipSuccess) return e;
+  if ((e = reserve(G.d_rcell2, G.cap_rcell2, (size_t)m_old)) != hipSuccess) return e;  // (free between appends: the marks)
+  uint32_t *w = G.d_rcell2;
+  hipLaunchKernelGGL(k_crop_rec_mark, dim3(tiles), dim3(kCropThreads), 0, s, (const GridPoint *)G.d_pts, m_old, new_index, w,
+                     cnt);
+  hipLaunchKernelGGL(k_crop_chunks, dim3(chunks), dim3(kCropThreads), 0, s, (const uint32_t *)cnt, tiles, sums);
+  hipLaunchKernelGGL(k_crop_rec_place, dim3(tiles), dim3(kCropThreads), 0, s, (const GridPoint *)G.d_pts, m_old, w,
+                     (const uint32_t *)cnt, (const uint32_t *)sums, G.d_pts2);
+  hipLaunchKernelGGL(k_crop_starts, dim3((nscan + kGridPad + 255) / 256), dim3(256), 0, s, (const uint32_t *)G.d_start, nscan,
+                     (const uint32_t *)w, m_old, kept, G.d_start2, G.d_pts2);
+  return hipGetLastError();
+}
+
+int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *new_index, size_t *removed) {
+  if (removed) *removed = 0;
+  ICP_TRY_RC(crop_quiesce(h));
+  if (h->m == 0) return ICP_OK;
+  Grid &G = h->grid;
+  hipStream_t s = h->stream;
+  const unsigned m_old = (unsigned)h->m, tiles = crop_tiles(m_old), chunks = crop_chunks(tiles);
+  const int dim = h->dim;
+  // the new_index table: the grid's build temporary of m words, free between builds; the tile counts, the chunk sums and
+  // one word for the normals: the append's shift table, free between appends
+  HIP_TRY(reserve(G.t_cell_of, G.cap_tcell, (size_t)m_old));
+  HIP_TRY(reserve(G.t_shift, G.cap_shift, (size_t)tiles + chunks + 1));
+  uint32_t *w = G.t_cell_of, *cnt = G.t_shift, *sums = cnt + tiles, *aux = sums + chunks;
+  const double r2 = radius * radius;
+  if (dim == 3)
+    hipLaunchKernelGGL(k_crop_mark<3>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
+  else
+    hipLaunchKernelGGL(k_crop_mark<2>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
+  hipLaunchKernelGGL(k_crop_chunks, dim3(chunks), dim3(kCropThreads), 0, s, (const uint32_t *)cnt, tiles, sums);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint32_t> host(chunks + 1);
+  HIP_TRY(hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  size_t kept_ = 0;
+  for (unsigned c = 0; c < chunks; ++c) kept_ += host[c];
+  const unsigned kept = (unsigned)kept_;
+  if (kept == m_old) {  // nothing to remove: the handle is left exactly as it was
+    if (new_index)
+      for (unsigned i = 0; i < m_old; ++i) new_index[i] = i;
+    return ICP_OK;
+  }
+  // ---- out of place: the kept points (and normals) into the second buffers ----
+  const bool with_normals = dim == 3 && h->d_normals && h->normals_m > 0;
+  const unsigned normals_m = with_normals ? (unsigned)h->normals_m : 0u;
+  if (kept > 0) {
+    HIP_TRY(reserve(h->d_dst_alt, h->cap_dst_alt, (size_t)kept * dim));
+    if (with_normals) HIP_TRY(reserve(h->d_normals_alt, h->cap_normals_alt, (size_t)kept * 3));
+  }
+  const bool count_normals = with_normals && normals_m < m_old;
+  if (kept > 0 || new_index || count_normals) {
+    if (dim == 3)
+      hipLaunchKernelGGL(k_crop_place<3>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, (const double *)h->d_normals,
+                         normals_m, m_old, w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt,
+                         with_normals && kept > 0 ? h->d_normals_alt : nullptr, count_normals ? aux : nullptr);
+    else
+      hipLaunchKernelGGL(k_crop_place<2>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, (const double *)nullptr, 0u, m_old,
+                         w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt, (double *)nullptr,
+                         (uint32_t *)nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  size_t normals_after = with_normals ? kept : 0;
+  if (count_normals) {
+    HIP_TRY(hipMemcpyAsync(&host[chunks], aux, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    normals_after = host[chunks];
+  }
+  if (new_index) {
+    HIP_TRY(hipMemcpyAsync(new_index, w, (size_t)m_old * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  // ---- the grid: move the sorted records, unless there is none or its cell size is due for a re-tune ----
+  const bool move = G.built && kept > 0 && G.m_full > 0 && !((double)kept < (double)G.m_full / kRebuildShrink);
+  if (move) HIP_TRY(crop_move_records(h, m_old, kept, w, cnt));
+  HIP_TRY(hipStreamSynchronize(s));
+  // ---- success so far: swap.  What is kept for a way back: the old cloud's buffers (they become the second set) ----
+  const double *old_dst = h->d_dst;
+  const bool old_owns = h->owns_dst;
+  const size_t old_normals_m = h->normals_m;
+  if (kept > 0) {
+    std::swap(h->d_dst_own, h->d_dst_alt);
+    std::swap(h->cap_dst_own, h->cap_dst_alt);
+    if (with_normals) {
+      std::swap(h->d_normals, h->d_normals_alt);
+      std::swap(h->cap_normals, h->cap_normals_alt);
+    }
+  }
+  h->d_dst = h->d_dst_own;
+  h->owns_dst = true;  // (a handle from icp_create_device stops borrowing, as at its first append)
+  h->m = kept;
+  h->normals_m = normals_after;
+  h->qsort.valid = false;  // snapshots and previous matches refer to the old cloud
+  h->qsort.have_prev = false;
+  h->brute_valid = h->screen_valid = false;
+  hipError_t e = hipSuccess;
+  if (move) {
+    std::swap(G.d_pts, G.d_pts2);
+    std::swap(G.cap_pts, G.cap_pts2);
+    std::swap(G.d_start, G.d_start2);
+    std::swap(G.cap_start, G.cap_start2);
+    G.rcell_valid = false;  // (the next incremental append derives it from the cell offsets again)
+  } else {
+    e = build_grid(h);
+  }
+  if (e == hipSuccess && resolved_nn_mode(h) == ICP_NN_BRUTE) {
+    if ((e = build_target_soa(h)) == hipSuccess) e = build_target_screen(h);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    // back to the cloud as it was: its points and normals were never written; the search structures are rebuilt for
+    // them (only a rebuild can fail here: the moved records were complete before the swap)
+    if (kept > 0) {
+      std::swap(h->d_dst_own, h->d_dst_alt);
+      std::swap(h->cap_dst_own, h->cap_dst_alt);
+      if (with_normals) {
+        std::swap(h->d_normals, h->d_normals_alt);
+        std::swap(h->cap_normals, h->cap_normals_alt);
+      }
+    }
+    h->d_dst = old_dst;
+    h->owns_dst = old_owns;
+    h->m = m_old;
+    h->normals_m = old_normals_m;
+    (void)build_grid(h);
+    (void)hipStreamSynchronize(s);
+    return map_hip(e);
+  }
+  ++(move ? G.crops_moved : G.crops_rebuilt);
+  if (removed) *removed = (size_t)m_old - kept;
+  return ICP_OK;
+}
+
+}  // namespace
+}  // namespace icp
+
+extern "C" int icp_crop_targets(icp_handle *h, const double center_xy[2], double radius, uint32_t *new_index,
+                                size_t *removed) {
+  // (radius >= 0 is false for a NaN; so is c == c)
+  if (!h || !center_xy || !(center_xy[0] == center_xy[0]) || !(center_xy[1] == center_xy[1]) || !(radius >= 0.))
+    return ICP_BAD_ARGUMENT;
+  int devices = 0;
+  if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return ICP_NO_DEVICE;
+  return crop_targets(h, center_xy[0], center_xy[1], radius, new_index, removed);
+}
+
+// Observability: out[0] = crops served by moving the grid's sorted records, out[1] = crops that rebuilt the grid
+extern "C" int icp_grid_crop_counters(const icp_handle *h, uint64_t out[2]) {
+  if (!h || !out) return ICP_BAD_ARGUMENT;
+  out[0] = h->grid.crops_moved;
+  out[1] = h->grid.crops_rebuilt;
+  return ICP_OK;
+}

@@ -477,6 +477,21 @@ extern "C" int icp_multi_append_targets(icp_multi *M, const double *pts, size_t 
   M->m += k;
   return ICP_OK;
 }
+// EXTENSION (include/icp_mi355x.h section 11 across the ranks): every rank crops its replica of the target cloud to the
+// same disc; the replicas hold the same points, so every rank removes the same ones and M->m follows.
+extern "C" int icp_multi_crop_targets(icp_multi *M, const double center_xy[2], double radius, size_t *removed) {
+  if (!M || !center_xy || !(center_xy[0] == center_xy[0]) || !(center_xy[1] == center_xy[1]) || !(radius >= 0.))
+    return ICP_BAD_ARGUMENT;
+  if (removed) *removed = 0;
+  size_t gone = 0;
+  for (auto &R : M->r) {
+    const int rc = icp_crop_targets(R.h, center_xy, radius, nullptr, &gone);
+    if (rc != ICP_OK) return rc;  // (a rank that failed leaves the replicas different: the object is then unusable)
+  }
+  M->m -= gone;
+  if (removed) *removed = gone;
+  return ICP_OK;
+}
 extern "C" size_t icp_multi_target_count(const icp_multi *M) { return M ? M->m : 0; }
 
 extern "C" int icp_multi_counters(const icp_multi *M, uint64_t out[2]) {

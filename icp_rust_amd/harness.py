@@ -114,7 +114,7 @@ def run_scan3d(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, p
 
 
 def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, max_frames=None,
-                    point_to_plane=None, max_correspondence_distance=None):
+                    point_to_plane=None, max_correspondence_distance=None, map_radius=None):
     """EXTENSION, not in the reference (BASELINE.json configs[4]): the
     scan3d frames registered against a map that grows.  The map starts as frame 0 (filtered as
     examples/scan3d.rs:63-69 does); every later frame is registered against the whole map with
@@ -129,6 +129,9 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
     `max_correspondence_distance=r` (point-to-point only): every frame holds points the map has not seen yet, so
     the frames are registered on the pairs within r of the map (estimate(..., max_correspondence_distance=r),
     include/icp_mi355x.h section 10); None registers as before.
+    `map_radius=R` (either residual): a sliding-window map -- after every frame's append (and its update_normals) the
+    map is cropped to the xy disc of radius R around the registered position, world.crop(transform.t, R)
+    (include/icp_mi355x.h section 11); None calls nothing, so the map grows as before.
     Returns (transforms, path_xy, map_handle)."""
     if point_to_plane and max_correspondence_distance is not None:
         raise ValueError("max_correspondence_distance applies to the point-to-point registration only")
@@ -153,6 +156,8 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
         world.append(scan, transform)
         if point_to_plane:
             world.update_normals(point_to_plane)
+        if map_radius is not None:
+            world.crop(transform.t, map_radius)
         transforms.append(transform)
         path.append(transform.t.copy())
     return transforms, np.array(path).reshape(-1, 2), world
@@ -175,6 +180,8 @@ def main(argv=None):
     ap.add_argument("--max-iter", type=int, default=20)
     ap.add_argument("--point-to-plane", type=int, default=0, metavar="K",
                     help="scan2map: register with point-to-plane residuals, normals from K nearest map points (extension)")
+    ap.add_argument("--map-radius", type=float, default=None, metavar="R",
+                    help="scan2map: keep the map within R of the registered position (sliding window, extension)")
     args = ap.parse_args(argv)
     if args.loop == "scan2d":
         if not args.scan_dir:
@@ -192,7 +199,8 @@ def main(argv=None):
     else:
         stream = PacketFile(args.scan_dir).as_array() if args.scan_dir else \
             synth.synthetic_scan3d_packets(PACKETS_PER_FRAME * (args.frames + 1))
-        _, path, world = run_scan_to_map(stream, max_iter=args.max_iter, point_to_plane=args.point_to_plane or None)
+        _, path, world = run_scan_to_map(stream, max_iter=args.max_iter, point_to_plane=args.point_to_plane or None,
+                                         map_radius=args.map_radius)
         print(f"# map: {world.target_count} points")
     for k, (x, y) in enumerate(path):
         print(f"{k:4d} {x:+.9f} {y:+.9f}")

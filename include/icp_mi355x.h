@@ -61,7 +61,8 @@ extern "C" {
 /* 8: additions only (section 8: icp_batch_*, many small registrations in one launch; icp_batch_counters in
  * icp_mi355x_debug.h).  Everything of version 7 is unchanged.  Section 9 (icp_quality, icp_evaluate*,
  * icp_batch_evaluate*; icp_batch_evaluate_counters in icp_mi355x_debug.h) was added later without a bump: an addition
- * detectable by symbol; so was section 10 (icp_estimate_gated*, icp_gate_pairs_device) */
+ * detectable by symbol; so was section 10 (icp_estimate_gated*, icp_gate_pairs_device); so was section 11
+ * (icp_crop_targets, icp_multi_crop_targets; icp_grid_crop_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -635,6 +636,45 @@ int icp_estimate_gated_device(icp_handle *h, const double *d_src, size_t n, cons
                               uint32_t *inliers);
 int icp_gate_pairs_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
                           double max_dist, double *d_a_xy, double *d_b_xy, uint32_t *d_kept, size_t *kept);
+
+/* ================================================================================
+ * 11. EXTENSION (not in the reference): a target cloud that lets go -- the sliding-window map
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  The counterpart of icp_append_targets
+ * (section 6): a map that a scan-to-map loop feeds grows without bound; icp_crop_targets keeps the targets inside a disc
+ * of the xy plane and removes the others, on the device, normals included.  It keeps the contract section 6 gives an
+ * append: afterwards the handle answers like a fresh icp_create on the cloud it now holds.  The reference has no such
+ * thing: no parity claim; DESIGN.md section 9f restates the definition.
+ *
+ * The keep rule.  For centre (cx, cy) = center_xy and radius r (r >= 0, or +inf), target i with coordinates (x, y[, z]):
+ *   dx = x - cx, dy = y - cy, d2 = dx dx + dy dy                        (no FMA)
+ *   kept = d2 <= r * r (r * r in f64; a NaN d2 is never kept)
+ * The same xy disc applies to 2-D and 3-D handles (the pose is SE(2), z is never estimated: a caller crops around the
+ * translation of its pose).  +inf and 0.0 are valid radii.
+ * After a crop of a cloud of m_before targets:
+ *   the kept targets stay in their original relative order; target index = position in the kept sequence;
+ *   icp_read_targets returns them bit for bit;
+ *   new_index (nullable, host, m_before words): new_index[i] = the new index of old target i, 0xffffffff if removed;
+ *   *removed (nullable) = the number of targets removed;
+ *   every CORRESPONDENCE is that of a fresh icp_create on the kept cloud, and so is every pose, bit for bit, for source
+ *   clouds that keep the caller's fold order (up to 65 536 points); larger source clouds fall under the clause of
+ *   section 6: a cropped handle may keep the grid of its last full build, and each handle equals the oracle evaluated in
+ *   ITS fold order (icp_last_fold_order) bit for bit.
+ * Normals (section 7): kept targets keep their normals, compacted alongside the points; the number of targets that have
+ * one becomes the number of kept targets among those that had one.  A map whose normals were complete stays usable
+ * for icp_estimate_point_to_plane* without recomputation; after an append without an update,
+ * icp_update_target_normals still gives normals to exactly the kept targets that have none.
+ * Edges.  Nothing removed: nothing about the handle changes (it keeps borrowing a caller's device buffer; no counter
+ * moves).  Otherwise a handle made by icp_create_device stops borrowing, as at its first append; the caller's buffer is
+ * never written.  Everything removed: the handle behaves like one created on an empty cloud (ICP_EMPTY_DST from
+ * icp_estimate; a later append works).
+ * Statuses: ICP_BAD_ARGUMENT (h or center_xy NULL, a NaN centre, a NaN or negative radius: checked before any device
+ * use); ICP_NO_DEVICE, ICP_HIP_ERROR, ICP_OUT_OF_MEMORY as elsewhere.  On any failure the handle is what it was before
+ * the call (the cloud is compacted out of place and the buffers are swapped on success).
+ * icp_multi_crop_targets: every rank crops its replica, icp_multi_target_count follows; a rank that fails leaves the
+ * replicas different and the object unusable, as for icp_multi_append_targets. */
+int icp_crop_targets(icp_handle *h, const double center_xy[2], double radius, uint32_t *new_index, size_t *removed);
+int icp_multi_crop_targets(icp_multi *M, const double center_xy[2], double radius, size_t *removed);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,13 @@ int icp_single_launch_counters(icp_handle *h, uint64_t out[3]);
  * top of this section). */
 int icp_grid_append_counters(const icp_handle *h, uint64_t out[2]);
 
+/* ... and of icp_crop_targets (icp_mi355x.h section 11): out[0] = crops served by moving the grid's sorted records
+ * (a second stable compaction in record order, cell offsets by one gather: no atomics, no re-sort; the grid keeps the box
+ * and cell size of its last full build), out[1] = crops that rebuilt the grid (no grid was built, nothing was kept, or
+ * the kept cloud fell below 1 / 1.5 of the cloud the cell size was chosen for).  A crop that removes nothing counts in
+ * neither. */
+int icp_grid_crop_counters(const icp_handle *h, uint64_t out[2]);
+
 int icp_multi_counters(const icp_multi *M, uint64_t out[2]);
 
 /* ... and of the one-launch inner loop across the ranks (section 5b): out[0] launches (per rank), out[1] evaluations they
