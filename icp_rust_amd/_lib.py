@@ -200,6 +200,10 @@ SIGNATURES = {
     "icp_estimate_gated": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
     "icp_estimate_gated_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
     "icp_gate_pairs_device": (C.c_int, [_vp, _vp, _sz, _pp, _vp, C.c_double, _vp, _vp, _vp, C.POINTER(_sz)]),
+    "icp_estimate_point_to_plane_gated": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
+    "icp_estimate_point_to_plane_gated_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
+    "icp_gate_plane_pairs_device": (C.c_int, [_vp, _vp, _sz, _pp, _vp, C.c_double, _vp, _vp, C.POINTER(_sz)]),
+    "icp_multi_estimate_point_to_plane_gated": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
     "icp_crop_targets": (C.c_int, [_vp, _dp, C.c_double, _vp, C.POINTER(_sz)]),
     "icp_multi_crop_targets": (C.c_int, [_vp, _dp, C.c_double, C.POINTER(_sz)]),
     "icp_grid_crop_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

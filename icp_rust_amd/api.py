@@ -706,8 +706,16 @@ class _Icp:
               "icp_read_target_normals")
         return out
 
-    def estimate_point_to_plane(self, src, initial_transform, max_iter, return_info=False):
-        """Icp3d::estimate with the residual n_q . (T p - q) (extension; needs compute_normals())."""
+    def estimate_point_to_plane(self, src, initial_transform, max_iter, return_info=False,
+                                max_correspondence_distance=None):
+        """Icp3d::estimate with the residual n_q . (T p - q) (extension; needs compute_normals()).
+
+        `max_correspondence_distance=r` (include/icp_mi355x.h section 12): the inner loop of each outer iteration sees
+        only the pairs whose nearest target lies within r of the moved source point (d2 <= r * r, evaluate's inlier
+        rule), in the caller's order; `return_info` then returns (T, idx, inner, inliers).  None: the ungated call."""
+        if max_correspondence_distance is not None:
+            return self._estimate_point_to_plane_gated(src, initial_transform, max_iter, return_info,
+                                                       max_correspondence_distance)
         o = Transform()
         inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
         if _is_device_tensor(src):
@@ -729,6 +737,60 @@ class _Icp:
                                                 C.byref(o.pose), C.c_void_p(idx.ctypes.data),
                                                 C.c_void_p(inner.ctypes.data)), "icp_estimate_point_to_plane")
         return (o, idx[:n], inner[:max_iter]) if return_info else o
+
+    def _estimate_point_to_plane_gated(self, src, initial_transform, max_iter, return_info, bound):
+        r = float(bound)
+        if not r >= 0.0:  # (also a NaN)
+            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {bound!r}")
+        o = Transform()
+        inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        inl = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        if _is_device_tensor(src):
+            import torch
+
+            self._dev(src, "src")
+            n = src.shape[0]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_info else None
+            check(lib().icp_estimate_point_to_plane_gated_device(
+                self._h, C.c_void_p(src.data_ptr()), n, C.byref(initial_transform.pose), max_iter, r, C.byref(o.pose),
+                C.c_void_p(idx.data_ptr()) if return_info else None, C.c_void_p(inner.ctypes.data),
+                C.c_void_p(inl.ctypes.data)), "icp_estimate_point_to_plane_gated_device")
+            if not return_info:
+                return o
+            return o, idx[:n].cpu().numpy().view(np.uint32), inner[:max_iter], inl[:max_iter]
+        s = _host(src, self.DIM)
+        n = s.shape[0]
+        idx = np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib().icp_estimate_point_to_plane_gated(self._h, _ptr(s), n, C.byref(initial_transform.pose), max_iter, r,
+                                                      C.byref(o.pose), C.c_void_p(idx.ctypes.data),
+                                                      C.c_void_p(inner.ctypes.data), C.c_void_p(inl.ctypes.data)),
+              "icp_estimate_point_to_plane_gated")
+        return (o, idx[:n], inner[:max_iter], inl[:max_iter]) if return_info else o
+
+    def gate_plane_pairs_device(self, d_src, transform, d_idx, r, d_pairs, d_kept=None):
+        """The gate of a gated point-to-plane registration alone (icp_gate_plane_pairs_device): for the inliers of the
+        search result `d_idx` at `transform`, in the order of d_src, the eight doubles of a pair (ax, ay, qx, qy, dz, nx,
+        ny, nz) in d_pairs (n x 8 float64) and their source positions in d_kept (n int32, optional).  Returns their
+        number."""
+        import torch
+
+        r = float(r)
+        if not r >= 0.0:
+            raise ValueError(f"the bound must be >= 0 (or +inf), got {r!r}")
+        n = self._dev(d_src, "d_src").shape[0]
+        _dev_index(d_idx, n, self._device, "d_idx")
+        if not (_is_device_tensor(d_pairs) and d_pairs.dtype == torch.float64 and d_pairs.is_contiguous()
+                and d_pairs.dim() == 2 and d_pairs.shape[1] == 8 and d_pairs.shape[0] >= n
+                and d_pairs.device.index == self._device):
+            raise ValueError(f"d_pairs: needs a contiguous float64 device tensor of at least {n} x 8 on the handle's device")
+        if d_kept is not None:
+            _dev_index(d_kept, n, self._device, "d_kept")
+        kept = C.c_size_t(0)
+        check(lib().icp_gate_plane_pairs_device(self._h, C.c_void_p(d_src.data_ptr()), n, C.byref(transform.pose),
+                                                C.c_void_p(d_idx.data_ptr()), r, C.c_void_p(d_pairs.data_ptr()),
+                                                C.c_void_p(d_kept.data_ptr()) if d_kept is not None else None,
+                                                C.byref(kept)), "icp_gate_plane_pairs_device")
+        return int(kept.value)
 
     def profile_enable(self, every=1):
         """Time every `every`-th NN search launch with HIP events (0 / False: off)."""
@@ -822,13 +884,27 @@ class IcpMulti:
     def update_target_normals(self, k=8):
         check(lib().icp_multi_update_target_normals(self._h, int(k)), "icp_multi_update_target_normals")
 
-    def estimate_point_to_plane(self, src, initial_transform, max_iter, return_info=False):
-        """EXTENSION (icp_multi_estimate_point_to_plane): search sharded over the ranks, inner loop replicated"""
+    def estimate_point_to_plane(self, src, initial_transform, max_iter, return_info=False,
+                                max_correspondence_distance=None):
+        """EXTENSION (icp_multi_estimate_point_to_plane): search sharded over the ranks, inner loop replicated.
+        `max_correspondence_distance=r` (icp_multi_estimate_point_to_plane_gated): every rank gates the whole cloud
+        first; `return_info` then returns (T, idx, inner, inliers)"""
+        if max_correspondence_distance is not None:
+            r = float(max_correspondence_distance)
+            if not r >= 0.0:  # (also a NaN)
+                raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
         s = _host(src, 3)
         n = s.shape[0]
         o = Transform()
         idx = np.zeros(max(n, 1), dtype=np.uint32)
         inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        if max_correspondence_distance is not None:
+            inl = np.zeros(max(max_iter, 1), dtype=np.uint32)
+            check(lib().icp_multi_estimate_point_to_plane_gated(self._h, _ptr(s), n, C.byref(initial_transform.pose),
+                                                                max_iter, r, C.byref(o.pose), C.c_void_p(idx.ctypes.data),
+                                                                C.c_void_p(inner.ctypes.data), C.c_void_p(inl.ctypes.data)),
+                  "icp_multi_estimate_point_to_plane_gated")
+            return (o, idx[:n], inner[:max_iter], inl[:max_iter]) if return_info else o
         check(lib().icp_multi_estimate_point_to_plane(self._h, _ptr(s), n, C.byref(initial_transform.pose), max_iter,
                                                       C.byref(o.pose), C.c_void_p(idx.ctypes.data), C.c_void_p(inner.ctypes.data)),
               "icp_multi_estimate_point_to_plane")

@@ -408,6 +408,7 @@ void free_handle(icp_handle *h) {  // really release everything
   (void)hipFree(h->d_plane_pairs);
   (void)hipFree(h->d_plane_fa);
   (void)hipFree(h->d_plane_fb);
+  (void)hipFree(h->d_plane_stage);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }

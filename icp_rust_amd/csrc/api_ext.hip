@@ -223,8 +223,11 @@ extern "C" int icp_read_target_normals(icp_handle *h, size_t first, size_t count
   return ICP_OK;
 }
 
+namespace icp {
+namespace api {
+
 // the per-pair scratch of a point-to-plane inner loop
-static int ensure_plane_buffers(icp_handle *h, size_t n) {
+int ensure_plane_buffers(icp_handle *h, size_t n) {
   if (n > h->cap_plane) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     (void)hipFree(h->d_plane_pairs);
@@ -241,23 +244,30 @@ static int ensure_plane_buffers(icp_handle *h, size_t n) {
   return ICP_OK;
 }
 
-// One outer iteration's inner loop (src/lib.rs:59-84 around the plane residual) for given correspondences d_idx of the
-// WHOLE source cloud under pose T: the pose update dT and the updates applied.  (icp_multi_estimate_point_to_plane runs
-// this on every rank after the ranks have exchanged the indices of their slices.)
-int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
-                               icp_pose *dT, uint32_t *applied_out) {
-  if (!h || h->dim != 3 || !T || !dT || (n > 0 && (!d_src || !d_idx)) || h->normals_m != h->m || h->m == 0) return ICP_BAD_ARGUMENT;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n, false));
-  ICP_TRY_RC(ensure_plane_buffers(h, n));
+// ... and the staging buffer of its gate (gate_plane.hip: n pairs; only a gated call asks for it)
+int ensure_plane_stage(icp_handle *h, size_t n) {
+  if (n > h->cap_plane_stage) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->d_plane_stage);
+    h->d_plane_stage = nullptr;
+    h->cap_plane_stage = 0;
+    HIP_TRY(hipMalloc(&h->d_plane_stage, n * p2pl_pair_bytes()));
+    h->cap_plane_stage = n;
+  }
+  return ICP_OK;
+}
+
+// The inner loop (src/lib.rs:59-84 around the plane residual) on the k pairs in h->d_plane_pairs, whoever wrote them
+// (the gather of all correspondences, or the gate's survivors): the pose update dT and the updates applied.  Fewer than
+// two pairs: check_input_size -- the identity, no update.
+int p2pl_loop_on_pairs(icp_handle *h, size_t k, Pose *dT, uint32_t *applied_out) {
   Workspace &w = h->ws;
-  HIP_TRY(launch_p2pl_gather(h, d_src, n, *T, d_idx, h->d_normals, h->d_plane_pairs));
   Pose Ti = transform_identity();
   uint32_t applied = 0;
-  if (n >= 2) {
+  if (k >= 2) {
     double prev_error = DBL_MAX;
-    for (int k = 0; k < ICP_INNER_MAX_ITER; ++k) {
-      HIP_TRY(launch_p2pl_eval(h, h->d_plane_pairs, n, Ti, h->d_plane_fa, h->d_plane_fb));
+    for (int it = 0; it < ICP_INNER_MAX_ITER; ++it) {
+      HIP_TRY(launch_p2pl_eval(h, h->d_plane_pairs, k, Ti, h->d_plane_fa, h->d_plane_fb));
       HIP_TRY(hipStreamSynchronize(h->stream));
       const GnResult &r = *w.h_res;
       if (r.nan_flag) return ICP_NAN_INPUT;
@@ -273,6 +283,39 @@ int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, con
   *dT = Ti;
   if (applied_out) *applied_out = applied;
   return ICP_OK;
+}
+
+}  // namespace api
+}  // namespace icp
+
+// One outer iteration's inner loop for given correspondences d_idx of the WHOLE source cloud under pose T: make the
+// pairs (one gather), loop on them.  (icp_multi_estimate_point_to_plane runs this on every rank after the ranks have
+// exchanged the indices of their slices.)
+int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                               icp_pose *dT, uint32_t *applied_out) {
+  if (!h || h->dim != 3 || !T || !dT || (n > 0 && (!d_src || !d_idx)) || h->normals_m != h->m || h->m == 0) return ICP_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(ensure_workspace(h, n, false));
+  ICP_TRY_RC(ensure_plane_buffers(h, n));
+  HIP_TRY(launch_p2pl_gather(h, d_src, n, *T, d_idx, h->d_normals, h->d_plane_pairs));
+  return p2pl_loop_on_pairs(h, n, dT, applied_out);
+}
+
+// ... with a maximum correspondence distance (include/icp_mi355x.h section 12): the gate makes the pairs of the inliers
+// only (gate_plane.hip: two launches and the wait that brings their number), the loop runs on those.
+int icp_p2pl_gated_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                                     double max_dist, icp_pose *dT, uint32_t *applied_out, size_t *kept) {
+  if (!h || h->dim != 3 || !T || !dT || !kept || (n > 0 && (!d_src || !d_idx)) || !(max_dist >= 0.) ||
+      h->normals_m != h->m || h->m == 0)
+    return ICP_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, false));
+  ICP_TRY_RC(ensure_plane_buffers(h, n));
+  ICP_TRY_RC(ensure_plane_stage(h, n));
+  HIP_TRY(launch_gate_plane(h, d_src, n, *T, d_idx, max_dist * max_dist, h->d_plane_pairs, nullptr));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  *kept = gate_count(h);
+  return p2pl_loop_on_pairs(h, *kept, dT, applied_out);
 }
 
 extern "C" int icp_estimate_point_to_plane_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init,

@@ -65,8 +65,26 @@ int estimate_transform_on_pairs(icp_handle *h, const double *d_a, const double *
 hipError_t launch_gate(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
                        double *d_a, double *d_b, uint32_t *d_kept);
 size_t gate_count(const icp_handle *h);
+// ... of a point-to-plane registration (gate_plane.hip): the same compaction, fused with what k_p2pl_gather does -- the
+// survivors' PlanePairs (8 doubles each) in d_pairs, their source positions in d_kept (nullable); the count as above.
+// Needs ensure_workspace(max(n, 256)), ensure_plane_stage(n) and current normals.
+hipError_t launch_gate_plane(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
+                             void *d_pairs, uint32_t *d_kept);
+// the per-pair scratch of a point-to-plane inner loop, and the staging buffer of its gate (api_ext.hip)
+int ensure_plane_buffers(icp_handle *h, size_t n);
+int ensure_plane_stage(icp_handle *h, size_t n);
+// the inner loop (src/lib.rs:59-84 around the plane residual) on the k pairs in h->d_plane_pairs (api_ext.hip)
+int p2pl_loop_on_pairs(icp_handle *h, size_t k, Pose *dT, uint32_t *applied_out);
 
 }  // namespace api
+}  // namespace icp
+// One outer iteration's point-to-plane inner loop for given correspondences of the whole source cloud (api_ext.hip), and
+// the same on the inliers of a gate at max_dist (*kept: their number)
+int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                               icp_pose *dT, uint32_t *applied_out);
+int icp_p2pl_gated_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                                     double max_dist, icp_pose *dT, uint32_t *applied_out, size_t *kept);
+namespace icp {
 hipError_t launch_sel_init(icp_handle *h, size_t n);  // (gn.hip)
 hipError_t launch_stddevs(icp_handle *h, const double *d_a, const double *d_b, size_t n, const Pose &T);
 }  // namespace icp

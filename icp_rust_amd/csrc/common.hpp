@@ -440,6 +440,10 @@ struct icp_handle {
   void *d_plane_pairs = nullptr;  // per-pair constants of a point-to-plane inner loop
   double *d_plane_fa = nullptr, *d_plane_fb = nullptr;
   size_t cap_plane = 0;
+  // ... gated (gate_plane.hip): where a tile's surviving pairs wait for their final position; allocated by the first
+  // gated point-to-plane call, never by an ungated one
+  void *d_plane_stage = nullptr;
+  size_t cap_plane_stage = 0;
   // live kernel timing (icp_profile_*): event pairs around the NN search kernel
   int profile = 0;         // 0: off; k: event pairs around every k-th search launch
   unsigned prof_seen = 0;

@@ -34,6 +34,8 @@ extern "C" int icp_shard_loop_launch_device(icp_handle *h, const double *d_a, co
                                             int first_kind, int second_kind);
 extern "C" int icp_shard_loop_wait(icp_handle *h, icp_pose *Ti, double *prev_error, uint32_t *applied, int *it, int *finished,
                                    uint32_t *evals);
+int icp_p2pl_gated_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                                     double max_dist, icp_pose *dT, uint32_t *applied_out, size_t *kept);
 int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx, icp_pose *dT,
                                uint32_t *applied_out);
 int icp_shard_loop_launch_fused(icp_handle *const *hs, int world, const double *const *d_a, const double *const *d_b, size_t n_total,
@@ -710,9 +712,12 @@ extern "C" int icp_multi_update_target_normals(icp_multi *M, int k) {
   return ICP_OK;
 }
 
-extern "C" int icp_multi_estimate_point_to_plane(icp_multi *M, const double *src, size_t n, const icp_pose *init, size_t max_iter,
-                                                 icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters) {
-  if (!M || M->dim != 3 || !init || !out || (n > 0 && !src) || n >= 0xffffffffull) return ICP_BAD_ARGUMENT;
+// the body of icp_multi_estimate_point_to_plane and of its gated sibling (section 12; gated: every rank gates the whole
+// cloud at max_dist before its inner loop, and the ranks must agree on the kept count too)
+static int multi_estimate_p2pl(icp_multi *M, const double *src, size_t n, const icp_pose *init, size_t max_iter, bool gated,
+                               double max_dist, icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters,
+                               uint32_t *inliers) {
+  if (M->dim != 3) return ICP_BAD_ARGUMENT;
   const int W = M->world;
   if (M->m == 0) {
     if (n > 0 && max_iter > 0) return ICP_EMPTY_DST;
@@ -769,19 +774,26 @@ extern "C" int icp_multi_estimate_point_to_plane(icp_multi *M, const double *src
     }
     Pose Ti0 = transform_identity();
     uint32_t ap0 = 0;
+    size_t kept0 = n;
     for (int q = 0; q < W; ++q) {  // the same inner loop on every rank
       auto &R = M->r[q];
       Pose Ti;
       uint32_t ap = 0;
-      ICP_TRY(icp_p2pl_inner_loop_device(R.h, R.d_p_src, n, &T, R.d_p_idx, &Ti, &ap));
+      size_t kept = n;
+      if (gated)
+        ICP_TRY(icp_p2pl_gated_inner_loop_device(R.h, R.d_p_src, n, &T, R.d_p_idx, max_dist, &Ti, &ap, &kept));
+      else
+        ICP_TRY(icp_p2pl_inner_loop_device(R.h, R.d_p_src, n, &T, R.d_p_idx, &Ti, &ap));
       if (q == 0) {
         Ti0 = Ti;
         ap0 = ap;
-      } else if (memcmp(&Ti, &Ti0, sizeof(Pose)) != 0 || ap != ap0) {
+        kept0 = kept;
+      } else if (memcmp(&Ti, &Ti0, sizeof(Pose)) != 0 || ap != ap0 || kept != kept0) {
         MULTI_FAIL("the ranks finished a point-to-plane inner loop differently");
       }
     }
     if (inner_iters) inner_iters[it] = ap0;
+    if (inliers) inliers[it] = (uint32_t)kept0;
     T = transform_mul(Ti0, T);
   }
   if (last_idx && max_iter > 0 && n > 0) {
@@ -791,4 +803,21 @@ extern "C" int icp_multi_estimate_point_to_plane(icp_multi *M, const double *src
   }
   *out = T;
   return ICP_OK;
+}
+
+extern "C" int icp_multi_estimate_point_to_plane(icp_multi *M, const double *src, size_t n, const icp_pose *init, size_t max_iter,
+                                                 icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters) {
+  if (!M || M->dim != 3 || !init || !out || (n > 0 && !src) || n >= 0xffffffffull) return ICP_BAD_ARGUMENT;
+  return multi_estimate_p2pl(M, src, n, init, max_iter, false, 0., out, last_idx, inner_iters, nullptr);
+}
+
+// (section 12) the arguments are decided first, the device next, the object is read only then
+extern "C" int icp_multi_estimate_point_to_plane_gated(icp_multi *M, const double *src, size_t n, const icp_pose *init,
+                                                       size_t max_iter, double max_dist, icp_pose *out, uint32_t *last_idx,
+                                                       uint32_t *inner_iters, uint32_t *inliers) {
+  // (max_dist >= 0 is false for a NaN)
+  if (!M || !init || !out || (n > 0 && !src) || !(max_dist >= 0.) || n >= 0xffffffffull) return ICP_BAD_ARGUMENT;
+  int devices = 0;
+  if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return ICP_NO_DEVICE;
+  return multi_estimate_p2pl(M, src, n, init, max_iter, true, max_dist, out, last_idx, inner_iters, inliers);
 }

@@ -16,6 +16,7 @@
 //   Huber error            = sum rho(r^2).
 #include "common.hpp"
 #include "gn_device.hpp"
+#include "p2plane_device.hpp"
 
 namespace icp {
 hipError_t launch_sel_init(icp_handle *h, size_t n);
@@ -159,13 +160,7 @@ __global__ __launch_bounds__(64) void k_target_normals(const double *__restrict_
   normals[(size_t)i * 3 + 2] = nrm[2];
 }
 
-// per pair: everything the inner loop needs that does not change with the inner pose
-struct PlanePair {
-  double ax, ay;        // xy(T_outer p)
-  double qx, qy, dz;    // matched target xy, p_z - q_z
-  double nx, ny, nz;    // its normal
-};
-
+// (PlanePair, the per-pair constants of an inner loop, and plane_residual: p2plane_device.hpp)
 __global__ void k_p2pl_gather(const double *__restrict__ src, unsigned n, Pose T, const uint32_t *__restrict__ idx,
                               const double *__restrict__ dst, const double *__restrict__ normals,
                               PlanePair *__restrict__ out) {
@@ -183,12 +178,6 @@ __global__ void k_p2pl_gather(const double *__restrict__ src, unsigned n, Pose T
   o.ny = normals[(size_t)j * 3 + 1];
   o.nz = normals[(size_t)j * 3 + 2];
   out[i] = o;
-}
-
-__device__ __forceinline__ double plane_residual(const PlanePair &p, const Pose &T) {
-  const double rx = ((T.r00 * p.ax + T.r01 * p.ay) + T.tx) - p.qx;
-  const double ry = ((T.r10 * p.ax + T.r11 * p.ay) + T.ty) - p.qy;
-  return (p.nx * rx + p.ny * ry) + p.nz * p.dz;
 }
 
 // residuals as the pairs ((r, 0), (0, 0)): launch_stddevs under the identity pose then selects the

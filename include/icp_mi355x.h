@@ -62,7 +62,8 @@ extern "C" {
  * icp_mi355x_debug.h).  Everything of version 7 is unchanged.  Section 9 (icp_quality, icp_evaluate*,
  * icp_batch_evaluate*; icp_batch_evaluate_counters in icp_mi355x_debug.h) was added later without a bump: an addition
  * detectable by symbol; so was section 10 (icp_estimate_gated*, icp_gate_pairs_device); so was section 11
- * (icp_crop_targets, icp_multi_crop_targets; icp_grid_crop_counters in icp_mi355x_debug.h) */
+ * (icp_crop_targets, icp_multi_crop_targets; icp_grid_crop_counters in icp_mi355x_debug.h); so was section 12
+ * (icp_estimate_point_to_plane_gated*, icp_gate_plane_pairs_device, icp_multi_estimate_point_to_plane_gated) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -675,6 +676,55 @@ int icp_gate_pairs_device(icp_handle *h, const double *d_src, size_t n, const ic
  * replicas different and the object unusable, as for icp_multi_append_targets. */
 int icp_crop_targets(icp_handle *h, const double center_xy[2], double radius, uint32_t *new_index, size_t *removed);
 int icp_multi_crop_targets(icp_multi *M, const double center_xy[2], double radius, size_t *removed);
+
+/* ================================================================================
+ * 12. EXTENSION (not in the reference): point-to-plane registration with a maximum correspondence distance
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 10's gate for section 7's estimator:
+ * the point-to-plane inner loop sees the INLIERS of each outer iteration only.  A frame registered against a growing
+ * map always holds surface the map does not; without the gate every such point pulls on the pose through the plane of
+ * whatever target happens to be nearest.  No parity claim; DESIGN.md section 9g restates the definition.
+ *
+ * icp_estimate_point_to_plane_gated[_device] runs the outer loop of icp_estimate_point_to_plane_device.  For outer
+ * iteration `it` at pose T: the exact 3-D search at T; then for every source point i with match j
+ *   qx = (r00 px + r01 py) + tx, qy = (r10 px + r11 py) + ty, ex = qx - dst[j].x, ey = qy - dst[j].y,
+ *   dz = pz - dst[j].z, d2 = ((ex ex + ey ey) + dz dz)                  (no FMA: d2 exactly as sections 9 / 10 define it)
+ *   inlier = d2 <= max_dist * max_dist (in f64; a NaN d2 is never an inlier);
+ * section 7's inner loop on the pairs of the inliers, IN THE CALLER'S ORDER WITH THE OTHERS REMOVED (the point-to-plane
+ * path has no snapshot order); T = dT * T.  The sums of an evaluation are folded in the tree of
+ * icp_reduce_geometry(number of inliers).
+ *   fewer than two inliers: the iteration applies no update (as n < 2 does in section 7), inner_iters[it] = 0;
+ *   inliers[it] (nullable, max_iter words): the number of inliers of iteration `it`;
+ *   last_idx / d_last_idx (nullable): the correspondences of ALL n points at the last iteration, caller order;
+ *   there is no fixed-point exit, as icp_estimate_point_to_plane has none: every iteration runs.
+ * Statuses, decided in this order: ICP_BAD_ARGUMENT (a required pointer NULL, max_dist NaN or negative, n >= 2^32 - 1:
+ * before any device use and before the handle is read; +inf and 0.0 are valid bounds); ICP_NO_DEVICE; then the handle:
+ * ICP_BAD_ARGUMENT (not a 3-D handle; normals not current), ICP_EMPTY_DST (no targets, when a search would run);
+ * ICP_NAN_INPUT (an inlier pair with a NaN residual); n == 0 and max_iter == 0 behave as in section 7.
+ * Consequence: for inputs without a NaN d2, max_dist = +inf returns the pose, the indices and the inner counts of
+ * icp_estimate_point_to_plane[_device], bit for bit (same pairs, same order, same n: the same reduction geometry), and
+ * inliers[it] == n.
+ *
+ * icp_gate_plane_pairs_device: the gate alone, in the style of section 4 (device buffers; synchronises the stream).
+ * From the source cloud, a pose and the indices of a search at that pose it writes, for the k-th inlier i_k in the order
+ * of d_src, the eight doubles the inner loop reads: d_pairs[8 k ..] = ax, ay (xy(T src[i_k])), qx, qy (xy of its match),
+ * dz (src z - match z), nx, ny, nz (the match's normal); d_kept[k] = i_k (nullable); *kept = their number.  d_pairs
+ * holds 8 n doubles, d_kept n words.  n == 0: ICP_OK, *kept = 0, nothing else is looked at.
+ *
+ * icp_multi_estimate_point_to_plane_gated: icp_multi_estimate_point_to_plane with the gate -- the search is sharded,
+ * every rank gates the whole cloud and runs the inner loop on its survivors; the ranks must agree on pose, applied
+ * count and kept count.  Result: one handle's icp_estimate_point_to_plane_gated, bit for bit. */
+int icp_estimate_point_to_plane_gated(icp_handle *h, const double *src, size_t n, const icp_pose *init, size_t max_iter,
+                                      double max_dist, icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters,
+                                      uint32_t *inliers);
+int icp_estimate_point_to_plane_gated_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init,
+                                             size_t max_iter, double max_dist, icp_pose *out, uint32_t *d_last_idx,
+                                             uint32_t *inner_iters, uint32_t *inliers);
+int icp_gate_plane_pairs_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
+                                double max_dist, double *d_pairs, uint32_t *d_kept, size_t *kept);
+int icp_multi_estimate_point_to_plane_gated(icp_multi *M, const double *src, size_t n, const icp_pose *init,
+                                            size_t max_iter, double max_dist, icp_pose *out, uint32_t *last_idx,
+                                            uint32_t *inner_iters, uint32_t *inliers);
 
 #ifdef __cplusplus
 }
