@@ -41,6 +41,16 @@ class QualityStruct(C.Structure):
                 ("information", C.c_double * 9)]
 
 
+class PlaneQualityStruct(C.Structure):
+    """`icp_plane_quality` (include/icp_mi355x.h section 13): the quality of a pose under the point-to-plane residual;
+    icp_rust_amd.PlaneQuality wraps it."""
+
+    _fields_ = [("n", C.c_uint64), ("inliers", C.c_uint64), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("inlier_sum_d2", C.c_double), ("plane_rmse", C.c_double), ("plane_sum_r2", C.c_double),
+                ("error", C.c_double), ("huber_error", C.c_double), ("information", C.c_double * 9),
+                ("translation_eig", C.c_double * 2)]
+
+
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)]
@@ -207,6 +217,8 @@ SIGNATURES = {
     "icp_crop_targets": (C.c_int, [_vp, _dp, C.c_double, _vp, C.POINTER(_sz)]),
     "icp_multi_crop_targets": (C.c_int, [_vp, _dp, C.c_double, C.POINTER(_sz)]),
     "icp_grid_crop_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_evaluate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
+    "icp_evaluate_point_to_plane_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
 }
 
 _lib = None

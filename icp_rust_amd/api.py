@@ -350,6 +350,44 @@ class Quality:
                 f"inlier_rmse={self.inlier_rmse:.6g}, error={self.error:.6g}, huber_error={self.huber_error:.6g})")
 
 
+class PlaneQuality:
+    """The quality of a pose under the point-to-plane residual (`icp_plane_quality`, include/icp_mi355x.h section 13) --
+    an extension beyond the reference.  n, inliers, fitness, inlier_rmse and inlier_sum_d2 as in Quality (same bits at
+    the same pose and bound); plane_rmse and plane_sum_r2 of the inliers' squared plane residuals; error and
+    huber_error, the folds of p2 and rho(p2) over all points; information, the 3 x 3 SE(2) information matrix the plane
+    residual gives on the inlier pairs in (x, y, theta), rank-deficient where the scene is; translation_eig, the
+    eigenvalues (lmin, lmax) of its 2 x 2 translation block."""
+
+    __slots__ = ("n", "inliers", "fitness", "inlier_rmse", "inlier_sum_d2", "plane_rmse", "plane_sum_r2", "error",
+                 "huber_error", "information", "translation_eig")
+
+    def __init__(self, q):
+        self.n, self.inliers = int(q.n), int(q.inliers)
+        self.fitness, self.inlier_rmse, self.inlier_sum_d2 = q.fitness, q.inlier_rmse, q.inlier_sum_d2
+        self.plane_rmse, self.plane_sum_r2 = q.plane_rmse, q.plane_sum_r2
+        self.error, self.huber_error = q.error, q.huber_error
+        self.information = np.array(q.information[:], dtype=np.float64).reshape(3, 3)
+        self.translation_eig = np.array(q.translation_eig[:], dtype=np.float64)
+
+    def as_array(self):
+        """the float fields in struct order (fitness, inlier_rmse, inlier_sum_d2, plane_rmse, plane_sum_r2, error,
+        huber_error, information row-major, translation_eig): what a bit-for-bit comparison compares, next to n and
+        inliers"""
+        return np.array([self.fitness, self.inlier_rmse, self.inlier_sum_d2, self.plane_rmse, self.plane_sum_r2,
+                         self.error, self.huber_error, *self.information.ravel(), *self.translation_eig])
+
+    def weak_direction(self):
+        """the unit vector of the xy plane along which the translation is observed least: the eigenvector of lmin of the
+        2 x 2 translation block (numpy.linalg.eigh; a convenience, no bit claim)"""
+        _, vecs = np.linalg.eigh(self.information[:2, :2])
+        return vecs[:, 0]
+
+    def __repr__(self):
+        return (f"PlaneQuality(n={self.n}, inliers={self.inliers}, fitness={self.fitness:.6g}, "
+                f"inlier_rmse={self.inlier_rmse:.6g}, plane_rmse={self.plane_rmse:.6g}, "
+                f"translation_eig=({self.translation_eig[0]:.6g}, {self.translation_eig[1]:.6g}))")
+
+
 class _Icp:
     DIM = 0
 
@@ -766,6 +804,36 @@ class _Icp:
                                                       C.c_void_p(inner.ctypes.data), C.c_void_p(inl.ctypes.data)),
               "icp_estimate_point_to_plane_gated")
         return (o, idx[:n], inner[:max_iter], inl[:max_iter]) if return_info else o
+
+    # -- EXTENSION (not in the reference): the quality of a pose under the plane residual, section 13 --
+    def evaluate_point_to_plane(self, src, transform, max_correspondence_distance=float("inf"), return_indices=False):
+        """The PlaneQuality of `transform` (icp_evaluate_point_to_plane[_device]; 3-D handles, needs current normals):
+        the handle's exact correspondences at that pose, the inliers within max_correspondence_distance, the plane
+        residual's RMSE, error / huber_error and the SE(2) information matrix it gives.  The handle's registration
+        state is left as it was.  return_indices=True also returns the correspondences (caller order).  numpy arrays or
+        contiguous float64 CUDA tensors (used in place)."""
+        if self.DIM != 3:
+            raise ValueError("evaluate_point_to_plane needs a 3-D handle (Icp3d): a 2-D cloud has no normals")
+        q = _lib.PlaneQualityStruct()
+        r = float(max_correspondence_distance)
+        if _is_device_tensor(src):
+            import torch
+
+            self._dev(src, "src")
+            n = src.shape[0]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_indices else None
+            check(lib().icp_evaluate_point_to_plane_device(self._h, C.c_void_p(src.data_ptr()), n,
+                                                           C.byref(transform.pose), r, C.byref(q),
+                                                           C.c_void_p(idx.data_ptr()) if return_indices else None),
+                  "icp_evaluate_point_to_plane_device")
+            return (PlaneQuality(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else PlaneQuality(q)
+        s = _host(src, self.DIM)
+        n = s.shape[0]
+        idx = np.zeros(max(n, 1), dtype=np.uint32) if return_indices else None
+        check(lib().icp_evaluate_point_to_plane(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
+                                                C.c_void_p(idx.ctypes.data) if return_indices else None),
+              "icp_evaluate_point_to_plane")
+        return (PlaneQuality(q), idx[:n]) if return_indices else PlaneQuality(q)
 
     def gate_plane_pairs_device(self, d_src, transform, d_idx, r, d_pairs, d_kept=None):
         """The gate of a gated point-to-plane registration alone (icp_gate_plane_pairs_device): for the inliers of the

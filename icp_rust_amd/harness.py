@@ -114,7 +114,8 @@ def run_scan3d(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, p
 
 
 def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, max_frames=None,
-                    point_to_plane=None, max_correspondence_distance=None, map_radius=None):
+                    point_to_plane=None, max_correspondence_distance=None, map_radius=None, quality_distance=None,
+                    qualities=None):
     """EXTENSION, not in the reference (BASELINE.json configs[4]): the
     scan3d frames registered against a map that grows.  The map starts as frame 0 (filtered as
     examples/scan3d.rs:63-69 does); every later frame is registered against the whole map with
@@ -132,6 +133,11 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
     `map_radius=R` (either residual): a sliding-window map -- after every frame's append (and its update_normals) the
     map is cropped to the xy disc of radius R around the registered position, world.crop(transform.t, R)
     (include/icp_mi355x.h section 11); None calls nothing, so the map grows as before.
+    `qualities=[]` (either residual): the quality of every frame's pose against the map it was registered to is
+    appended to the list, after the frame's estimate and before its append -- with point_to_plane set,
+    world.evaluate_point_to_plane(scan, transform, quality_distance or inf) (a PlaneQuality, include/icp_mi355x.h
+    section 13), otherwise world.evaluate(scan, transform, quality_distance or inf) (a Quality, section 9).  None calls
+    nothing.
     Returns (transforms, path_xy, map_handle)."""
     if point_to_plane and max_correspondence_distance is not None:
         raise ValueError("max_correspondence_distance applies to the point-to-point registration only")
@@ -153,6 +159,12 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
                                        max_correspondence_distance=max_correspondence_distance)
         else:
             transform = world.estimate(scan, transform, max_iter)
+        if qualities is not None:
+            bound = quality_distance or float("inf")
+            if point_to_plane:
+                qualities.append(world.evaluate_point_to_plane(scan, transform, bound))
+            else:
+                qualities.append(world.evaluate(scan, transform, bound))
         world.append(scan, transform)
         if point_to_plane:
             world.update_normals(point_to_plane)

@@ -63,7 +63,8 @@ extern "C" {
  * icp_batch_evaluate*; icp_batch_evaluate_counters in icp_mi355x_debug.h) was added later without a bump: an addition
  * detectable by symbol; so was section 10 (icp_estimate_gated*, icp_gate_pairs_device); so was section 11
  * (icp_crop_targets, icp_multi_crop_targets; icp_grid_crop_counters in icp_mi355x_debug.h); so was section 12
- * (icp_estimate_point_to_plane_gated*, icp_gate_plane_pairs_device, icp_multi_estimate_point_to_plane_gated) */
+ * (icp_estimate_point_to_plane_gated*, icp_gate_plane_pairs_device, icp_multi_estimate_point_to_plane_gated); so was
+ * section 13 (icp_plane_quality, icp_evaluate_point_to_plane*) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -725,6 +726,67 @@ int icp_gate_plane_pairs_device(icp_handle *h, const double *d_src, size_t n, co
 int icp_multi_estimate_point_to_plane_gated(icp_multi *M, const double *src, size_t n, const icp_pose *init,
                                             size_t max_iter, double max_dist, icp_pose *out, uint32_t *last_idx,
                                             uint32_t *inner_iters, uint32_t *inliers);
+
+/* ================================================================================
+ * 13. EXTENSION (not in the reference): the quality of a pose under the point-to-plane residual
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 9 scores a pose by the point-to-point
+ * residual: its information matrix has the translation block c * I whatever the scene looks like.  A pose registered
+ * with plane residuals (sections 7, 12) is observed only along the normals of the surfaces it was matched to -- in a
+ * corridor it slides freely along the axis -- and a filter or a pose graph needs the information that residual
+ * actually gives.  This section scores a pose for a 3-D handle with current normals: the fitness, the plane-residual
+ * RMSE and the unweighted jtj of section 7's accumulation at the pose, rank-deficient exactly where the scene is.
+ * The reference has no such thing: no parity claim; DESIGN.md section 9h restates the definition.
+ *
+ * For a handle with targets dst (m points) and their normals nrm, a source cloud src (n points, caller order), a pose
+ * T and max_dist r (r >= 0, or +inf), for every source point p (no FMA anywhere):
+ *   qx = (r00 px + r01 py) + tx, qy = (r10 px + r11 py) + ty               (transform_xy)
+ *   j  = the handle's exact 3-D nearest neighbour of (qx, qy, pz); b = dst[j], (nx, ny, nz) = nrm[j]
+ *   ex = qx - bx, ey = qy - by, dz = pz - bz
+ *   d2 = ((ex ex + ey ey) + dz dz)                                         (section 9's d2)
+ *   inlier = d2 <= r * r (r * r in f64; a NaN d2 is never an inlier)
+ *   rp = (nx ex + ny ey) + nz dz                (section 7's plane residual at the identity inner pose)
+ *   p2 = rp rp
+ *   c  = (nx * (-qy)) + (ny * qx)               (the third entry of section 7's Jacobian row (nx, ny, c) at identity)
+ * Ten sums, each by section 9's fold over the n values in caller order (n == 1: the one value); a point that is not an
+ * inlier adds +0.0 to the inlier-only sums:
+ *   S_d2 = fold(inlier ? d2)     S_p2 = fold(inlier ? p2)     E = fold(p2)     H = fold(rho(p2))  (huber.rs)
+ *   Ixx = fold(inlier ? nx nx)   Ixy = fold(inlier ? nx ny)   Iyy = fold(inlier ? ny ny)
+ *   Ixt = fold(inlier ? nx c)    Iyt = fold(inlier ? ny c)    Itt = fold(inlier ? c c)
+ *   inliers        the count (exact)                  fitness      inliers / n
+ *   inlier_sum_d2  S_d2                               inlier_rmse  sqrt(S_d2 / inliers) (0 without inliers): the bits
+ *                                                                  icp_evaluate gives at the same T and r
+ *   plane_sum_r2   S_p2                               plane_rmse   sqrt(S_p2 / inliers) (0 without inliers)
+ *   error          E                                  huber_error  H (what section 7's evaluation reports as its error)
+ *   information    row-major [[Ixx, Ixy, Ixt], [Ixy, Iyy, Iyt], [Ixt, Iyt, Itt]]: the SE(2) Hessian in (x, y, theta) of
+ *                  the plane residual on the inlier pairs, unweighted
+ *   translation_eig  the eigenvalues lmin, lmax of [[Ixx, Ixy], [Ixy, Iyy]], on the host with + - * sqrt only:
+ *                  h = (Ixx + Iyy) * 0.5, g = (Ixx - Iyy) * 0.5, s = sqrt(g g + Ixy Ixy), lmin = h - s, lmax = h + s.
+ *                  Only the translation block gets eigenvalues: its units are consistent; the 3 x 3 matrix mixes metres
+ *                  and radians and is left to the caller.
+ * Statuses, decided in this order: ICP_BAD_ARGUMENT (h, T or out NULL; src NULL with n > 0; r NaN or negative;
+ * n >= 2^32 - 1: before any device use and before the handle is read); n == 0 -> ICP_OK and zeros; ICP_NO_DEVICE; then
+ * the handle: ICP_BAD_ARGUMENT (not a 3-D handle; normals not current), ICP_EMPTY_DST (no targets); ICP_NAN_INPUT (some
+ * p2 is NaN).  *out is the result when the call returns ICP_OK; otherwise it holds n and zeros.
+ * idx / d_idx (nullable): the n correspondences at T, caller order.  The handle's registration state is not touched:
+ * an estimate after an evaluation gives the bits it gives without one. */
+typedef struct icp_plane_quality {
+  uint64_t n;                 /* source points                                          */
+  uint64_t inliers;           /* points with d2 <= max_dist^2                           */
+  double fitness;             /* inliers / n                                            */
+  double inlier_rmse;         /* sqrt(inlier_sum_d2 / inliers): section 9's             */
+  double inlier_sum_d2;       /* fold of the inliers' squared distances                 */
+  double plane_rmse;          /* sqrt(plane_sum_r2 / inliers), 0 without inliers        */
+  double plane_sum_r2;        /* fold of the inliers' squared plane residuals           */
+  double error;               /* fold of p2 over all points                             */
+  double huber_error;         /* fold of rho(p2) over all points                        */
+  double information[9];      /* row-major SE(2) information of the inlier pairs        */
+  double translation_eig[2];  /* lmin, lmax of the 2 x 2 translation block              */
+} icp_plane_quality;
+int icp_evaluate_point_to_plane(icp_handle *h, const double *src, size_t n, const icp_pose *T, double max_dist,
+                                icp_plane_quality *out, uint32_t *idx);
+int icp_evaluate_point_to_plane_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, double max_dist,
+                                       icp_plane_quality *out, uint32_t *d_idx);
 
 #ifdef __cplusplus
 }
