@@ -309,7 +309,7 @@ int icp_p2pl_gated_inner_loop_device(icp_handle *h, const double *d_src, size_t 
       h->normals_m != h->m || h->m == 0)
     return ICP_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   ICP_TRY_RC(ensure_plane_buffers(h, n));
   ICP_TRY_RC(ensure_plane_stage(h, n));
   HIP_TRY(launch_gate_plane(h, d_src, n, *T, d_idx, max_dist * max_dist, h->d_plane_pairs, nullptr));
@@ -337,14 +337,7 @@ extern "C" int icp_estimate_point_to_plane_device(icp_handle *h, const double *d
     const int prc = icp_prepare_source_device(h, d_src, n, init);
     if (prc != ICP_OK) return prc;
   }
-  struct Quiesce {
-    icp_handle *h;
-    ~Quiesce() {
-      (void)hipStreamSynchronize(h->stream);
-      h->qsort.valid = false;
-      h->qsort.have_prev = false;
-    }
-  } quiesce_on_exit{h};
+  Quiesce quiesce_on_exit{h};
   for (size_t it = 0; it < max_iter; ++it) {
     uint32_t *idx = (it + 1 == max_iter && d_last_idx) ? d_last_idx : w.d_idx;
     int rc = icp_correspond_device(h, d_src, n, &T, nullptr, nullptr, idx);  // exact 3-D NN, src/lib.rs:161-167

@@ -13,31 +13,12 @@ using namespace icp::api;
 
 namespace {
 
-// (max_dist >= 0 is false for a NaN)
-bool gated_args_ok(const icp_handle *h, const void *src, size_t n, const icp_pose *init, double max_dist,
-                   const icp_pose *out) {
-  return h && init && out && (n == 0 || src) && max_dist >= 0. && n < 0xffffffffull;
-}
-
-bool have_device() {
-  int count = 0;
-  return hipGetDeviceCount(&count) == hipSuccess && count > 0;
-}
-
 int estimate_gated(icp_handle *h, const double *d_src, size_t n, const Pose &init, size_t max_iter, double max_dist,
                    Pose *out, uint32_t *d_last_idx, uint32_t *inner_iters, uint32_t *inliers) {
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   // Whatever way this call ends, nothing of it is in flight afterwards and its search snapshot is dropped
   // (icp_estimate_device's discipline: the snapshot is keyed on a buffer the caller may now rewrite).
-  struct Quiesce {
-    icp_handle *h;
-    ~Quiesce() {
-      (void)hipStreamSynchronize(h->stream);
-      h->qsort.valid = false;
-      h->qsort.have_prev = false;
-      h->qsort.slot_order = false;
-    }
-  } quiesce_on_exit{h};
+  Quiesce quiesce_on_exit{h};
   Workspace &w = h->ws;
   h->qsort.fold_n = 0;  // (identity, until this call takes a snapshot)
   Pose T = init;
@@ -85,7 +66,7 @@ int estimate_gated(icp_handle *h, const double *d_src, size_t n, const Pose &ini
 extern "C" int icp_estimate_gated_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init,
                                          size_t max_iter, double max_dist, icp_pose *out, uint32_t *d_last_idx,
                                          uint32_t *inner_iters, uint32_t *inliers) {
-  if (!gated_args_ok(h, d_src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, d_src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
   if (!have_device()) return ICP_NO_DEVICE;
   HIP_TRY(hipSetDevice(h->device));
   return estimate_gated(h, d_src, n, *init, max_iter, max_dist, out, d_last_idx, inner_iters, inliers);
@@ -94,10 +75,10 @@ extern "C" int icp_estimate_gated_device(icp_handle *h, const double *d_src, siz
 extern "C" int icp_estimate_gated(icp_handle *h, const double *src, size_t n, const icp_pose *init, size_t max_iter,
                                   double max_dist, icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters,
                                   uint32_t *inliers) {
-  if (!gated_args_ok(h, src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
   if (!have_device()) return ICP_NO_DEVICE;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, true));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), true));
   if (n > 0)
     HIP_TRY(hipMemcpyAsync(h->ws.d_src, src, n * h->dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
   ICP_TRY_RC(estimate_gated(h, h->ws.d_src, n, *init, max_iter, max_dist, out, last_idx ? h->ws.d_idx : nullptr,

@@ -11,17 +11,6 @@ using namespace icp::api;
 
 namespace {
 
-// (max_dist >= 0 is false for a NaN)
-bool gated_plane_args_ok(const icp_handle *h, const void *src, size_t n, const icp_pose *init, double max_dist,
-                         const icp_pose *out) {
-  return h && init && out && (n == 0 || src) && max_dist >= 0. && n < 0xffffffffull;
-}
-
-bool have_device() {
-  int count = 0;
-  return hipGetDeviceCount(&count) == hipSuccess && count > 0;
-}
-
 // what icp_estimate_point_to_plane_device decides on the handle, in its order; *done: nothing to run, *out is set
 int gated_plane_handle_ok(const icp_handle *h, size_t n, const icp_pose *init, size_t max_iter, icp_pose *out, bool *done) {
   *done = false;
@@ -38,20 +27,13 @@ int gated_plane_handle_ok(const icp_handle *h, size_t n, const icp_pose *init, s
 
 int estimate_plane_gated(icp_handle *h, const double *d_src, size_t n, const Pose &init, size_t max_iter, double max_dist,
                          Pose *out, uint32_t *d_last_idx, uint32_t *inner_iters, uint32_t *inliers) {
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   ICP_TRY_RC(ensure_plane_buffers(h, n));
   ICP_TRY_RC(ensure_plane_stage(h, n));
   Workspace &w = h->ws;
   Pose T = init;
   if (max_iter > 0) ICP_TRY_RC(icp_prepare_source_device(h, d_src, n, &init));
-  struct Quiesce {
-    icp_handle *h;
-    ~Quiesce() {
-      (void)hipStreamSynchronize(h->stream);
-      h->qsort.valid = false;
-      h->qsort.have_prev = false;
-    }
-  } quiesce_on_exit{h};
+  Quiesce quiesce_on_exit{h};
   for (size_t it = 0; it < max_iter; ++it) {
     uint32_t *idx = (it + 1 == max_iter && d_last_idx) ? d_last_idx : w.d_idx;
     ICP_TRY_RC(icp_correspond_device(h, d_src, n, &T, nullptr, nullptr, idx));  // exact 3-D NN, src/lib.rs:161-167
@@ -73,7 +55,7 @@ int estimate_plane_gated(icp_handle *h, const double *d_src, size_t n, const Pos
 extern "C" int icp_estimate_point_to_plane_gated_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init,
                                                         size_t max_iter, double max_dist, icp_pose *out,
                                                         uint32_t *d_last_idx, uint32_t *inner_iters, uint32_t *inliers) {
-  if (!gated_plane_args_ok(h, d_src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, d_src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
   if (!have_device()) return ICP_NO_DEVICE;
   bool done;
   ICP_TRY_RC(gated_plane_handle_ok(h, n, init, max_iter, out, &done));
@@ -85,13 +67,13 @@ extern "C" int icp_estimate_point_to_plane_gated_device(icp_handle *h, const dou
 extern "C" int icp_estimate_point_to_plane_gated(icp_handle *h, const double *src, size_t n, const icp_pose *init,
                                                  size_t max_iter, double max_dist, icp_pose *out, uint32_t *last_idx,
                                                  uint32_t *inner_iters, uint32_t *inliers) {
-  if (!gated_plane_args_ok(h, src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, src, n, init, max_dist, out)) return ICP_BAD_ARGUMENT;
   if (!have_device()) return ICP_NO_DEVICE;
   bool done;
   ICP_TRY_RC(gated_plane_handle_ok(h, n, init, max_iter, out, &done));
   if (done) return ICP_OK;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, true));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), true));
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->ws.d_src, src, n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   uint32_t *d_li = nullptr;
   if (last_idx && n > 0) HIP_TRY(hipMalloc(&d_li, n * sizeof(uint32_t)));
@@ -116,7 +98,7 @@ extern "C" int icp_gate_plane_pairs_device(icp_handle *h, const double *d_src, s
   if (h->m == 0) return ICP_EMPTY_DST;
   if (h->normals_m != h->m) return ICP_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   ICP_TRY_RC(ensure_plane_stage(h, n));
   HIP_TRY(launch_gate_plane(h, d_src, n, *T, d_idx, max_dist * max_dist, d_pairs, d_kept));
   HIP_TRY(hipStreamSynchronize(h->stream));

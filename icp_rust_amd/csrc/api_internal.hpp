@@ -34,6 +34,35 @@ int wgn_step(icp_handle *h, const double *d_a, const double *d_b, size_t n, cons
 int resolved_nn_mode(const icp_handle *h);
 // check_input_size, src/lib.rs:186-189
 inline bool input_size_ok(size_t n) { return n > 0 && n >= 2; }
+
+// ---- what the entries of the extensions share (each entry keeps its own ORDER of decisions: tests/test_*_abi.py) ----
+// is there a device to run on (ICP_NO_DEVICE otherwise)
+inline bool have_device() {
+  int count = 0;
+  return hipGetDeviceCount(&count) == hipSuccess && count > 0;
+}
+// the arguments of an entry that takes a cloud of n points, a pose and a distance (max_dist >= 0 is false for a NaN)
+inline bool sized_args_ok(const icp_handle *h, const void *src, size_t n, const icp_pose *pose, double max_dist,
+                          const void *out) {
+  return h && pose && out && (n == 0 || src) && max_dist >= 0. && n < 0xffffffffull;
+}
+// points to ask ensure_workspace for: the scratch of a gate or an evaluation (tile counts, level records) lives in the
+// per-point buffers and needs 256 points' worth even for the smallest cloud
+inline size_t workspace_points(size_t n) { return n < 256 ? 256 : n; }
+// Whatever way the call that holds it ends, nothing of it is in flight on h->stream afterwards, and the search snapshot
+// it may have taken (the cell-sorted copy, keyed on a buffer the caller may now rewrite) is dropped, as
+// icp_estimate_device drops its own.  slot_order is cleared for icp_estimate_gated_device, the one holder that sets it;
+// for the others it is already false: only that entry and icp_estimate_device set it, each behind its guard, which
+// clears it on every exit.
+struct Quiesce {
+  icp_handle *h;
+  ~Quiesce() {
+    (void)hipStreamSynchronize(h->stream);
+    h->qsort.valid = false;
+    h->qsort.have_prev = false;
+    h->qsort.slot_order = false;
+  }
+};
 // what the next evaluation's window is centred on: this evaluation's exact median and sigma (api.hip)
 void record_statistics(Workspace &w, int kind, bool has_median, const GnResult &r);
 

@@ -541,15 +541,19 @@ size_t tiny_lds_bytes_of(int dim, unsigned m);
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
-// EXTENSION: the quality of a pose (quality.hip; include/icp_mi355x.h section 9).  A record of its fold tree: the six
-// sums that are doubles -- inlier d2, e2, rho(e2), inlier qx, qy, qx qx + qy qy -- the inlier count and whether some e2
-// was NaN.
-constexpr int kQualitySums = 6;
-struct QualityPart {
-  double v[kQualitySums];
+// A record of the fold tree of section 9 (fold_device.hpp): SUMS sums that are doubles, the inlier count and whether some
+// residual was NaN.
+template <int SUMS>
+struct FoldPart {
+  double v[SUMS];
   unsigned long long inliers;
   unsigned nan, pad;
 };
+// EXTENSION: the quality of a pose (quality.hip; include/icp_mi355x.h section 9).  Its six sums: inlier d2, e2,
+// rho(e2), inlier qx, qy, qx qx + qy qy.
+constexpr int kQualitySums = 6;
+using QualityPart = FoldPart<kQualitySums>;
+static_assert(sizeof(QualityPart) == 64, "eight doubles per record: ceil(n / 256) of them fit in max(n, 256)");
 // host: n and zeros; the fields of section 9 from the root record (ICP_NAN_INPUT where it carries the flag)
 void quality_clear(size_t n, icp_quality *q);
 int quality_result(size_t n, const QualityPart &p, icp_quality *q);

@@ -1,9 +1,9 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 11): the sliding-window map -- icp_crop_targets keeps the
 // targets of a handle that lie in a disc of the xy plane and lets go of the others; the counterpart of
-// icp_append_targets (section 6).  Two STABLE compactions, each in the shape of the gate (gate.hip): a mark launch that
-// counts the survivors of every tile of 1 024 consecutive elements (ballot + lane rank per wave), a chunk-sum launch
-// (always run here: its sums are also how the host learns the total) and a place launch in which a workgroup per tile
-// adds up the counts in front of it and moves its survivors there.
+// icp_append_targets (section 6).  Two STABLE compactions (compact_device.hpp): a mark launch that counts the survivors
+// of every tile of 1 024 consecutive elements, the chunk-sum launch k_compact_chunks (always run here: its sums are also
+// how the host learns the total) and a place launch in which a workgroup per tile adds up the counts in front of it and
+// moves its survivors there.
 //   targets   k_crop_mark<DIM>      w[i] = kept ? 0 : kCropGone by the keep rule, cnt[tile]
 //             k_crop_place<DIM>     w[i] = the new index of target i (or kCropGone): the new_index table; the points, and
 //                                   the normals where present, move to their new index in a second buffer
@@ -12,13 +12,13 @@
 //                                   the number of survivors in front of it, its idx rewritten; that number is left in
 //                                   w[p] for EVERY p, so that
 //             k_crop_starts         start2[c] = w[start[c]] (one gather), and the sentinel records follow the last one
-// Every position counts survivors that come EARLIER in the input: the order is kept and a position is a pure function
-// of the inputs.  No atomics, no float reductions, no workgroup waits for another.  The grid keeps the box and the cell
-// size of its last full build (upper bounds of the kept cloud's: exact, like the grid of an incremental append).
+// No float reductions.  The grid keeps the box and the cell size of its last full build (upper bounds of the kept
+// cloud's: exact, like the grid of an incremental append).
 #include <cmath>
 #include <utility>
 
 #include "api_internal.hpp"
+#include "compact_device.hpp"
 
 using namespace icp;
 using namespace icp::api;
@@ -26,78 +26,26 @@ using namespace icp::api;
 namespace icp {
 namespace {
 
-constexpr unsigned kCropThreads = 256, kCropWaves = kCropThreads / 64;
-constexpr unsigned kCropRounds = 4;
-constexpr unsigned kCropTile = kCropThreads * kCropRounds;  // elements per workgroup
-constexpr unsigned kCropChunk = 8192;                       // tiles whose counts one workgroup adds up itself (2^23 elements)
 constexpr uint32_t kCropGone = 0xffffffffu;
 // The kept cloud has fallen below 1 / kRebuildShrink of the cloud the grid's cell size was chosen for: rebuild (the
 // mirror of append_grid's kRebuildGrowth)
 constexpr double kRebuildShrink = 1.5;
-
-// the sum of v over the workgroup (every thread calls it; every thread gets it)
-__device__ __forceinline__ unsigned crop_block_sum(unsigned v, unsigned *lds) {
-  const unsigned tid = threadIdx.x;
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  __syncthreads();  // (lds may still be read from an earlier call)
-  if ((tid & 63u) == 0) lds[tid >> 6] = v;
-  __syncthreads();
-  unsigned t = 0;
-#pragma unroll
-  for (unsigned w = 0; w < kCropWaves; ++w) t += lds[w];
-  return t;
-}
-
-// in[k]: the flag of the thread's element of round k (element k * kCropThreads + tid of the tile).  rank[k] = the
-// tile's survivors in front of that element (whether it survives or not); returns the tile's survivors.
-__device__ __forceinline__ unsigned crop_tile_ranks(const bool (&in)[kCropRounds], unsigned (&rank)[kCropRounds],
-                                                    unsigned (*wcnt)[kCropWaves]) {
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const unsigned long long mask = __ballot(in[k]);
-    rank[k] = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) wcnt[k][wave] = __popcll(mask);
-  }
-  __syncthreads();
-  unsigned total = 0;
-#pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-#pragma unroll
-    for (unsigned w = 0; w < kCropWaves; ++w) {
-      if (w == wave) rank[k] += total;
-      total += wcnt[k][w];
-    }
-  }
-  return total;
-}
-
-// the survivors of the tiles in front of `tile`: the chunk sums in front of its chunk + the counts in front of it there
-__device__ __forceinline__ unsigned crop_tile_base(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ sums,
-                                                   unsigned tile, unsigned *lds) {
-  const unsigned tid = threadIdx.x, chunk = tile / kCropChunk;
-  unsigned s = 0;
-  for (unsigned c = tid; c < chunk; c += kCropThreads) s += sums[c];
-  for (size_t t = (size_t)chunk * kCropChunk + tid; t < tile; t += kCropThreads) s += cnt[t];
-  return crop_block_sum(s, lds);
-}
 
 }  // namespace
 
 // The keep rule (include/icp_mi355x.h section 11): dx = x - cx, dy = y - cy, d2 = dx dx + dy dy (no FMA: the library is
 // compiled with -ffp-contract=off), kept iff d2 <= r2 (false for a NaN d2).  z takes no part.
 template <int DIM>
-__global__ __launch_bounds__(kCropThreads) void k_crop_mark(const double *__restrict__ dst, unsigned m, double cx, double cy,
+__global__ __launch_bounds__(kCompactThreads) void k_crop_mark(const double *__restrict__ dst, unsigned m, double cx, double cy,
                                                             double r2, uint32_t *__restrict__ w,
                                                             uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
-  const size_t first = (size_t)blockIdx.x * kCropTile;
-  bool in[kCropRounds];
-  unsigned rank[kCropRounds];
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  bool in[kCompactRounds];
+  unsigned rank[kCompactRounds];
 #pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const size_t i = first + k * kCropThreads + threadIdx.x;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + threadIdx.x;
     in[k] = false;
     if (i < m) {
       const double dx = dst[i * DIM] - cx, dy = dst[i * DIM + 1] - cy;
@@ -106,47 +54,35 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_mark(const double *__rest
       w[i] = in[k] ? 0u : kCropGone;
     }
   }
-  const unsigned total = crop_tile_ranks(in, rank, wcnt);
+  const unsigned total = compact_tile_ranks(in, rank, wcnt);
   if (threadIdx.x == 0) cnt[blockIdx.x] = total;
-}
-
-// sums[c] = the survivors of tiles [kCropChunk c, kCropChunk (c + 1))
-__global__ __launch_bounds__(kCropThreads) void k_crop_chunks(const uint32_t *__restrict__ cnt, unsigned tiles,
-                                                              uint32_t *__restrict__ sums) {
-  __shared__ unsigned lds[kCropWaves];
-  const size_t t0 = (size_t)blockIdx.x * kCropChunk;
-  const size_t t1 = t0 + kCropChunk < tiles ? t0 + kCropChunk : tiles;
-  unsigned s = 0;
-  for (size_t t = t0 + threadIdx.x; t < t1; t += kCropThreads) s += cnt[t];
-  s = crop_block_sum(s, lds);
-  if (threadIdx.x == 0) sums[blockIdx.x] = s;
 }
 
 // w: in, the marks; out, the new_index table.  *normals_kept (nullable) receives the survivors among the first
 // normals_m targets when normals_m < m (the host knows it otherwise: all of them).
 template <int DIM>
-__global__ __launch_bounds__(kCropThreads) void k_crop_place(const double *__restrict__ dst,
+__global__ __launch_bounds__(kCompactThreads) void k_crop_place(const double *__restrict__ dst,
                                                              const double *__restrict__ normals, unsigned normals_m,
                                                              unsigned m, uint32_t *__restrict__ w,
                                                              const uint32_t *__restrict__ cnt,
                                                              const uint32_t *__restrict__ sums, double *__restrict__ out,
                                                              double *__restrict__ out_normals,
                                                              uint32_t *__restrict__ normals_kept) {
-  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
-  __shared__ unsigned lds[kCropWaves];
-  const unsigned base = crop_tile_base(cnt, sums, blockIdx.x, lds);
-  const size_t first = (size_t)blockIdx.x * kCropTile;
-  bool in[kCropRounds];
-  unsigned rank[kCropRounds];
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  __shared__ unsigned lds[kCompactWaves];
+  const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  bool in[kCompactRounds];
+  unsigned rank[kCompactRounds];
 #pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const size_t i = first + k * kCropThreads + threadIdx.x;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + threadIdx.x;
     in[k] = i < m && w[i] != kCropGone;
   }
-  (void)crop_tile_ranks(in, rank, wcnt);
+  (void)compact_tile_ranks(in, rank, wcnt);
 #pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const size_t i = first + k * kCropThreads + threadIdx.x;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + threadIdx.x;
     if (i >= m) continue;
     const size_t at = (size_t)base + rank[k];  // (< the survivors in all: inside a buffer that holds them)
     if (normals_kept && i == normals_m) *normals_kept = (uint32_t)at;
@@ -162,16 +98,16 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_place(const double *__res
 }
 
 // w[p] = the new index of the target behind the record at sorted position p (kCropGone: removed)
-__global__ __launch_bounds__(kCropThreads) void k_crop_rec_mark(const GridPoint *__restrict__ pts, unsigned m,
+__global__ __launch_bounds__(kCompactThreads) void k_crop_rec_mark(const GridPoint *__restrict__ pts, unsigned m,
                                                                 const uint32_t *__restrict__ new_index,
                                                                 uint32_t *__restrict__ w, uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
-  const size_t first = (size_t)blockIdx.x * kCropTile;
-  bool in[kCropRounds];
-  unsigned rank[kCropRounds];
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  bool in[kCompactRounds];
+  unsigned rank[kCompactRounds];
 #pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const size_t p = first + k * kCropThreads + threadIdx.x;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t p = first + k * kCompactThreads + threadIdx.x;
     in[k] = false;
     if (p < m) {
       const uint32_t j = pts[p].idx;
@@ -180,32 +116,32 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_rec_mark(const GridPoint 
       in[k] = to != kCropGone;
     }
   }
-  const unsigned total = crop_tile_ranks(in, rank, wcnt);
+  const unsigned total = compact_tile_ranks(in, rank, wcnt);
   if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 
 // w: in, the records' new indices; out, for EVERY sorted position p the survivors in front of it
-__global__ __launch_bounds__(kCropThreads) void k_crop_rec_place(const GridPoint *__restrict__ pts, unsigned m,
+__global__ __launch_bounds__(kCompactThreads) void k_crop_rec_place(const GridPoint *__restrict__ pts, unsigned m,
                                                                  uint32_t *__restrict__ w, const uint32_t *__restrict__ cnt,
                                                                  const uint32_t *__restrict__ sums,
                                                                  GridPoint *__restrict__ pts2) {
-  __shared__ unsigned wcnt[kCropRounds][kCropWaves];
-  __shared__ unsigned lds[kCropWaves];
-  const unsigned base = crop_tile_base(cnt, sums, blockIdx.x, lds);
-  const size_t first = (size_t)blockIdx.x * kCropTile;
-  bool in[kCropRounds];
-  unsigned rank[kCropRounds];
-  uint32_t to[kCropRounds];
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  __shared__ unsigned lds[kCompactWaves];
+  const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  bool in[kCompactRounds];
+  unsigned rank[kCompactRounds];
+  uint32_t to[kCompactRounds];
 #pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const size_t p = first + k * kCropThreads + threadIdx.x;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t p = first + k * kCompactThreads + threadIdx.x;
     to[k] = p < m ? w[p] : kCropGone;
     in[k] = to[k] != kCropGone;
   }
-  (void)crop_tile_ranks(in, rank, wcnt);
+  (void)compact_tile_ranks(in, rank, wcnt);
 #pragma unroll
-  for (unsigned k = 0; k < kCropRounds; ++k) {
-    const size_t p = first + k * kCropThreads + threadIdx.x;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t p = first + k * kCompactThreads + threadIdx.x;
     if (p >= m) continue;
     const size_t at = (size_t)base + rank[k];
     w[p] = (uint32_t)at;
@@ -231,9 +167,6 @@ __global__ void k_crop_starts(const uint32_t *__restrict__ start, unsigned nscan
 
 namespace {
 
-unsigned crop_tiles(size_t n) { return (unsigned)((n + kCropTile - 1) / kCropTile); }
-unsigned crop_chunks(unsigned tiles) { return (tiles + kCropChunk - 1) / kCropChunk; }
-
 int crop_quiesce(icp_handle *h) {
   HIP_TRY(hipSetDevice(h->device));
   if (h->own_stream) HIP_TRY(hipStreamSynchronize(h->own_stream));
@@ -248,16 +181,16 @@ hipError_t crop_move_records(icp_handle *h, unsigned m_old, unsigned kept, const
   Grid &G = h->grid;
   hipStream_t s = h->stream;
   hipError_t e;
-  const unsigned nscan = G.ncell + 1, tiles = crop_tiles(m_old), chunks = crop_chunks(tiles);
+  const unsigned nscan = G.ncell + 1, tiles = compact_tiles(m_old);
   uint32_t *sums = cnt + tiles;
   if ((e = reserve(G.d_pts2, G.cap_pts2, (size_t)kept + kGridPad)) != hipSuccess) return e;
   if ((e = reserve(G.d_start2, G.cap_start2, (size_t)nscan)) != hipSuccess) return e;
   if ((e = reserve(G.d_rcell2, G.cap_rcell2, (size_t)m_old)) != hipSuccess) return e;  // (free between appends: the marks)
   uint32_t *w = G.d_rcell2;
-  hipLaunchKernelGGL(k_crop_rec_mark, dim3(tiles), dim3(kCropThreads), 0, s, (const GridPoint *)G.d_pts, m_old, new_index, w,
+  hipLaunchKernelGGL(k_crop_rec_mark, dim3(tiles), dim3(kCompactThreads), 0, s, (const GridPoint *)G.d_pts, m_old, new_index, w,
                      cnt);
-  hipLaunchKernelGGL(k_crop_chunks, dim3(chunks), dim3(kCropThreads), 0, s, (const uint32_t *)cnt, tiles, sums);
-  hipLaunchKernelGGL(k_crop_rec_place, dim3(tiles), dim3(kCropThreads), 0, s, (const GridPoint *)G.d_pts, m_old, w,
+  if ((e = launch_compact_chunks(cnt, tiles, sums, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_crop_rec_place, dim3(tiles), dim3(kCompactThreads), 0, s, (const GridPoint *)G.d_pts, m_old, w,
                      (const uint32_t *)cnt, (const uint32_t *)sums, G.d_pts2);
   hipLaunchKernelGGL(k_crop_starts, dim3((nscan + kGridPad + 255) / 256), dim3(256), 0, s, (const uint32_t *)G.d_start, nscan,
                      (const uint32_t *)w, m_old, kept, G.d_start2, G.d_pts2);
@@ -270,7 +203,7 @@ int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *n
   if (h->m == 0) return ICP_OK;
   Grid &G = h->grid;
   hipStream_t s = h->stream;
-  const unsigned m_old = (unsigned)h->m, tiles = crop_tiles(m_old), chunks = crop_chunks(tiles);
+  const unsigned m_old = (unsigned)h->m, tiles = compact_tiles(m_old), chunks = compact_chunks(tiles);
   const int dim = h->dim;
   // the new_index table: the grid's build temporary of m words, free between builds; the tile counts, the chunk sums and
   // one word for the normals: the append's shift table, free between appends
@@ -279,11 +212,10 @@ int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *n
   uint32_t *w = G.t_cell_of, *cnt = G.t_shift, *sums = cnt + tiles, *aux = sums + chunks;
   const double r2 = radius * radius;
   if (dim == 3)
-    hipLaunchKernelGGL(k_crop_mark<3>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
+    hipLaunchKernelGGL(k_crop_mark<3>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
   else
-    hipLaunchKernelGGL(k_crop_mark<2>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
-  hipLaunchKernelGGL(k_crop_chunks, dim3(chunks), dim3(kCropThreads), 0, s, (const uint32_t *)cnt, tiles, sums);
-  HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_crop_mark<2>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
+  HIP_TRY(launch_compact_chunks(cnt, tiles, sums, s));
   std::vector<uint32_t> host(chunks + 1);
   HIP_TRY(hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -305,11 +237,11 @@ int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *n
   const bool count_normals = with_normals && normals_m < m_old;
   if (kept > 0 || new_index || count_normals) {
     if (dim == 3)
-      hipLaunchKernelGGL(k_crop_place<3>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, (const double *)h->d_normals,
+      hipLaunchKernelGGL(k_crop_place<3>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, (const double *)h->d_normals,
                          normals_m, m_old, w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt,
                          with_normals && kept > 0 ? h->d_normals_alt : nullptr, count_normals ? aux : nullptr);
     else
-      hipLaunchKernelGGL(k_crop_place<2>, dim3(tiles), dim3(kCropThreads), 0, s, h->d_dst, (const double *)nullptr, 0u, m_old,
+      hipLaunchKernelGGL(k_crop_place<2>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, (const double *)nullptr, 0u, m_old,
                          w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt, (double *)nullptr,
                          (uint32_t *)nullptr);
     HIP_TRY(hipGetLastError());
@@ -393,8 +325,7 @@ extern "C" int icp_crop_targets(icp_handle *h, const double center_xy[2], double
   // (radius >= 0 is false for a NaN; so is c == c)
   if (!h || !center_xy || !(center_xy[0] == center_xy[0]) || !(center_xy[1] == center_xy[1]) || !(radius >= 0.))
     return ICP_BAD_ARGUMENT;
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return ICP_NO_DEVICE;
+  if (!have_device()) return ICP_NO_DEVICE;
   return crop_targets(h, center_xy[0], center_xy[1], radius, new_index, removed);
 }
 

@@ -1,64 +1,40 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 10): the gate of a registration with a maximum
 // correspondence distance -- from a source cloud, a pose and the indices of a search, the pairs (xy(T src), xy(dst[idx]))
 // of the INLIERS (d2 <= r * r, section 9's rule), written densely and in the order of the source cloud.
-// A stable compaction in two launches (qsort.hip's count launch + scatter launch is the pattern):
-//   k_gate_stage<DIM>   a tile = 1 024 consecutive points = one workgroup of four waves, four rounds of 256 points.  A lane
-//                       recomputes q, b and d2 of its four points (the ONE gather of dst), a ballot per round and wave
-//                       gives the wave's count and the lane's rank among its wave's survivors, the sixteen counts meet
-//                       in LDS, and the tile's survivors go -- compacted, in order -- to the start of the tile's own
-//                       segment of the staging buffers (consecutive survivors = consecutive 16-byte stores); the tile's
-//                       count goes to cnt[tile]
-//   k_gate_chunks       only beyond kGateChunk tiles (2^23 points): the counts of every kGateChunk tiles added up, so that
-//                       a workgroup of the next launch reads at most kGateChunk counts and the chunk sums in front of it
+// The stable compaction of compact_device.hpp in two launches (qsort.hip's count launch + scatter launch is the pattern):
+//   k_gate_stage<DIM>   a tile = 1 024 consecutive points.  A lane recomputes q, b and d2 of its four points (the ONE
+//                       gather of dst), and the tile's survivors go -- compacted, in order -- to the start of the tile's
+//                       own segment of the staging buffers (consecutive survivors = consecutive 16-byte stores); the
+//                       tile's count goes to cnt[tile]
+//   k_compact_chunks    only beyond kCompactChunk tiles (2^23 points): a workgroup of the next launch then reads at most
+//                       kCompactChunk counts and the chunk sums in front of it
 //   k_gate_place        a workgroup per tile: (survivors of the tiles in front) = where the tile's staged survivors
 //                       go; it copies them there (streaming: no gather, no recomputation), and the workgroup of the
 //                       last tile leaves the total in the handle's pinned result block
-// Every term of a survivor's position counts survivors that come EARLIER in the source cloud: the order is kept and
-// the position is a pure function of the inputs.  No atomics, no float reductions, no workgroup waits for another.
+// No float reductions: like a survivor's position, its values are a pure function of the inputs.
 #include "api_internal.hpp"
+#include "compact_device.hpp"
 
 using namespace icp;
 using namespace icp::api;
 
 namespace icp {
-namespace {
-
-constexpr unsigned kGateThreads = 256, kGateWaves = kGateThreads / 64;
-constexpr unsigned kGateRounds = 4;
-constexpr unsigned kGateTile = kGateThreads * kGateRounds;  // points per workgroup
-constexpr unsigned kGateChunk = 8192;                       // tiles whose counts one workgroup adds up itself
-
-// the sum of v over the workgroup (every thread calls it; every thread gets it)
-__device__ __forceinline__ unsigned gate_block_sum(unsigned v, unsigned *lds) {
-  const unsigned tid = threadIdx.x;
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  __syncthreads();  // (lds may still be read from an earlier call)
-  if ((tid & 63u) == 0) lds[tid >> 6] = v;
-  __syncthreads();
-  unsigned t = 0;
-#pragma unroll
-  for (unsigned w = 0; w < kGateWaves; ++w) t += lds[w];
-  return t;
-}
-
-}  // namespace
 
 template <int DIM>
-__global__ __launch_bounds__(kGateThreads) void k_gate_stage(const double *__restrict__ src, unsigned n, Pose T,
-                                                             const uint32_t *__restrict__ idx,
-                                                             const double *__restrict__ dst, unsigned m, double r2,
-                                                             double2 *__restrict__ st_a, double2 *__restrict__ st_b,
-                                                             uint32_t *__restrict__ st_pos, uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kGateRounds][kGateWaves];
-  const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const size_t first = (size_t)blockIdx.x * kGateTile;
-  double2 a[kGateRounds], b[kGateRounds];
-  unsigned rank[kGateRounds];
-  bool keep[kGateRounds];
+__global__ __launch_bounds__(kCompactThreads) void k_gate_stage(const double *__restrict__ src, unsigned n, Pose T,
+                                                                const uint32_t *__restrict__ idx,
+                                                                const double *__restrict__ dst, unsigned m, double r2,
+                                                                double2 *__restrict__ st_a, double2 *__restrict__ st_b,
+                                                                uint32_t *__restrict__ st_pos, uint32_t *__restrict__ cnt) {
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  const unsigned tid = threadIdx.x;
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  double2 a[kCompactRounds], b[kCompactRounds];
+  unsigned rank[kCompactRounds];
+  bool keep[kCompactRounds];
 #pragma unroll
-  for (unsigned k = 0; k < kGateRounds; ++k) {
-    const size_t i = first + k * kGateThreads + tid;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + tid;
     bool in = false;
     a[k] = make_double2(0., 0.);
     b[k] = make_double2(0., 0.);
@@ -81,63 +57,37 @@ __global__ __launch_bounds__(kGateThreads) void k_gate_stage(const double *__res
       a[k] = make_double2(qx, qy);
       b[k] = make_double2(bx, by);
     }
-    const unsigned long long mask = __ballot(in);
-    rank[k] = __popcll(mask & ((1ull << lane) - 1ull));
+    rank[k] = compact_wave_rank(__ballot(in), wcnt[k]);
     keep[k] = in;
-    if (lane == 0) wcnt[k][wave] = __popcll(mask);
   }
   __syncthreads();
-  // survivors of the rounds and waves in front of each of the lane's four (rounds in order, waves in order inside one)
-  unsigned before = 0, total = 0;
+  unsigned total = 0;
 #pragma unroll
-  for (unsigned k = 0; k < kGateRounds; ++k) {
-    unsigned mine = 0;
-#pragma unroll
-    for (unsigned w = 0; w < kGateWaves; ++w) {
-      const unsigned c = wcnt[k][w];
-      if (w == wave) mine = total;
-      total += c;
-    }
-    before = mine;
-    if (keep[k]) {
-      const size_t at = first + before + rank[k];  // (< first + the tile's points: inside the tile's own segment)
-      st_a[at] = a[k];
-      st_b[at] = b[k];
-      if (st_pos) st_pos[at] = (uint32_t)(first + k * kGateThreads + tid);
-    }
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    unsigned before = 0;  // (apart from rank[k]: summed into it, the kernel takes more registers)
+    compact_round_offset(before, wcnt[k], total);
+    if (!keep[k]) continue;
+    const size_t at = first + before + rank[k];  // (< first + the tile's points: inside the tile's own segment)
+    st_a[at] = a[k];
+    st_b[at] = b[k];
+    if (st_pos) st_pos[at] = (uint32_t)(first + k * kCompactThreads + tid);
   }
   if (tid == 0) cnt[blockIdx.x] = total;
 }
 
-// sums[c] = the survivors of tiles [kGateChunk c, kGateChunk (c + 1))
-__global__ __launch_bounds__(kGateThreads) void k_gate_chunks(const uint32_t *__restrict__ cnt, unsigned tiles,
-                                                              uint32_t *__restrict__ sums) {
-  __shared__ unsigned lds[kGateWaves];
-  const size_t t0 = (size_t)blockIdx.x * kGateChunk;
-  const size_t t1 = t0 + kGateChunk < tiles ? t0 + kGateChunk : tiles;
-  unsigned s = 0;
-  for (size_t t = t0 + threadIdx.x; t < t1; t += kGateThreads) s += cnt[t];
-  s = gate_block_sum(s, lds);
-  if (threadIdx.x == 0) sums[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(kGateThreads) void k_gate_place(const double2 *__restrict__ st_a,
-                                                             const double2 *__restrict__ st_b,
-                                                             const uint32_t *__restrict__ st_pos,
-                                                             const uint32_t *__restrict__ cnt,
-                                                             const uint32_t *__restrict__ sums, unsigned tiles,
-                                                             double2 *__restrict__ out_a, double2 *__restrict__ out_b,
-                                                             uint32_t *__restrict__ out_pos, unsigned *__restrict__ h_total) {
-  __shared__ unsigned lds[kGateWaves];
+__global__ __launch_bounds__(kCompactThreads) void k_gate_place(const double2 *__restrict__ st_a,
+                                                                const double2 *__restrict__ st_b,
+                                                                const uint32_t *__restrict__ st_pos,
+                                                                const uint32_t *__restrict__ cnt,
+                                                                const uint32_t *__restrict__ sums, unsigned tiles,
+                                                                double2 *__restrict__ out_a, double2 *__restrict__ out_b,
+                                                                uint32_t *__restrict__ out_pos, unsigned *__restrict__ h_total) {
+  __shared__ unsigned lds[kCompactWaves];
   const unsigned tid = threadIdx.x, tile = blockIdx.x;
-  const unsigned chunk = tile / kGateChunk;
-  unsigned s = 0;
-  for (unsigned c = tid; c < chunk; c += kGateThreads) s += sums[c];  // (no chunk in front below kGateChunk tiles: sums unread)
-  for (size_t t = (size_t)chunk * kGateChunk + tid; t < tile; t += kGateThreads) s += cnt[t];
-  const unsigned base = gate_block_sum(s, lds);
+  const unsigned base = compact_tile_base(cnt, sums, tile, lds);
   const unsigned c = cnt[tile];
-  const size_t from = (size_t)tile * kGateTile;
-  for (unsigned r = tid; r < c; r += kGateThreads) {
+  const size_t from = (size_t)tile * kCompactTile;
+  for (unsigned r = tid; r < c; r += kCompactThreads) {
     out_a[(size_t)base + r] = st_a[from + r];
     out_b[(size_t)base + r] = st_b[from + r];
     if (out_pos) out_pos[(size_t)base + r] = st_pos[from + r];
@@ -156,25 +106,21 @@ hipError_t launch_gate(icp_handle *h, const double *d_src, size_t n, const Pose 
   Workspace &w = h->ws;
   w.h_res->pad = 0;
   if (n == 0) return hipSuccess;
-  const unsigned tiles = (unsigned)((n + kGateTile - 1) / kGateTile);
-  const unsigned chunks = (tiles + kGateChunk - 1) / kGateChunk;
+  const unsigned tiles = compact_tiles(n), chunks = compact_chunks(tiles);
   // (cap_n >= 256 doubles per residual buffer: tiles + chunks words fit -- a word per 1 024 points and one per 2^23)
   uint32_t *cnt = reinterpret_cast<uint32_t *>(w.d_ry), *sums = cnt + tiles;
   uint32_t *st_pos = d_kept ? reinterpret_cast<uint32_t *>(w.d_rx) : nullptr;
   double2 *st_a = reinterpret_cast<double2 *>(w.d_a3), *st_b = reinterpret_cast<double2 *>(w.d_b3);
   if (h->dim == 2)
-    hipLaunchKernelGGL(k_gate_stage<2>, dim3(tiles), dim3(kGateThreads), 0, h->stream, d_src, (unsigned)n, T, d_idx,
+    hipLaunchKernelGGL(k_gate_stage<2>, dim3(tiles), dim3(kCompactThreads), 0, h->stream, d_src, (unsigned)n, T, d_idx,
                        h->d_dst, (unsigned)h->m, r2, st_a, st_b, st_pos, cnt);
   else
-    hipLaunchKernelGGL(k_gate_stage<3>, dim3(tiles), dim3(kGateThreads), 0, h->stream, d_src, (unsigned)n, T, d_idx,
+    hipLaunchKernelGGL(k_gate_stage<3>, dim3(tiles), dim3(kCompactThreads), 0, h->stream, d_src, (unsigned)n, T, d_idx,
                        h->d_dst, (unsigned)h->m, r2, st_a, st_b, st_pos, cnt);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (chunks > 1) {
-    hipLaunchKernelGGL(k_gate_chunks, dim3(chunks), dim3(kGateThreads), 0, h->stream, (const uint32_t *)cnt, tiles, sums);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_gate_place, dim3(tiles), dim3(kGateThreads), 0, h->stream, (const double2 *)st_a,
+  if (chunks > 1 && (e = launch_compact_chunks(cnt, tiles, sums, h->stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_gate_place, dim3(tiles), dim3(kCompactThreads), 0, h->stream, (const double2 *)st_a,
                      (const double2 *)st_b, (const uint32_t *)st_pos, (const uint32_t *)cnt, (const uint32_t *)sums,
                      tiles, reinterpret_cast<double2 *>(d_a), reinterpret_cast<double2 *>(d_b), d_kept, &w.h_res->pad);
   return hipGetLastError();
@@ -193,11 +139,10 @@ extern "C" int icp_gate_pairs_device(icp_handle *h, const double *d_src, size_t 
     return ICP_BAD_ARGUMENT;
   *kept = 0;
   if (n == 0) return ICP_OK;
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return ICP_NO_DEVICE;
+  if (!have_device()) return ICP_NO_DEVICE;
   if (h->m == 0) return ICP_EMPTY_DST;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < 256 ? 256 : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   HIP_TRY(launch_gate(h, d_src, n, *T, d_idx, max_dist * max_dist, d_a, d_b, d_kept));
   HIP_TRY(hipStreamSynchronize(h->stream));
   *kept = gate_count(h);

@@ -1,67 +1,45 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 12): the gate of a POINT-TO-PLANE registration with a
 // maximum correspondence distance -- from a source cloud, a pose, the indices of a search and the targets' normals, the
 // PlanePair (p2plane_device.hpp: what k_p2pl_gather writes for every point) of the INLIERS only (d2 <= r * r, section
-// 9's rule), written densely and in the order of the source cloud.  gate.hip's stable compaction around the wider record:
-//   k_plgate_stage    a tile = 1 024 consecutive points = one workgroup of four waves, four rounds of 256 points.  A lane
-//                     does the ONE gather of dst[j] and normals[j] of its four points and computes d2 and the eight
-//                     values; a ballot per round and wave gives the wave's count and the lane's rank among its wave's
-//                     survivors, the sixteen counts meet in LDS, and the tile's survivors go -- compacted, in order --
+// 9's rule), written densely and in the order of the source cloud.  The stable compaction of compact_device.hpp around
+// the wider record:
+//   k_plgate_stage    a tile = 1 024 consecutive points.  A lane does the ONE gather of dst[j] and normals[j] of its four
+//                     points and computes d2 and the eight values, and the tile's survivors go -- compacted, in order --
 //                     to the start of the tile's own segment of the staging buffer (a survivor = four 16-byte stores,
 //                     consecutive survivors = consecutive 64 bytes); the tile's count goes to cnt[tile]
-//   k_plgate_chunks   only beyond kPlaneGateChunk tiles (2^23 points): the counts of every kPlaneGateChunk tiles added up
+//   k_compact_chunks  only beyond kCompactChunk tiles (2^23 points): the counts of every kCompactChunk tiles added up
 //   k_plgate_place    a workgroup per tile: (survivors of the tiles in front) = where the tile's staged survivors go; it
 //                     streams them there, 16 bytes per lane and step, and the workgroup of the last tile leaves the
 //                     total in the handle's pinned result block
-// Every term of a survivor's position counts survivors that come EARLIER in the source cloud: the order is kept and
-// the position is a pure function of the inputs.  No atomics, no float reductions, no workgroup waits for another.
+// No float reductions: like a survivor's position, its values are a pure function of the inputs.
 #include "api_internal.hpp"
+#include "compact_device.hpp"
 #include "p2plane_device.hpp"
 
 using namespace icp;
 using namespace icp::api;
 
 namespace icp {
-namespace {
 
-constexpr unsigned kPlaneGateThreads = 256, kPlaneGateWaves = kPlaneGateThreads / 64;
-constexpr unsigned kPlaneGateRounds = 4;
-constexpr unsigned kPlaneGateTile = kPlaneGateThreads * kPlaneGateRounds;  // points per workgroup
-constexpr unsigned kPlaneGateChunk = 8192;  // tiles whose counts one workgroup adds up itself
-constexpr unsigned kPairWords = sizeof(PlanePair) / sizeof(double2);       // 16-byte words of a pair
+constexpr unsigned kPairWords = sizeof(PlanePair) / sizeof(double2);  // 16-byte words of a pair
 static_assert(sizeof(PlanePair) == 64 && kPairWords == 4, "a pair is four 16-byte words");
 
-// the sum of v over the workgroup (every thread calls it; every thread gets it)
-__device__ __forceinline__ unsigned plgate_block_sum(unsigned v, unsigned *lds) {
+__global__ __launch_bounds__(kCompactThreads) void k_plgate_stage(const double *__restrict__ src, unsigned n, Pose T,
+                                                                  const uint32_t *__restrict__ idx,
+                                                                  const double *__restrict__ dst, unsigned m,
+                                                                  const double *__restrict__ normals, double r2,
+                                                                  double2 *__restrict__ st_pairs,
+                                                                  uint32_t *__restrict__ st_pos,
+                                                                  uint32_t *__restrict__ cnt) {
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
   const unsigned tid = threadIdx.x;
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  double2 w0[kCompactRounds], w1[kCompactRounds], w2[kCompactRounds], w3[kCompactRounds];
+  unsigned rank[kCompactRounds];
+  bool keep[kCompactRounds];
 #pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  __syncthreads();  // (lds may still be read from an earlier call)
-  if ((tid & 63u) == 0) lds[tid >> 6] = v;
-  __syncthreads();
-  unsigned t = 0;
-#pragma unroll
-  for (unsigned w = 0; w < kPlaneGateWaves; ++w) t += lds[w];
-  return t;
-}
-
-}  // namespace
-
-__global__ __launch_bounds__(kPlaneGateThreads) void k_plgate_stage(const double *__restrict__ src, unsigned n, Pose T,
-                                                                    const uint32_t *__restrict__ idx,
-                                                                    const double *__restrict__ dst, unsigned m,
-                                                                    const double *__restrict__ normals, double r2,
-                                                                    double2 *__restrict__ st_pairs,
-                                                                    uint32_t *__restrict__ st_pos,
-                                                                    uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kPlaneGateRounds][kPlaneGateWaves];
-  const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const size_t first = (size_t)blockIdx.x * kPlaneGateTile;
-  double2 w0[kPlaneGateRounds], w1[kPlaneGateRounds], w2[kPlaneGateRounds], w3[kPlaneGateRounds];
-  unsigned rank[kPlaneGateRounds];
-  bool keep[kPlaneGateRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kPlaneGateRounds; ++k) {
-    const size_t i = first + k * kPlaneGateThreads + tid;
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + tid;
     bool in = false;
     w0[k] = w1[k] = w2[k] = w3[k] = make_double2(0., 0.);
     if (i < n) {
@@ -81,68 +59,43 @@ __global__ __launch_bounds__(kPlaneGateThreads) void k_plgate_stage(const double
       w2[k] = make_double2(dz, nx);
       w3[k] = make_double2(ny, nz);
     }
-    const unsigned long long mask = __ballot(in);
-    rank[k] = __popcll(mask & ((1ull << lane) - 1ull));
+    rank[k] = compact_wave_rank(__ballot(in), wcnt[k]);
     keep[k] = in;
-    if (lane == 0) wcnt[k][wave] = __popcll(mask);
   }
   __syncthreads();
-  // survivors of the rounds and waves in front of each of the lane's four (rounds in order, waves in order inside one)
   unsigned total = 0;
 #pragma unroll
-  for (unsigned k = 0; k < kPlaneGateRounds; ++k) {
-    unsigned before = 0;
-#pragma unroll
-    for (unsigned w = 0; w < kPlaneGateWaves; ++w) {
-      const unsigned c = wcnt[k][w];
-      if (w == wave) before = total;
-      total += c;
-    }
-    if (keep[k]) {
-      const size_t at = first + before + rank[k];  // (< first + the tile's points: inside the tile's own segment)
-      double2 *o = st_pairs + at * kPairWords;
-      o[0] = w0[k];
-      o[1] = w1[k];
-      o[2] = w2[k];
-      o[3] = w3[k];
-      if (st_pos) st_pos[at] = (uint32_t)(first + k * kPlaneGateThreads + tid);
-    }
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    unsigned before = 0;  // (apart from rank[k]: summed into it, the kernel takes more registers)
+    compact_round_offset(before, wcnt[k], total);
+    if (!keep[k]) continue;
+    const size_t at = first + before + rank[k];  // (< first + the tile's points: inside the tile's own segment)
+    double2 *o = st_pairs + at * kPairWords;
+    o[0] = w0[k];
+    o[1] = w1[k];
+    o[2] = w2[k];
+    o[3] = w3[k];
+    if (st_pos) st_pos[at] = (uint32_t)(first + k * kCompactThreads + tid);
   }
   if (tid == 0) cnt[blockIdx.x] = total;
 }
 
-// sums[c] = the survivors of tiles [kPlaneGateChunk c, kPlaneGateChunk (c + 1))
-__global__ __launch_bounds__(kPlaneGateThreads) void k_plgate_chunks(const uint32_t *__restrict__ cnt, unsigned tiles,
-                                                                     uint32_t *__restrict__ sums) {
-  __shared__ unsigned lds[kPlaneGateWaves];
-  const size_t t0 = (size_t)blockIdx.x * kPlaneGateChunk;
-  const size_t t1 = t0 + kPlaneGateChunk < tiles ? t0 + kPlaneGateChunk : tiles;
-  unsigned s = 0;
-  for (size_t t = t0 + threadIdx.x; t < t1; t += kPlaneGateThreads) s += cnt[t];
-  s = plgate_block_sum(s, lds);
-  if (threadIdx.x == 0) sums[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(kPlaneGateThreads) void k_plgate_place(const double2 *__restrict__ st_pairs,
-                                                                    const uint32_t *__restrict__ st_pos,
-                                                                    const uint32_t *__restrict__ cnt,
-                                                                    const uint32_t *__restrict__ sums, unsigned tiles,
-                                                                    double2 *__restrict__ out_pairs,
-                                                                    uint32_t *__restrict__ out_pos,
-                                                                    unsigned *__restrict__ h_total) {
-  __shared__ unsigned lds[kPlaneGateWaves];
+__global__ __launch_bounds__(kCompactThreads) void k_plgate_place(const double2 *__restrict__ st_pairs,
+                                                                  const uint32_t *__restrict__ st_pos,
+                                                                  const uint32_t *__restrict__ cnt,
+                                                                  const uint32_t *__restrict__ sums, unsigned tiles,
+                                                                  double2 *__restrict__ out_pairs,
+                                                                  uint32_t *__restrict__ out_pos,
+                                                                  unsigned *__restrict__ h_total) {
+  __shared__ unsigned lds[kCompactWaves];
   const unsigned tid = threadIdx.x, tile = blockIdx.x;
-  const unsigned chunk = tile / kPlaneGateChunk;
-  unsigned s = 0;
-  for (unsigned c = tid; c < chunk; c += kPlaneGateThreads) s += sums[c];  // (no chunk in front below kPlaneGateChunk tiles: sums unread)
-  for (size_t t = (size_t)chunk * kPlaneGateChunk + tid; t < tile; t += kPlaneGateThreads) s += cnt[t];
-  const unsigned base = plgate_block_sum(s, lds);
+  const unsigned base = compact_tile_base(cnt, sums, tile, lds);
   const unsigned c = cnt[tile];  // (<= the tile's points: every read below stays inside the tile's segment)
-  const double2 *from = st_pairs + (size_t)tile * kPlaneGateTile * kPairWords;
+  const double2 *from = st_pairs + (size_t)tile * kCompactTile * kPairWords;
   double2 *to = out_pairs + (size_t)base * kPairWords;
-  for (unsigned r = tid; r < c * kPairWords; r += kPlaneGateThreads) to[r] = from[r];
+  for (unsigned r = tid; r < c * kPairWords; r += kCompactThreads) to[r] = from[r];
   if (out_pos)
-    for (unsigned r = tid; r < c; r += kPlaneGateThreads) out_pos[(size_t)base + r] = st_pos[(size_t)tile * kPlaneGateTile + r];
+    for (unsigned r = tid; r < c; r += kCompactThreads) out_pos[(size_t)base + r] = st_pos[(size_t)tile * kCompactTile + r];
   if (tile + 1 == tiles && tid == 0) *h_total = base + c;  // (pinned host memory: there when the stream's wait returns)
 }
 
@@ -157,22 +110,17 @@ hipError_t launch_gate_plane(icp_handle *h, const double *d_src, size_t n, const
   Workspace &w = h->ws;
   w.h_res->pad = 0;
   if (n == 0) return hipSuccess;
-  const unsigned tiles = (unsigned)((n + kPlaneGateTile - 1) / kPlaneGateTile);
-  const unsigned chunks = (tiles + kPlaneGateChunk - 1) / kPlaneGateChunk;
+  const unsigned tiles = compact_tiles(n), chunks = compact_chunks(tiles);
   // (cap_n >= 256 doubles per residual buffer: tiles + chunks words fit -- a word per 1 024 points and one per 2^23)
   uint32_t *cnt = reinterpret_cast<uint32_t *>(w.d_ry), *sums = cnt + tiles;
   uint32_t *st_pos = d_kept ? reinterpret_cast<uint32_t *>(w.d_rx) : nullptr;
   double2 *st = reinterpret_cast<double2 *>(h->d_plane_stage);
-  hipLaunchKernelGGL(k_plgate_stage, dim3(tiles), dim3(kPlaneGateThreads), 0, h->stream, d_src, (unsigned)n, T, d_idx,
+  hipLaunchKernelGGL(k_plgate_stage, dim3(tiles), dim3(kCompactThreads), 0, h->stream, d_src, (unsigned)n, T, d_idx,
                      h->d_dst, (unsigned)h->m, (const double *)h->d_normals, r2, st, st_pos, cnt);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (chunks > 1) {
-    hipLaunchKernelGGL(k_plgate_chunks, dim3(chunks), dim3(kPlaneGateThreads), 0, h->stream, (const uint32_t *)cnt, tiles,
-                       sums);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_plgate_place, dim3(tiles), dim3(kPlaneGateThreads), 0, h->stream, (const double2 *)st,
+  if (chunks > 1 && (e = launch_compact_chunks(cnt, tiles, sums, h->stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_plgate_place, dim3(tiles), dim3(kCompactThreads), 0, h->stream, (const double2 *)st,
                      (const uint32_t *)st_pos, (const uint32_t *)cnt, (const uint32_t *)sums, tiles,
                      reinterpret_cast<double2 *>(d_pairs), d_kept, &w.h_res->pad);
   return hipGetLastError();

@@ -112,6 +112,21 @@ int map_hip(hipError_t e) {
     if (rc__ != ICP_OK) return rc__; \
   } while (0)
 
+// whatever way the call that holds it ends, nothing of it is in flight on any rank afterwards and no rank keeps a
+// cell-sorted snapshot of a source buffer that the next call overwrites
+struct QuiesceRanks {
+  icp_multi *M;
+  ~QuiesceRanks() {
+    for (auto &R : M->r)
+      if (R.h) {
+        (void)hipSetDevice(R.device);
+        (void)hipStreamSynchronize(R.h->stream);
+        R.h->qsort.valid = false;
+        R.h->qsort.have_prev = false;
+      }
+  }
+};
+
 // memory a peer device reads while the owner's kernels are still running must be fine-grained
 hipError_t alloc_export(void **p, size_t bytes, bool peers) {
   if (peers) return hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained);
@@ -525,21 +540,8 @@ extern "C" int icp_multi_estimate(icp_multi *M, const double *src, size_t n, con
   const int W = M->world, dim = M->dim;
   Pose T = *init;
   if (n > 0 && max_iter > 0 && M->m == 0) return ICP_EMPTY_DST;  // index.unwrap(), src/lib.rs:122,165
-  // whatever way this call ends (an error half-way through an evaluation leaves kernels of the other
-  // ranks enqueued, some of them waiting on flags), nothing of it is in flight afterwards and no
-  // rank keeps a cell-sorted snapshot of a source buffer that the next call overwrites
-  struct Quiesce {
-    icp_multi *M;
-    ~Quiesce() {
-      for (auto &R : M->r)
-        if (R.h) {
-          (void)hipSetDevice(R.device);
-          (void)hipStreamSynchronize(R.h->stream);
-          R.h->qsort.valid = false;
-          R.h->qsort.have_prev = false;
-        }
-    }
-  } quiesce_on_exit{M};
+  // (an error half-way through an evaluation leaves kernels of the other ranks enqueued, some of them waiting on flags)
+  QuiesceRanks quiesce_on_exit{M};
   for (auto &R : M->r)  // (a wait that gave up in an earlier call must not fail this one)
     if (R.d_err) __atomic_store_n(R.d_err, 0u, __ATOMIC_RELEASE);
   // One handle folds its sums over the source cloud in FOLD ORDER (icp_last_fold_order: the cell-sorted
@@ -724,18 +726,7 @@ static int multi_estimate_p2pl(icp_multi *M, const double *src, size_t n, const 
     *out = *init;
     return ICP_OK;
   }
-  struct Quiesce {
-    icp_multi *M;
-    ~Quiesce() {
-      for (auto &R : M->r)
-        if (R.h) {
-          (void)hipSetDevice(R.device);
-          (void)hipStreamSynchronize(R.h->stream);
-          R.h->qsort.valid = false;
-          R.h->qsort.have_prev = false;
-        }
-    }
-  } quiesce_on_exit{M};
+  QuiesceRanks quiesce_on_exit{M};
   Pose T = *init;
   std::vector<size_t> lo(W + 1);
   for (int q = 0; q <= W; ++q) lo[q] = n * (size_t)q / (size_t)W;

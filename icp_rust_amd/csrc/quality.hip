@@ -1,17 +1,16 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 9): the quality of a pose -- fitness, inlier RMSE, the
 // reference's error / huber_error and the SE(2) information matrix at a GIVEN pose, with the handle's own exact search.
 //   k_quality_terms<DIM>  one workgroup per 256 source points: each point's terms from src, T, idx and dst, folded by the
-//                         tree of section 9 into one record per group
-//   k_quality_fold        the next level of the same tree: one workgroup per 256 records (as many launches as levels)
+//                         tree of section 9 (fold_device.hpp) into one record per group
+//   k_fold_level<6>       the next level of the same tree: one workgroup per 256 records (as many launches as levels)
 //   k_quality_batch<DIM>  one workgroup per item of icp_batch_evaluate: the item's targets in LDS, exact brute-force
 //                         nearest neighbour in f64, the same terms and the same tree (api_batch.hip drives it)
-// Nothing crosses workgroups inside a launch and no sum uses atomics: every sum is the fixed tree, so a result is a pure
-// function of the inputs, whichever kernel computed it.
+// Every sum is the fixed tree, so a result is a pure function of the inputs, whichever kernel computed it.
 #include <cmath>
 #include <cstring>
-#include <utility>
 
 #include "api_internal.hpp"
+#include "fold_device.hpp"
 #include "gn_device.hpp"
 
 using namespace icp;
@@ -19,15 +18,6 @@ using namespace icp::api;
 
 namespace icp {
 namespace {
-
-constexpr unsigned kQGroup = 256;  // values per group of the fold tree
-
-// one group of the tree in LDS (15 KB)
-struct QualityFoldLds {
-  double v[kQualitySums][kQGroup];
-  unsigned long long c[kQGroup];
-  unsigned f[kQGroup];
-};
 
 // A point's terms: the expressions of section 9 (the library is built with -ffp-contract=off: no FMA).  b is the
 // matched target; d2 is the search's distance expression, e2 its xy part.
@@ -52,53 +42,6 @@ __device__ __forceinline__ void quality_terms(double qx, double qy, double qz, d
   nan = (e2 != e2) ? 1u : 0u;
 }
 
-__device__ __forceinline__ void fold_put(QualityFoldLds &L, unsigned lane, const double v[kQualitySums],
-                                         unsigned long long c, unsigned f) {
-#pragma unroll
-  for (int k = 0; k < kQualitySums; ++k) L.v[k][lane] = v[k];
-  L.c[lane] = c;
-  L.f[lane] = f;
-}
-
-__device__ __forceinline__ void fold_put_zero(QualityFoldLds &L, unsigned lane) {
-#pragma unroll
-  for (int k = 0; k < kQualitySums; ++k) L.v[k][lane] = 0.;
-  L.c[lane] = 0;
-  L.f[lane] = 0;
-}
-
-__device__ __forceinline__ QualityPart make_part(const double v[kQualitySums], unsigned long long c, unsigned f) {
-  QualityPart p;
-#pragma unroll
-  for (int k = 0; k < kQualitySums; ++k) p.v[k] = v[k];
-  p.inliers = c;
-  p.nan = f;
-  p.pad = 0;
-  return p;
-}
-
-// The tree over one group: lanes [0, 256) hold the values (+0.0 where the group has none); g[i] += g[i + s] for
-// s = 128, 64, ..., 1.  Every thread of the workgroup calls it (barriers); afterwards lane 0 holds the group's fold.
-__device__ __forceinline__ void fold_group(QualityFoldLds &L, unsigned tid) {
-  for (unsigned s = kQGroup / 2; s > 0; s >>= 1) {
-    __syncthreads();
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < kQualitySums; ++k) L.v[k][tid] = L.v[k][tid] + L.v[k][tid + s];
-      L.c[tid] += L.c[tid + s];
-      L.f[tid] |= L.f[tid + s];
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ QualityPart fold_take(const QualityFoldLds &L) {
-  double v[kQualitySums];
-#pragma unroll
-  for (int k = 0; k < kQualitySums; ++k) v[k] = L.v[k][0];
-  return make_part(v, L.c[0], L.f[0]);
-}
-
 }  // namespace
 
 // level 1: the terms of source points [256 g, 256 g + 256), folded -> out[g].  n == 1: out[0] is the one point's terms
@@ -107,9 +50,9 @@ template <int DIM>
 __global__ __launch_bounds__(256) void k_quality_terms(const double *__restrict__ src, unsigned n, Pose T,
                                                        const uint32_t *__restrict__ idx, const double *__restrict__ dst,
                                                        unsigned m, double r2, QualityPart *__restrict__ out) {
-  __shared__ QualityFoldLds L;
+  __shared__ FoldLds<kQualitySums> L;
   const unsigned tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * kQGroup + tid;
+  const size_t i = (size_t)blockIdx.x * kFoldGroup + tid;
   double v[kQualitySums] = {0., 0., 0., 0., 0., 0.};
   unsigned in = 0, nan = 0;
   if (i < n) {
@@ -123,22 +66,10 @@ __global__ __launch_bounds__(256) void k_quality_terms(const double *__restrict_
     quality_terms<DIM>(qx, qy, pz, b[0], b[1], DIM == 3 ? b[2] : 0., r2, v, in, nan);
   }
   if (n == 1) {
-    if (tid == 0) out[0] = make_part(v, in, nan);
+    if (tid == 0) out[0] = fold_part(v, in, nan);
     return;
   }
   fold_put(L, tid, v, in, nan);
-  fold_group(L, tid);
-  if (tid == 0) out[blockIdx.x] = fold_take(L);
-}
-
-// the next level: records [256 g, 256 g + 256) of `in` (k of them), +0.0 beyond, folded -> out[g]
-__global__ __launch_bounds__(256) void k_quality_fold(const QualityPart *__restrict__ in, unsigned k,
-                                                      QualityPart *__restrict__ out) {
-  __shared__ QualityFoldLds L;
-  const unsigned tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * kQGroup + tid;
-  if (i < k) fold_put(L, tid, in[i].v, in[i].inliers, in[i].nan);
-  else fold_put_zero(L, tid);
   fold_group(L, tid);
   if (tid == 0) out[blockIdx.x] = fold_take(L);
 }
@@ -153,8 +84,8 @@ __global__ __launch_bounds__(kQualityBatchThreads) void k_quality_batch(const do
                                                                         const QualityBatchItem *__restrict__ items,
                                                                         double r2, QualityPart *__restrict__ res) {
   extern __shared__ double q_tgt[];  // x[m] | y[m] | z[m]
-  __shared__ QualityFoldLds L;
-  __shared__ QualityPart grp[kQualityMaxN / kQGroup];
+  __shared__ FoldLds<kQualitySums> L;
+  __shared__ QualityPart grp[kQualityMaxN / kFoldGroup];
   const QualityBatchItem it = items[blockIdx.x];
   const unsigned n = it.n, m = it.m, tid = threadIdx.x;
   double *tx = q_tgt, *ty = tx + m, *tz = ty + m;
@@ -191,13 +122,13 @@ __global__ __launch_bounds__(kQualityBatchThreads) void k_quality_batch(const do
     quality_terms<DIM>(qx, qy, pz, tx[bi], ty[bi], DIM == 3 ? tz[bi] : 0., r2, v, in, nan);
   }
   if (n == 1) {  // (uniform across the workgroup)
-    if (tid == 0) res[it.slot] = make_part(v, in, nan);
+    if (tid == 0) res[it.slot] = fold_part(v, in, nan);
     return;
   }
-  const unsigned groups = (n + kQGroup - 1) / kQGroup;
+  const unsigned groups = (n + kFoldGroup - 1) / kFoldGroup;
   for (unsigned g = 0; g < groups; ++g) {
-    const unsigned lane = tid - g * kQGroup;  // (wraps for the threads below the group: never < kQGroup then)
-    if (lane < kQGroup) fold_put(L, lane, v, in, nan);
+    const unsigned lane = tid - g * kFoldGroup;  // (wraps for the threads below the group: never < kFoldGroup then)
+    if (lane < kFoldGroup) fold_put(L, lane, v, in, nan);
     fold_group(L, tid);
     if (tid == 0) grp[g] = fold_take(L);
     __syncthreads();
@@ -206,7 +137,7 @@ __global__ __launch_bounds__(kQualityBatchThreads) void k_quality_batch(const do
     if (tid == 0) res[it.slot] = grp[0];
     return;
   }
-  if (tid < kQGroup) {
+  if (tid < kFoldGroup) {
     if (tid < groups) fold_put(L, tid, grp[tid].v, grp[tid].inliers, grp[tid].nan);
     else fold_put_zero(L, tid);
   }
@@ -255,50 +186,29 @@ int quality_result(size_t n, const QualityPart &p, icp_quality *q) {
 
 namespace {
 
-bool evaluate_args_ok(const icp_handle *h, const void *src, size_t n, const icp_pose *T, double max_dist,
-                      const icp_quality *out) {
-  // (max_dist >= 0 is false for a NaN)
-  return h && T && out && (n == 0 || src) && max_dist >= 0. && n < 0xffffffffull;
-}
-
 // The device part of both entries: the handle's search at T, then the terms and the tree.
 int evaluate(icp_handle *h, const double *d_src, size_t n, const Pose &T, double max_dist, icp_quality *out,
              uint32_t *d_idx) {
-  // Whatever way this call ends, nothing of it is in flight afterwards, and the search snapshot it may have taken (the
-  // cell-sorted copy estimate calls take) is dropped, as icp_estimate_device drops its own.
-  struct Quiesce {
-    icp_handle *h;
-    ~Quiesce() {
-      (void)hipStreamSynchronize(h->stream);
-      h->qsort.valid = false;
-      h->qsort.have_prev = false;
-    }
-  } quiesce_on_exit{h};
+  Quiesce quiesce_on_exit{h};
   Workspace &w = h->ws;
   // (the level records live in the residual buffers: ceil(n / 256) records of 8 doubles fit in max(n, 256) doubles)
-  HIP_TRY(ensure_workspace(h, n < kQGroup ? kQGroup : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   uint32_t *idx = d_idx ? d_idx : w.d_idx;
   ICP_TRY_RC(icp_prepare_source_device(h, d_src, n, &T));
   ICP_TRY_RC(icp_correspond_device(h, d_src, n, &T, w.d_a, w.d_b, idx));
   const double r2 = max_dist * max_dist;
-  unsigned k = (unsigned)((n + kQGroup - 1) / kQGroup);
+  const unsigned k = (unsigned)((n + kFoldGroup - 1) / kFoldGroup);
   QualityPart *cur = reinterpret_cast<QualityPart *>(w.d_rx), *nxt = reinterpret_cast<QualityPart *>(w.d_ry);
   if (h->dim == 2)
-    hipLaunchKernelGGL(k_quality_terms<2>, dim3(k), dim3(kQGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
+    hipLaunchKernelGGL(k_quality_terms<2>, dim3(k), dim3(kFoldGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
                        (unsigned)h->m, r2, cur);
   else
-    hipLaunchKernelGGL(k_quality_terms<3>, dim3(k), dim3(kQGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
+    hipLaunchKernelGGL(k_quality_terms<3>, dim3(k), dim3(kFoldGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
                        (unsigned)h->m, r2, cur);
   HIP_TRY(hipGetLastError());
-  while (k > 1) {
-    const unsigned k2 = (k + kQGroup - 1) / kQGroup;
-    hipLaunchKernelGGL(k_quality_fold, dim3(k2), dim3(kQGroup), 0, h->stream, cur, k, nxt);
-    HIP_TRY(hipGetLastError());
-    std::swap(cur, nxt);
-    k = k2;
-  }
-  QualityPart r;
-  HIP_TRY(hipMemcpyAsync(&r, cur, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+  QualityPart r, *root;
+  HIP_TRY(fold_levels(cur, nxt, k, h->stream, &root));
+  HIP_TRY(hipMemcpyAsync(&r, root, sizeof(r), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return quality_result(n, r, out);
 }
@@ -307,7 +217,7 @@ int evaluate(icp_handle *h, const double *d_src, size_t n, const Pose &T, double
 
 extern "C" int icp_evaluate_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, double max_dist,
                                    icp_quality *out, uint32_t *d_idx) {
-  if (!evaluate_args_ok(h, d_src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, d_src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
   quality_clear(n, out);
   if (n == 0) return ICP_OK;
   if (h->m == 0) return ICP_EMPTY_DST;  // index.unwrap() on an empty tree, src/lib.rs:122,165
@@ -317,12 +227,12 @@ extern "C" int icp_evaluate_device(icp_handle *h, const double *d_src, size_t n,
 
 extern "C" int icp_evaluate(icp_handle *h, const double *src, size_t n, const icp_pose *T, double max_dist,
                             icp_quality *out, uint32_t *idx) {
-  if (!evaluate_args_ok(h, src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
   quality_clear(n, out);
   if (n == 0) return ICP_OK;
   if (h->m == 0) return ICP_EMPTY_DST;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < kQGroup ? kQGroup : n, true));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), true));
   HIP_TRY(hipMemcpyAsync(h->ws.d_src, src, n * h->dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
   const int rc = evaluate(h, h->ws.d_src, n, *T, max_dist, out, h->ws.d_idx);
   if ((rc == ICP_OK || rc == ICP_NAN_INPUT) && idx) {  // (the search ran: its correspondences are there either way)

@@ -4,15 +4,14 @@
 // at a GIVEN pose, with the handle's own exact search and its normals.
 //   k_plane_quality_terms  one workgroup per 256 source points: a lane gathers src[i], idx[i], dst[j], nrm[j] once
 //                          (76 B), forms the ten terms of section 13, and the group folds them by the tree of section 9
-//                          into one 96-byte record
-//   k_plane_quality_fold   the next level of the same tree: one workgroup per 256 records (as many launches as levels)
-// Nothing crosses workgroups inside a launch and no sum uses atomics: every sum is the fixed tree, so a result is a pure
-// function of the inputs.  quality.hip (section 9) and its QualityPart are left as they are: this file has its own record.
+//                          (fold_device.hpp) into one 96-byte record
+//   k_fold_level<10>       the next level of the same tree: one workgroup per 256 records (as many launches as levels)
+// Every sum is the fixed tree, so a result is a pure function of the inputs.
 #include <cmath>
 #include <cstring>
-#include <utility>
 
 #include "api_internal.hpp"
+#include "fold_device.hpp"
 #include "gn_device.hpp"
 
 using namespace icp;
@@ -21,71 +20,9 @@ using namespace icp::api;
 namespace icp {
 namespace {
 
-constexpr unsigned kPQGroup = 256;  // values per group of the fold tree
-constexpr int kPlaneSums = 10;      // S_d2, S_p2, E, H, Ixx, Ixy, Iyy, Ixt, Iyt, Itt
-
-// a record of the tree: 96 bytes
-struct PlaneQualityPart {
-  double v[kPlaneSums];
-  unsigned long long inliers;
-  unsigned nan, pad;
-};
+constexpr int kPlaneSums = 10;  // S_d2, S_p2, E, H, Ixx, Ixy, Iyy, Ixt, Iyt, Itt
+using PlaneQualityPart = FoldPart<kPlaneSums>;
 static_assert(sizeof(PlaneQualityPart) == 96, "twelve doubles per record: ceil(n / 256) of them fit in max(n, 256)");
-
-// one group of the tree in LDS (23 552 bytes: below the 64 KB every kernel has without a grant)
-struct PlaneFoldLds {
-  double v[kPlaneSums][kPQGroup];
-  unsigned long long c[kPQGroup];
-  unsigned f[kPQGroup];
-};
-
-__device__ __forceinline__ void pq_put(PlaneFoldLds &L, unsigned lane, const double v[kPlaneSums], unsigned long long c,
-                                       unsigned f) {
-#pragma unroll
-  for (int k = 0; k < kPlaneSums; ++k) L.v[k][lane] = v[k];
-  L.c[lane] = c;
-  L.f[lane] = f;
-}
-
-__device__ __forceinline__ void pq_put_zero(PlaneFoldLds &L, unsigned lane) {
-#pragma unroll
-  for (int k = 0; k < kPlaneSums; ++k) L.v[k][lane] = 0.;
-  L.c[lane] = 0;
-  L.f[lane] = 0;
-}
-
-__device__ __forceinline__ PlaneQualityPart pq_part(const double v[kPlaneSums], unsigned long long c, unsigned f) {
-  PlaneQualityPart p;
-#pragma unroll
-  for (int k = 0; k < kPlaneSums; ++k) p.v[k] = v[k];
-  p.inliers = c;
-  p.nan = f;
-  p.pad = 0;
-  return p;
-}
-
-// The tree over one group (section 9's fold): lanes [0, 256) hold the values (+0.0 where the group has none);
-// g[i] += g[i + s] for s = 128, 64, ..., 1.  Every thread of the workgroup calls it (barriers); afterwards lane 0 holds
-// the group's fold.
-__device__ __forceinline__ void pq_fold_group(PlaneFoldLds &L, unsigned tid) {
-  for (unsigned s = kPQGroup / 2; s > 0; s >>= 1) {
-    __syncthreads();
-    if (tid < s) {
-#pragma unroll
-      for (int k = 0; k < kPlaneSums; ++k) L.v[k][tid] = L.v[k][tid] + L.v[k][tid + s];
-      L.c[tid] += L.c[tid + s];
-      L.f[tid] |= L.f[tid + s];
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ PlaneQualityPart pq_take(const PlaneFoldLds &L) {
-  double v[kPlaneSums];
-#pragma unroll
-  for (int k = 0; k < kPlaneSums; ++k) v[k] = L.v[k][0];
-  return pq_part(v, L.c[0], L.f[0]);
-}
 
 }  // namespace
 
@@ -97,9 +34,9 @@ __global__ __launch_bounds__(256) void k_plane_quality_terms(const double *__res
                                                              const double *__restrict__ dst,
                                                              const double *__restrict__ nrm, unsigned m, double r2,
                                                              PlaneQualityPart *__restrict__ out) {
-  __shared__ PlaneFoldLds L;
+  __shared__ FoldLds<kPlaneSums> L;
   const unsigned tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * kPQGroup + tid;
+  const size_t i = (size_t)blockIdx.x * kFoldGroup + tid;
   double v[kPlaneSums] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
   unsigned in = 0, nan = 0;
   if (i < n) {
@@ -130,24 +67,12 @@ __global__ __launch_bounds__(256) void k_plane_quality_terms(const double *__res
     nan = (p2 != p2) ? 1u : 0u;
   }
   if (n == 1) {
-    if (tid == 0) out[0] = pq_part(v, in, nan);
+    if (tid == 0) out[0] = fold_part(v, in, nan);
     return;
   }
-  pq_put(L, tid, v, in, nan);
-  pq_fold_group(L, tid);
-  if (tid == 0) out[blockIdx.x] = pq_take(L);
-}
-
-// the next level: records [256 g, 256 g + 256) of `in` (k of them), +0.0 beyond, folded -> out[g]
-__global__ __launch_bounds__(256) void k_plane_quality_fold(const PlaneQualityPart *__restrict__ in, unsigned k,
-                                                            PlaneQualityPart *__restrict__ out) {
-  __shared__ PlaneFoldLds L;
-  const unsigned tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * kPQGroup + tid;
-  if (i < k) pq_put(L, tid, in[i].v, in[i].inliers, in[i].nan);
-  else pq_put_zero(L, tid);
-  pq_fold_group(L, tid);
-  if (tid == 0) out[blockIdx.x] = pq_take(L);
+  fold_put(L, tid, v, in, nan);
+  fold_group(L, tid);
+  if (tid == 0) out[blockIdx.x] = fold_take(L);
 }
 
 }  // namespace icp
@@ -185,24 +110,13 @@ int plane_quality_result(size_t n, const PlaneQualityPart &p, icp_plane_quality 
   return ICP_OK;
 }
 
-// (max_dist >= 0 is false for a NaN)
-bool plane_evaluate_args_ok(const icp_handle *h, const void *src, size_t n, const icp_pose *T, double max_dist,
-                            const icp_plane_quality *out) {
-  return h && T && out && (n == 0 || src) && max_dist >= 0. && n < 0xffffffffull;
-}
-
-bool have_device() {
-  int count = 0;
-  return hipGetDeviceCount(&count) == hipSuccess && count > 0;
-}
-
 // What both entries decide before any work, in the order section 13 gives: the arguments, n == 0, the device, and only
 // then the handle.  *done: the status is final.
 int plane_evaluate_enter(icp_handle *h, const void *src, size_t n, const icp_pose *T, double max_dist,
                          icp_plane_quality *out, bool *done) {
   *done = true;
   if (out) plane_quality_clear(n, out);
-  if (!plane_evaluate_args_ok(h, src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
+  if (!sized_args_ok(h, src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
   if (n == 0) return ICP_OK;
   if (!have_device()) return ICP_NO_DEVICE;
   if (h->dim != 3 || h->normals_m != h->m) return ICP_BAD_ARGUMENT;  // icp_compute_target_normals first (again after an append)
@@ -214,37 +128,22 @@ int plane_evaluate_enter(icp_handle *h, const void *src, size_t n, const icp_pos
 // The device part of both entries: the handle's search at T, then the terms and the tree.
 int plane_evaluate(icp_handle *h, const double *d_src, size_t n, const Pose &T, double max_dist, icp_plane_quality *out,
                    uint32_t *d_idx) {
-  // Whatever way this call ends, nothing of it is in flight afterwards, and the search snapshot it may have taken (the
-  // cell-sorted copy estimate calls take) is dropped, as icp_evaluate_device drops its own.
-  struct Quiesce {
-    icp_handle *h;
-    ~Quiesce() {
-      (void)hipStreamSynchronize(h->stream);
-      h->qsort.valid = false;
-      h->qsort.have_prev = false;
-    }
-  } quiesce_on_exit{h};
+  Quiesce quiesce_on_exit{h};
   Workspace &w = h->ws;
   // (the level records live in the residual buffers: ceil(n / 256) records of 12 doubles fit in max(n, 256) doubles)
-  HIP_TRY(ensure_workspace(h, n < kPQGroup ? kPQGroup : n, false));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
   uint32_t *idx = d_idx ? d_idx : w.d_idx;
   ICP_TRY_RC(icp_prepare_source_device(h, d_src, n, &T));
   ICP_TRY_RC(icp_correspond_device(h, d_src, n, &T, nullptr, nullptr, idx));  // exact 3-D NN
   const double r2 = max_dist * max_dist;
-  unsigned k = (unsigned)((n + kPQGroup - 1) / kPQGroup);
+  const unsigned k = (unsigned)((n + kFoldGroup - 1) / kFoldGroup);
   PlaneQualityPart *cur = reinterpret_cast<PlaneQualityPart *>(w.d_rx), *nxt = reinterpret_cast<PlaneQualityPart *>(w.d_ry);
-  hipLaunchKernelGGL(k_plane_quality_terms, dim3(k), dim3(kPQGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
+  hipLaunchKernelGGL(k_plane_quality_terms, dim3(k), dim3(kFoldGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
                      (const double *)h->d_normals, (unsigned)h->m, r2, cur);
   HIP_TRY(hipGetLastError());
-  while (k > 1) {
-    const unsigned k2 = (k + kPQGroup - 1) / kPQGroup;
-    hipLaunchKernelGGL(k_plane_quality_fold, dim3(k2), dim3(kPQGroup), 0, h->stream, cur, k, nxt);
-    HIP_TRY(hipGetLastError());
-    std::swap(cur, nxt);
-    k = k2;
-  }
-  PlaneQualityPart r;
-  HIP_TRY(hipMemcpyAsync(&r, cur, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+  PlaneQualityPart r, *root;
+  HIP_TRY(fold_levels(cur, nxt, k, h->stream, &root));
+  HIP_TRY(hipMemcpyAsync(&r, root, sizeof(r), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return plane_quality_result(n, r, out);
 }
@@ -266,7 +165,7 @@ extern "C" int icp_evaluate_point_to_plane(icp_handle *h, const double *src, siz
   const int erc = plane_evaluate_enter(h, src, n, T, max_dist, out, &done);
   if (done) return erc;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n < kPQGroup ? kPQGroup : n, true));
+  HIP_TRY(ensure_workspace(h, workspace_points(n), true));
   HIP_TRY(hipMemcpyAsync(h->ws.d_src, src, n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   const int rc = plane_evaluate(h, h->ws.d_src, n, *T, max_dist, out, h->ws.d_idx);
   if ((rc == ICP_OK || rc == ICP_NAN_INPUT) && idx) {  // (the search ran: its correspondences are there either way)

@@ -199,7 +199,7 @@ def test_crop_kernels_do_not_spill_and_leave_room_for_four_waves_per_simd():
 
     regs = _usage("crop.hip")
     kernels = [k for k in regs if not k.endswith("#scratch")]
-    for frag in ("k_crop_markILi2E", "k_crop_markILi3E", "k_crop_chunks", "k_crop_placeILi2E", "k_crop_placeILi3E",
+    for frag in ("k_crop_markILi2E", "k_crop_markILi3E", "k_compact_chunks", "k_crop_placeILi2E", "k_crop_placeILi3E",
                  "k_crop_rec_mark", "k_crop_rec_place", "k_crop_starts"):
         assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
     assert len(kernels) == 8, kernels

@@ -173,7 +173,7 @@ def test_gate_kernels_do_not_spill_and_leave_room_for_four_waves_per_simd():
 
     regs = _usage("gate.hip")
     kernels = [k for k in regs if not k.endswith("#scratch")]
-    for frag in ("k_gate_stageILi2E", "k_gate_stageILi3E", "k_gate_chunks", "k_gate_place"):
+    for frag in ("k_gate_stageILi2E", "k_gate_stageILi3E", "k_compact_chunks", "k_gate_place"):
         assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
     for k in kernels:
         assert regs.get(k + "#scratch", 0) == 0, (k, regs.get(k + "#scratch"))

@@ -168,7 +168,7 @@ def test_plane_gate_kernels_do_not_spill_and_leave_room_for_four_waves_per_simd(
 
     regs = _usage("gate_plane.hip")
     kernels = [k for k in regs if not k.endswith("#scratch")]
-    for frag in ("k_plgate_stage", "k_plgate_chunks", "k_plgate_place"):
+    for frag in ("k_plgate_stage", "k_compact_chunks", "k_plgate_place"):
         assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
     assert len(kernels) == 3, kernels
     for k in kernels:

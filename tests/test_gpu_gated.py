@@ -338,6 +338,47 @@ def test_stage_call_against_flatnonzero(dim, n):
     assert len(_gate(icp, np.ascontiguousarray(patterns["none"]), dst, INF)) == n
 
 
+def test_stage_call_on_the_chunk_sum_path():
+    """the smallest n whose last tile has a whole chunk of tiles (8 192 tiles of 1 024 points) and one more tile in front
+    of it: 2^23 + 1025 -- the chunk-sum launch runs and the last tile adds a chunk sum and a tile count.  d_idx is given
+    (no search runs); count, positions and both pair arrays are checked exactly, and nothing is written behind them."""
+    import torch
+
+    m, block = 512, 4096
+    n = (1 << 23) + 1025
+    rng = np.random.default_rng(3)
+    dst = rng.uniform(1.0, 10.0, size=(m, 2))
+    icp = I.Icp2d(dst)
+    # the keep pattern divides neither 2^23 + 1025 nor the tile into equal survivor counts: 1 keep in 3, then 2 in 5
+    keep_block = (np.arange(block) % 3 == 0) | (np.arange(block) % 5 == 1)
+    off = np.where(keep_block, 0.001, 1.0)
+    tile = dst[np.arange(block) % m] + np.stack([off, np.zeros(block)], 1)
+    reps = -(-n // block)
+    d_src = torch.from_numpy(np.ascontiguousarray(tile)).cuda().repeat(reps, 1)[:n].contiguous()
+    # idx = arange % m, and the block is a multiple of m: the partner of point i is dst[i % m]
+    assert block % m == 0
+    d_idx = (torch.arange(n, dtype=torch.int64, device="cuda") % m).to(torch.int32)
+    d_a = torch.full((n, 2), -7.0, dtype=torch.float64, device="cuda")
+    d_b = torch.full((n, 2), -7.0, dtype=torch.float64, device="cuda")
+    d_kept = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    r = 0.01
+    kept = icp.gate_pairs_device(d_src, I.Transform(), d_idx, r, d_a, d_b, d_kept)
+    want = torch.from_numpy(np.tile(keep_block, reps)[:n]).cuda().nonzero().flatten()
+    # the kernel's operations at the identity pose (q = (1 p_x + 0 p_y) + 0 = p exactly: every coordinate is >= 1)
+    b_all = torch.from_numpy(dst).cuda()[d_idx.long()]
+    e = d_src - b_all
+    d2 = e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]
+    assert torch.equal((d2 <= r * r).nonzero().flatten(), want)  # (the pattern is what the rule keeps)
+    assert kept == want.shape[0], (kept, want.shape[0])
+    assert torch.equal(d_kept[:kept], want.to(torch.int32))
+    assert torch.equal(d_a[:kept].view(torch.int64), d_src[want].view(torch.int64))
+    assert torch.equal(d_b[:kept].view(torch.int64), b_all[want].view(torch.int64))
+    assert bool((d_a[kept:] == -7.0).all()) and bool((d_b[kept:] == -7.0).all())  # nothing behind the survivors
+    assert bool((d_kept[kept:] == -1).all())
+    del d_a, d_b, d_kept, d_src, d_idx, want, b_all, e, d2
+    torch.cuda.empty_cache()
+
+
 def test_stage_call_drops_a_nan_source_point():
     rng = np.random.default_rng(2)
     dst = rng.uniform(-10.0, 10.0, size=(9000, 3))

@@ -250,7 +250,7 @@ def test_plane_quality_kernels_do_not_spill_and_leave_room_for_four_waves_per_si
 
     regs = _usage("quality_plane.hip")
     kernels = [k for k in regs if not k.endswith("#scratch")]
-    for frag in ("k_plane_quality_terms", "k_plane_quality_fold"):
+    for frag in ("k_plane_quality_terms", "k_fold_levelILi10E"):
         assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
     assert len(kernels) == 2, kernels
     for k in kernels:

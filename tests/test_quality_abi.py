@@ -180,7 +180,7 @@ def test_quality_kernels_do_not_spill_and_fit_a_cu():
     from test_registers import BUDGET
 
     regs = _usage("quality.hip")
-    threads = {"k_quality_termsILi2E": 256, "k_quality_termsILi3E": 256, "k_quality_fold": 256,
+    threads = {"k_quality_termsILi2E": 256, "k_quality_termsILi3E": 256, "k_fold_levelILi6E": 256,
                "k_quality_batchILi2E": 1024, "k_quality_batchILi3E": 1024}
     for frag, b in threads.items():
         names = [k for k in regs if frag in k and not k.endswith("#scratch")]
