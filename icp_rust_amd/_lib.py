@@ -219,6 +219,13 @@ SIGNATURES = {
     "icp_grid_crop_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_evaluate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_evaluate_point_to_plane_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
+    "icp_compute_target_line_normals": (C.c_int, [_vp, C.c_int]),
+    "icp_update_target_line_normals": (C.c_int, [_vp, C.c_int]),
+    "icp_read_target_line_normals": (C.c_int, [_vp, _sz, _sz, _vp]),
+    "icp_estimate_point_to_line": (C.c_int, [_vp, _vp, _sz, _pp, _sz, _pp, _vp, _vp]),
+    "icp_estimate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, _pp, _vp, _vp]),
+    "icp_estimate_point_to_line_gated": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
+    "icp_estimate_point_to_line_gated_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -860,6 +860,70 @@ class _Icp:
                                                 C.byref(kept)), "icp_gate_plane_pairs_device")
         return int(kept.value)
 
+    # -- EXTENSION (not in the reference): point-to-line residuals for 2-D handles, include/icp_mi355x.h section 14 --
+    def _need_2d(self, what):
+        if self.DIM != 2:
+            raise ValueError(f"{what} needs a 2-D handle (Icp2d); a 3-D handle registers with compute_normals() / "
+                             "estimate_point_to_plane()")
+
+    def compute_line_normals(self, k=10):
+        """Unit line normals of the target points from their k nearest targets (2-D handles)."""
+        self._need_2d("compute_line_normals")
+        check(lib().icp_compute_target_line_normals(self._h, int(k)), "icp_compute_target_line_normals")
+
+    def update_line_normals(self, k=10):
+        """Line normals for the targets appended since compute_line_normals / update_line_normals (from the cloud as
+        it is now); the older targets keep theirs."""
+        self._need_2d("update_line_normals")
+        check(lib().icp_update_target_line_normals(self._h, int(k)), "icp_update_target_line_normals")
+
+    def read_line_normals(self, first=0, count=None):
+        self._need_2d("read_line_normals")
+        count = self.target_count - first if count is None else count
+        out = np.empty((count, 2), dtype=np.float64)
+        check(lib().icp_read_target_line_normals(self._h, first, count, C.c_void_p(out.ctypes.data)),
+              "icp_read_target_line_normals")
+        return out
+
+    def estimate_point_to_line(self, src, initial_transform, max_iter, return_info=False,
+                               max_correspondence_distance=None):
+        """Icp2d::estimate with the residual n_q . (T p - q), n_q the line normal of the matched target (extension;
+        needs compute_line_normals()).  Returns what estimate_point_to_plane returns: the Transform, with
+        return_info=True (T, idx, inner).
+
+        `max_correspondence_distance=r`: the inner loop of each outer iteration sees only the pairs whose nearest
+        target lies within r of the moved source point (d2 <= r * r), in the caller's order; `return_info` then returns
+        (T, idx, inner, inliers).  None: the ungated call."""
+        self._need_2d("estimate_point_to_line")
+        gated = max_correspondence_distance is not None
+        r = float(max_correspondence_distance) if gated else 0.0
+        if gated and not r >= 0.0:  # (also a NaN)
+            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
+        o = Transform()
+        inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        inl = np.zeros(max(max_iter, 1), dtype=np.uint32)
+        on_device = _is_device_tensor(src)
+        if on_device:
+            import torch
+
+            self._dev(src, "src")
+            n = src.shape[0]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_info else None
+            sp, ip = C.c_void_p(src.data_ptr()), (C.c_void_p(idx.data_ptr()) if return_info else None)
+        else:
+            s = _host(src, self.DIM)
+            n = s.shape[0]
+            idx = np.zeros(max(n, 1), dtype=np.uint32)
+            sp, ip = _ptr(s), C.c_void_p(idx.ctypes.data)
+        name = "icp_estimate_point_to_line" + ("_gated" if gated else "") + ("_device" if on_device else "")
+        args = [self._h, sp, n, C.byref(initial_transform.pose), max_iter] + ([r] if gated else [])
+        args += [C.byref(o.pose), ip, C.c_void_p(inner.ctypes.data)] + ([C.c_void_p(inl.ctypes.data)] if gated else [])
+        check(getattr(lib(), name)(*args), name)
+        if not return_info:
+            return o
+        idx = idx[:n].cpu().numpy().view(np.uint32) if on_device else idx[:n]
+        return (o, idx, inner[:max_iter], inl[:max_iter]) if gated else (o, idx, inner[:max_iter])
+
     def profile_enable(self, every=1):
         """Time every `every`-th NN search launch with HIP events (0 / False: off)."""
         check(lib().icp_profile_enable(self._h, int(every)), "icp_profile_enable")

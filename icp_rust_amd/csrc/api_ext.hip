@@ -169,24 +169,25 @@ extern "C" int icp_read_targets(icp_handle *h, size_t first, size_t k, double *o
 // Not in the reference (no normals anywhere in src/); definition and CPU restatement: p2plane.hip,
 // the CPU checker under tests (tests/test_p2plane.py).  Everything around the residual is the reference's: exact 3-D
 // nearest neighbour, SE(2) pose on xy, Huber / MAD Gauss-Newton, the inner loop's break tests.
-extern "C" int icp_compute_target_normals(icp_handle *h, int k) {
-  if (!h || h->dim != 3 || k < 3 || k > 16) return ICP_BAD_ARGUMENT;
+namespace icp {
+namespace api {
+
+// What icp_compute_target_normals and icp_compute_target_line_normals (api_line.hip) share once each has decided on the
+// handle's dimension: `launch` is the normals kernel of that dimension.  The normals are m x 3 either way.
+int compute_normals_with(icp_handle *h, int k, NormalsLaunch launch) {
   if (h->m == 0) return ICP_EMPTY_DST;
   if (!h->grid.built) return ICP_BAD_ARGUMENT;  // non-finite targets: no grid to search neighbourhoods with
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(reserve(h->d_normals, h->cap_normals, h->m * 3));
-  HIP_TRY(launch_target_normals(h, k, h->d_normals));
+  HIP_TRY(launch(h, k, h->d_normals, 0));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->normals_m = h->m;
   h->normals_k = k;
   return ICP_OK;
 }
 
-// The targets appended since the normals were last computed get theirs (from their k nearest targets in the cloud
-// as it is NOW); the older targets keep the normals they have -- "normals at insertion time", the definition a map that
-// grows frame by frame uses (a full icp_compute_target_normals re-derives all of them from the current cloud).
-extern "C" int icp_update_target_normals(icp_handle *h, int k) {
-  if (!h || h->dim != 3 || k < 3 || k > 16) return ICP_BAD_ARGUMENT;
+// ... and the two update entries: the targets behind normals_m get theirs, the older ones keep what they have
+int update_normals_with(icp_handle *h, int k, NormalsLaunch launch) {
   if (h->m == 0) return ICP_EMPTY_DST;
   if (!h->grid.built || h->normals_m > h->m) return ICP_BAD_ARGUMENT;
   if (h->normals_m > 0 && h->normals_k != k) return ICP_BAD_ARGUMENT;  // one neighbourhood size per cloud
@@ -206,11 +207,27 @@ extern "C" int icp_update_target_normals(icp_handle *h, int k) {
       return map_hip(e);
     }
   }
-  HIP_TRY(launch_target_normals(h, k, h->d_normals, h->normals_m));
+  HIP_TRY(launch(h, k, h->d_normals, h->normals_m));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->normals_m = h->m;
   h->normals_k = k;
   return ICP_OK;
+}
+
+}  // namespace api
+}  // namespace icp
+
+extern "C" int icp_compute_target_normals(icp_handle *h, int k) {
+  if (!h || h->dim != 3 || k < 3 || k > 16) return ICP_BAD_ARGUMENT;
+  return compute_normals_with(h, k, launch_target_normals);
+}
+
+// The targets appended since the normals were last computed get theirs (from their k nearest targets in the cloud
+// as it is NOW); the older targets keep the normals they have -- "normals at insertion time", the definition a map that
+// grows frame by frame uses (a full icp_compute_target_normals re-derives all of them from the current cloud).
+extern "C" int icp_update_target_normals(icp_handle *h, int k) {
+  if (!h || h->dim != 3 || k < 3 || k > 16) return ICP_BAD_ARGUMENT;
+  return update_normals_with(h, k, launch_target_normals);
 }
 
 extern "C" int icp_read_target_normals(icp_handle *h, size_t first, size_t count, double *out) {

@@ -99,6 +99,14 @@ size_t gate_count(const icp_handle *h);
 // Needs ensure_workspace(max(n, 256)), ensure_plane_stage(n) and current normals.
 hipError_t launch_gate_plane(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
                              void *d_pairs, uint32_t *d_kept);
+// ... of a point-to-line registration on a 2-D handle (p2line.hip): the same, the clouds read at a stride of 2
+hipError_t launch_gate_line(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
+                            void *d_pairs, uint32_t *d_kept);
+// compute / update the targets' normals with the normals kernel of the handle's dimension (api_ext.hip; the callers
+// have checked h, k and the dimension)
+using NormalsLaunch = hipError_t (*)(icp_handle *h, int k, double *d_normals, size_t first);
+int compute_normals_with(icp_handle *h, int k, NormalsLaunch launch);
+int update_normals_with(icp_handle *h, int k, NormalsLaunch launch);
 // the per-pair scratch of a point-to-plane inner loop, and the staging buffer of its gate (api_ext.hip)
 int ensure_plane_buffers(icp_handle *h, size_t n);
 int ensure_plane_stage(icp_handle *h, size_t n);

@@ -652,6 +652,10 @@ hipError_t multi_put_pairs(hipStream_t s, const double *a_loc, const double *b_l
 hipError_t launch_target_normals(icp_handle *h, int k, double *d_normals, size_t first = 0);
 hipError_t launch_p2pl_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
                               const double *d_normals, void *d_pairs);
+// ... and their 2-D twins (p2line.hip): line normals (stored m x 3 with nz = +0.0) and the pairs with dz = nz = 0
+hipError_t launch_line_normals(icp_handle *h, int k, double *d_normals, size_t first);
+hipError_t launch_line_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
+                              const double *d_normals, void *d_pairs);
 hipError_t launch_p2pl_eval(icp_handle *h, const void *d_pairs, size_t n, const Pose &T, double *d_fa, double *d_fb);
 size_t p2pl_pair_bytes();
 // unweighted accumulation (gauss_newton_update / error / huber_error)

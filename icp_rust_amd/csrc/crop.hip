@@ -228,7 +228,7 @@ int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *n
     return ICP_OK;
   }
   // ---- out of place: the kept points (and normals) into the second buffers ----
-  const bool with_normals = dim == 3 && h->d_normals && h->normals_m > 0;
+  const bool with_normals = h->d_normals && h->normals_m > 0;  // (a 2-D handle's line normals are m x 3 too)
   const unsigned normals_m = with_normals ? (unsigned)h->normals_m : 0u;
   if (kept > 0) {
     HIP_TRY(reserve(h->d_dst_alt, h->cap_dst_alt, (size_t)kept * dim));
@@ -241,9 +241,9 @@ int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *n
                          normals_m, m_old, w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt,
                          with_normals && kept > 0 ? h->d_normals_alt : nullptr, count_normals ? aux : nullptr);
     else
-      hipLaunchKernelGGL(k_crop_place<2>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, (const double *)nullptr, 0u, m_old,
-                         w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt, (double *)nullptr,
-                         (uint32_t *)nullptr);
+      hipLaunchKernelGGL(k_crop_place<2>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, (const double *)h->d_normals,
+                         normals_m, m_old, w, (const uint32_t *)cnt, (const uint32_t *)sums, h->d_dst_alt,
+                         with_normals && kept > 0 ? h->d_normals_alt : nullptr, count_normals ? aux : nullptr);
     HIP_TRY(hipGetLastError());
   }
   size_t normals_after = with_normals ? kept : 0;

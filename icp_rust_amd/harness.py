@@ -14,12 +14,15 @@ from .scans import PacketFile, load_scan2d, write_packets
 from .synth import PACKETS_PER_FRAME, remove_invalid_values
 
 
-def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None):
+def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None, point_to_line=None):
     """examples/scan2d.rs:62-115.  `index` starts at 0 and is incremented BEFORE use, so
     000.txt is never read and 001.txt is the fixed source (:63,69-77); every later frame k
     loads dst = k.txt, builds Icp2d::new(&dst) and estimates warm-started from the previous
     frame (:85-88); the plotted pose is transform.inverse() (:90) and its translation is
     appended to the path (:105).  The loop ends at the first missing file (:72).
+    `point_to_line=k` (EXTENSION, not in the reference; include/icp_mi355x.h section 14): every frame's handle computes
+    the line normals of its targets from their k nearest (compute_line_normals(k)) and registers with the point-to-line
+    residual (estimate_point_to_line) instead; None calls exactly what it always called.
     Returns (transforms, inverse_transforms, path_xy)."""
     icp_factory = icp_factory or Icp2d
     index = 0
@@ -36,7 +39,11 @@ def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None):
             continue
         dst = load_scan2d(filename)
         icp = icp_factory(dst)
-        transform = icp.estimate(src, transform, max_iter)
+        if point_to_line:
+            icp.compute_line_normals(point_to_line)
+            transform = icp.estimate_point_to_line(src, transform, max_iter)
+        else:
+            transform = icp.estimate(src, transform, max_iter)
         inv = transform.inverse()
         transforms.append(transform)
         inverses.append(inv)
@@ -192,13 +199,15 @@ def main(argv=None):
     ap.add_argument("--max-iter", type=int, default=20)
     ap.add_argument("--point-to-plane", type=int, default=0, metavar="K",
                     help="scan2map: register with point-to-plane residuals, normals from K nearest map points (extension)")
+    ap.add_argument("--point-to-line", type=int, default=0, metavar="K",
+                    help="scan2d: register with point-to-line residuals, line normals from K nearest targets (extension)")
     ap.add_argument("--map-radius", type=float, default=None, metavar="R",
                     help="scan2map: keep the map within R of the registered position (sliding window, extension)")
     args = ap.parse_args(argv)
     if args.loop == "scan2d":
         if not args.scan_dir:
             ap.error("scan2d needs the scan directory")
-        _, _, path = run_scan2d(args.scan_dir, max_iter=args.max_iter)
+        _, _, path = run_scan2d(args.scan_dir, max_iter=args.max_iter, point_to_line=args.point_to_line or None)
     elif args.loop == "write-synth":
         if not args.scan_dir:
             ap.error("write-synth needs the output file")

@@ -64,7 +64,8 @@ extern "C" {
  * detectable by symbol; so was section 10 (icp_estimate_gated*, icp_gate_pairs_device); so was section 11
  * (icp_crop_targets, icp_multi_crop_targets; icp_grid_crop_counters in icp_mi355x_debug.h); so was section 12
  * (icp_estimate_point_to_plane_gated*, icp_gate_plane_pairs_device, icp_multi_estimate_point_to_plane_gated); so was
- * section 13 (icp_plane_quality, icp_evaluate_point_to_plane*) */
+ * section 13 (icp_plane_quality, icp_evaluate_point_to_plane*); so was section 14 (icp_*_target_line_normals,
+ * icp_estimate_point_to_line*) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -787,6 +788,62 @@ int icp_evaluate_point_to_plane(icp_handle *h, const double *src, size_t n, cons
                                 icp_plane_quality *out, uint32_t *idx);
 int icp_evaluate_point_to_plane_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, double max_dist,
                                        icp_plane_quality *out, uint32_t *d_idx);
+
+/* ================================================================================
+ * 14. EXTENSION (not in the reference): point-to-line registration for 2-D handles
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  The planar counterpart of sections 7 and 12
+ * ("PLICP"): a 2-D scan and its target sample the same walls at different places, so nearest-neighbour pairs differ
+ * ALONG the wall by up to the sample spacing; the line residual does not see that, the point residual does.  Lifting
+ * a scan to z = 0 and calling section 7 does not give it: the covariance of coplanar neighbours has its smallest
+ * eigenvector along z, every normal is (0, 0, 1) and every residual nz dz = 0.  Every entry is for dim == 2 handles
+ * only (ICP_BAD_ARGUMENT on a 3-D handle); sections 7, 12 and 13 keep refusing a 2-D handle.  The reference has no
+ * such thing: no parity claim; DESIGN.md section 9i restates the definition.
+ *
+ * The line normal of a target q (section 7's definition with the third coordinate removed; no FMA anywhere):
+ *   neighbourhood  the k targets nearest to q in the xy plane, q itself included, ordered by (d2, index) with
+ *                  d2 = dx dx + dy dy; 3 <= k <= 16, k clamped to the number of targets
+ *   mean, a        mean[d] = (sum over the neighbours in that order) / count; a[r][s] += e[r] e[s] with e = p - mean, in
+ *                  that order: the 2 x 2 covariance (unnormalised)
+ *   eigenvector    one Jacobi rotation of the pair (0, 1) -- theta = (a11 - a00) / (2 a01),
+ *                  t = sign(theta) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c; A <- A J,
+ *                  A <- J^T A, V <- V J -- skipped when a01 == 0; the column of the smaller diagonal, a tie: column 0
+ *   normalisation  by sqrt(n0 n0 + n1 n1); sign: the first non-zero of (n_y, n_x) is positive
+ *   degenerate     fewer than 3 neighbours, or zero length: the zero vector
+ * icp_compute_target_line_normals computes all of them through the target grid; icp_update_target_line_normals gives
+ * one to the targets appended since (from the cloud as it is now; the older targets keep theirs bit for bit; the same
+ * k as before, ICP_BAD_ARGUMENT otherwise); icp_read_target_line_normals copies count x 2 doubles out.  As in
+ * section 7 an append leaves the normals stale until an update, and icp_crop_targets (section 11) carries the kept
+ * targets' normals along.  Statuses: ICP_BAD_ARGUMENT (h NULL, k outside [3, 16]); ICP_NO_DEVICE; then the handle:
+ * ICP_BAD_ARGUMENT (not a 2-D handle; non-finite targets; read: normals not current or the range outside the cloud),
+ * ICP_EMPTY_DST (no targets).
+ *
+ * icp_estimate_point_to_line[_device]: Icp2d::estimate (src/lib.rs:105-130) with the residual n_q . (T p - q), ONE
+ * scalar per pair, where q is the handle's exact 2-D nearest neighbour of T p and n_q its line normal.  Weights
+ * (sigma = 1.4826 MAD(r), Huber 1.345), Jacobian row n^T [R | R (-a_y, a_x)^T], Huber error, the inner loop and its
+ * break tests are section 7's, applied to pairs with dz = 0 and nz = 0.  inner_iters / last_idx as there.
+ * icp_estimate_point_to_line_gated[_device]: section 12's gate around it -- the inner loop of outer iteration `it`
+ * sees the pairs with d2 = ex ex + ey ey <= max_dist * max_dist only (ex = qx - dst[j].x, ey = qy - dst[j].y at the
+ * iteration's pose; a NaN d2 is never an inlier), in the caller's order; inliers[it] (nullable) their number.
+ * Statuses, decided in this order: ICP_BAD_ARGUMENT (a required pointer NULL, n >= 2^32 - 1, gated: max_dist NaN or
+ * negative; +inf and 0.0 are valid bounds); ICP_NO_DEVICE; then the handle: ICP_BAD_ARGUMENT (not a 2-D handle),
+ * ICP_EMPTY_DST (no targets, only when a search would run: n > 0 and max_iter > 0; otherwise *out = *init),
+ * ICP_BAD_ARGUMENT (normals absent or stale); ICP_NAN_INPUT (a pair with a NaN residual).  Fewer than two pairs: the
+ * iteration applies no update.  Consequence: for inputs without a NaN d2, max_dist = +inf returns the pose, the
+ * indices and the inner counts of the ungated call, bit for bit, and inliers[it] == n. */
+int icp_compute_target_line_normals(icp_handle *h, int k);
+int icp_update_target_line_normals(icp_handle *h, int k);
+int icp_read_target_line_normals(icp_handle *h, size_t first, size_t count, double *out_xy);
+int icp_estimate_point_to_line(icp_handle *h, const double *src, size_t n, const icp_pose *init, size_t max_iter,
+                               icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters);
+int icp_estimate_point_to_line_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init, size_t max_iter,
+                                      icp_pose *out, uint32_t *d_last_idx, uint32_t *inner_iters);
+int icp_estimate_point_to_line_gated(icp_handle *h, const double *src, size_t n, const icp_pose *init, size_t max_iter,
+                                     double max_dist, icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters,
+                                     uint32_t *inliers);
+int icp_estimate_point_to_line_gated_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init,
+                                            size_t max_iter, double max_dist, icp_pose *out, uint32_t *d_last_idx,
+                                            uint32_t *inner_iters, uint32_t *inliers);
 
 #ifdef __cplusplus
 }
