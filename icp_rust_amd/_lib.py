@@ -226,6 +226,10 @@ SIGNATURES = {
     "icp_estimate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, _pp, _vp, _vp]),
     "icp_estimate_point_to_line_gated": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
     "icp_estimate_point_to_line_gated_device": (C.c_int, [_vp, _vp, _sz, _pp, _sz, C.c_double, _pp, _vp, _vp, _vp]),
+    "icp_batch_estimate_point_to_line": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, _vp, _vp, _vp, _vp]),
+    "icp_batch_estimate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, _vp, _vp, _vp,
+                                                          _vp]),
+    "icp_batch_line_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

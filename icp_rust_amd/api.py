@@ -1123,7 +1123,13 @@ class IcpBatch:
         """The same over pre-packed clouds: `items` = [(src_first, n, dst_first, m, init Transform), ...] ranges of
         `src` / `dst` (ranges may overlap).  numpy arrays go through icp_batch_estimate; contiguous float64 CUDA tensors
         through icp_batch_estimate_device, in place."""
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, None)
+
+    def _estimate_packed(self, src, dst, items, max_iter, return_info, allow_failures, line_k):
+        """estimate_packed (line_k None) and estimate_point_to_line_packed (line_k = the normals' neighbours)"""
         count = len(items)
+        name = what = "icp_batch_estimate" if line_k is None else "icp_batch_estimate_point_to_line"
+        kargs = [] if line_k is None else [int(line_k)]
         arr = (_lib.BatchItem * max(count, 1))()
         for i, (f, n, g, m, T) in enumerate(items):
             arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
@@ -1143,25 +1149,25 @@ class IcpBatch:
             for t in (src, dst):  # (the batch's own stream is not ordered against the producer's)
                 torch.cuda.current_stream(t.device).synchronize()
             idx = torch.zeros(max(total, 1), dtype=torch.int32, device=src.device) if want_idx else None
-            check(lib().icp_batch_estimate_device(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
-                                                  C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count, max_iter, out,
-                                                  C.c_void_p(status.ctypes.data),
-                                                  C.c_void_p(idx.data_ptr()) if want_idx else None,
-                                                  C.c_void_p(inner.ctypes.data)), "icp_batch_estimate_device")
+            name += "_device"
+            check(getattr(lib(), name)(self._b, C.c_void_p(src.data_ptr()), src.shape[0], C.c_void_p(dst.data_ptr()),
+                                       dst.shape[0], arr, count, *kargs, max_iter, out, C.c_void_p(status.ctypes.data),
+                                       C.c_void_p(idx.data_ptr()) if want_idx else None,
+                                       C.c_void_p(inner.ctypes.data)), name)
             idx = idx.cpu().numpy().view(np.uint32) if want_idx else None
         else:
             s, d = _host(src, self.DIM), _host(dst, self.DIM)
             idx = np.zeros(max(total, 1), dtype=np.uint32) if want_idx else None
-            check(lib().icp_batch_estimate(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, max_iter,
-                                           out, C.c_void_p(status.ctypes.data),
-                                           C.c_void_p(idx.ctypes.data) if want_idx else None,
-                                           C.c_void_p(inner.ctypes.data)), "icp_batch_estimate")
+            check(getattr(lib(), name)(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, *kargs, max_iter,
+                                       out, C.c_void_p(status.ctypes.data),
+                                       C.c_void_p(idx.ctypes.data) if want_idx else None,
+                                       C.c_void_p(inner.ctypes.data)), name)
         status = status[:count]
         Ts = []
         for i in range(count):
             if status[i] != _lib.OK:
                 if not allow_failures:
-                    raise IcpError(int(status[i]), f"icp_batch_estimate item {i}")
+                    raise IcpError(int(status[i]), f"{what} item {i}")
                 Ts.append(None)
             else:
                 Ts.append(Transform.from_pose(out[i]))
@@ -1185,6 +1191,40 @@ class IcpBatch:
         a = np.ascontiguousarray(s[:, :2])
         errs = [huber_error(T, a, np.ascontiguousarray(d[ix.astype(np.int64), :2])) for T, ix in zip(Ts, idxs)]
         return Ts, np.array(errs)
+
+    # -- EXTENSION: the same with the point-to-line residual (icp_batch_estimate_point_to_line*, section 15) --
+    def _need_2d(self, what):
+        if self.DIM != 2:
+            raise ValueError(f"{what} needs a 2-D batch (IcpBatch(2)): the line residual is section 14's, for 2-D scans")
+
+    def estimate_point_to_line(self, srcs, dsts, inits, max_iter, k=10, return_info=False, allow_failures=False):
+        """estimate() with the point-to-line residual: item i is what Icp2d(dsts[i]) returns after
+        compute_line_normals(k) from estimate_point_to_line(srcs[i], inits[i], max_iter), bit for bit; items of up to
+        1024 source and 2048 target points run as one workgroup each (normals included), the others one by one."""
+        self._need_2d("estimate_point_to_line")
+        srcs, dsts = list(srcs), list(dsts)
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
+        src, sf, sn = self._pack(srcs, "src")
+        dst, df, dm = self._pack(dsts, "dst")
+        items = list(zip(sf, sn, df, dm, self._inits(inits, len(srcs))))
+        return self.estimate_point_to_line_packed(src, dst, items, max_iter, k, return_info, allow_failures)
+
+    def estimate_point_to_line_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False):
+        """The same over pre-packed clouds (`items` as for estimate_packed; K hypotheses share one src and one dst range).
+        numpy arrays go through icp_batch_estimate_point_to_line; contiguous float64 CUDA tensors through
+        icp_batch_estimate_point_to_line_device, in place."""
+        self._need_2d("estimate_point_to_line_packed")
+        if not 3 <= int(k) <= 16:
+            raise ValueError(f"k must be in [3, 16], got {k!r}")
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k))
+
+    def line_counters(self):
+        """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
+        estimate_point_to_line*"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_line_counters(self._b, out), "icp_batch_line_counters")
+        return tuple(int(x) for x in out)
 
     # -- the quality of many poses in one call (icp_batch_evaluate*, include/icp_mi355x.h section 9) --
     def evaluate(self, srcs, dsts, transforms, max_correspondence_distance=float("inf"), allow_failures=False,

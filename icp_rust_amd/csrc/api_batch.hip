@@ -2,6 +2,9 @@
 // The items that fit one workgroup run as k_tiny_estimate_batch (gn_fast.hip), one workgroup each, in at most three
 // launches (one per workgroup size); the rest go one by one through a handle of the pool, exactly as a single call would
 // serve them.  Every item's bits are those of icp_create + icp_estimate on its own ranges.
+// Section 15, the same call with the point-to-line residual of section 14: k_line_estimate_batch (p2line_batch.hip), one
+// workgroup per item in at most two launches; one by one: icp_create_device + icp_compute_target_line_normals +
+// icp_estimate_point_to_line_device.
 #include <cstring>
 #include <new>
 #include <vector>
@@ -28,6 +31,7 @@ struct icp_batch {
   uint32_t *h_inner = nullptr;  // pinned: count x max_iter inner counts
   size_t cap_inner = 0;
   uint64_t ctr[4] = {0, 0, 0, 0};  // icp_batch_counters
+  uint64_t lctr[4] = {0, 0, 0, 0};  // icp_batch_line_counters
   // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
   QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
   size_t cap_qitems = 0, cap_h_qitems = 0;
@@ -77,16 +81,26 @@ int check_args(const icp_batch *b, const double *src, size_t src_points, const d
 bool tiny_fits(const icp_batch_item &it, size_t max_iter) {
   return it.n >= 1 && it.n <= kTinyMaxN && it.m >= 1 && it.m <= kTinyMaxM && max_iter >= 1 && max_iter <= kTinyMaxIter;
 }
+bool line_fits(const icp_batch_item &it, size_t max_iter) {
+  return it.n >= 1 && it.n <= kLineBatchMaxN && it.m >= 1 && it.m <= kLineBatchMaxM && max_iter >= 1 &&
+         max_iter <= kLineBatchMaxIter;
+}
 
 // Item i the way a single call serves it: a handle of the pool on the item's targets, icp_estimate_device on its
 // sources.  Per-item outcomes land in *status; anything else (HIP, memory, device) is the call's failure.
-int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter,
+// line_k > 0 (section 15): the handle's line normals from line_k neighbours, then icp_estimate_point_to_line_device.
+int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter, int line_k,
               icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner) {
   icp_handle *h = nullptr;
   int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
   if (rc == ICP_OK) {
-    rc = icp_estimate_device(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr, (size_t)it.n, &it.init, max_iter, out,
-                             d_idx, inner);
+    const double *s = it.n > 0 ? d_src + it.src_first * b->dim : nullptr;
+    if (line_k > 0) {
+      rc = icp_compute_target_line_normals(h, line_k);
+      if (rc == ICP_OK) rc = icp_estimate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
+    } else {
+      rc = icp_estimate_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
+    }
     icp_destroy(h);
   }
   if (rc == ICP_OK || rc == ICP_NONE || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT) {
@@ -96,8 +110,10 @@ int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_
   return rc;
 }
 
+// line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line residual, normals from line_k neighbours)
 int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
-        size_t max_iter, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
+        size_t max_iter, int line_k, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
+  uint64_t *ctr = line_k > 0 ? b->lctr : b->ctr;
   // where each item's indices go, and which items a workgroup may serve, by workgroup size
   std::vector<uint64_t> idx_first(count);
   std::vector<size_t> cls[3], one_by_one;
@@ -105,8 +121,8 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
   for (size_t i = 0; i < count; ++i) {
     idx_first[i] = at;
     at += items[i].n;
-    if (tiny_fits(items[i], max_iter)) {
-      const unsigned t = tiny_threads(items[i].n);
+    if (line_k > 0 ? line_fits(items[i], max_iter) : tiny_fits(items[i], max_iter)) {
+      const unsigned t = line_k > 0 ? line_batch_threads(items[i].n) : tiny_threads(items[i].n);
       cls[t == 512u ? 0 : (t == 768u ? 1 : 2)].push_back(i);
     } else {
       one_by_one.push_back(i);
@@ -141,10 +157,15 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
     bool granted = true;
     for (int c = 0; c < 3; ++c) {
       if (cls[c].empty()) continue;
-      HIP_TRY(launch_tiny_estimate_batch(b->dim, kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
-                                         (unsigned)cls[c].size(), (unsigned)max_iter, b->h_res,
-                                         inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
-      ++b->ctr[granted ? 2 : 3];
+      if (line_k > 0)
+        HIP_TRY(launch_line_estimate_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first, (unsigned)cls[c].size(),
+                                           (unsigned)max_iter, line_k, b->h_res, inner_iters ? b->h_inner : nullptr, d_idx,
+                                           b->stream, &granted));
+      else
+        HIP_TRY(launch_tiny_estimate_batch(b->dim, kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
+                                           (unsigned)cls[c].size(), (unsigned)max_iter, b->h_res,
+                                           inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
+      ++ctr[granted ? 2 : 3];
       first += cls[c].size();
     }
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -155,7 +176,7 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
           handed_back.push_back(i);
           continue;
         }
-        ++b->ctr[0];
+        ++ctr[0];
         if (r.status == 3) {
           status[i] = ICP_NAN_INPUT;
           continue;
@@ -167,9 +188,9 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
   }
   one_by_one.insert(one_by_one.end(), handed_back.begin(), handed_back.end());
   for (size_t i : one_by_one) {
-    ICP_TRY_RC(serve_one(b, d_src, d_dst, items[i], max_iter, &out[i], &status[i], d_idx ? d_idx + idx_first[i] : nullptr,
-                         inner_iters ? inner_iters + i * max_iter : nullptr));
-    ++b->ctr[1];
+    ICP_TRY_RC(serve_one(b, d_src, d_dst, items[i], max_iter, line_k, &out[i], &status[i],
+                         d_idx ? d_idx + idx_first[i] : nullptr, inner_iters ? inner_iters + i * max_iter : nullptr));
+    ++ctr[1];
   }
   return ICP_OK;
 }
@@ -226,18 +247,24 @@ extern "C" void icp_batch_destroy(icp_batch *b) {
   delete b;
 }
 
-extern "C" int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
-                                         size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
-                                         icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
+namespace {
+
+// section 15's two checks on top of check_args: a 2-D batch, 3 <= k <= 16
+bool line_args_ok(const icp_batch *b, int k) { return b && b->dim == 2 && k >= 3 && k <= 16; }
+
+int estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst, size_t dst_points,
+                    const icp_batch_item *items, size_t count, size_t max_iter, int line_k, icp_pose *out, int *status,
+                    uint32_t *d_last_idx, uint32_t *inner_iters) {
   ICP_TRY_RC(check_args(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, out, status, inner_iters));
   if (count == 0) return ICP_OK;
   ICP_TRY_RC(ensure_device(b));
-  return run(b, d_src, d_dst, items, count, max_iter, out, status, d_last_idx, inner_iters);
+  return run(b, d_src, d_dst, items, count, max_iter, line_k, out, status, d_last_idx, inner_iters);
 }
 
-extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
-                                  const icp_batch_item *items, size_t count, size_t max_iter, icp_pose *out, int *status,
-                                  uint32_t *last_idx, uint32_t *inner_iters) {
+// the entries that take host clouds: staged through the batch's buffers, the last indices read back
+int estimate_host(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                  const icp_batch_item *items, size_t count, size_t max_iter, int line_k, icp_pose *out, int *status,
+                  uint32_t *last_idx, uint32_t *inner_iters) {
   ICP_TRY_RC(check_args(b, src, src_points, dst, dst_points, items, count, max_iter, out, status, inner_iters));
   if (count == 0) return ICP_OK;
   ICP_TRY_RC(ensure_device(b));
@@ -257,12 +284,51 @@ extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_po
   // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
   HIP_TRY(hipStreamSynchronize(b->stream));
   const int rc = run(b, src_points > 0 ? b->d_src : nullptr, dst_points > 0 ? b->d_dst : nullptr, items, count, max_iter,
-                     out, status, want_idx ? b->d_idx : nullptr, inner_iters);
+                     line_k, out, status, want_idx ? b->d_idx : nullptr, inner_iters);
   if (rc != ICP_OK) return rc;
   if (want_idx) {
     HIP_TRY(hipMemcpyAsync(last_idx, b->d_idx, total_n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
   }
+  return ICP_OK;
+}
+
+}  // namespace
+
+extern "C" int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                         size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
+                                         icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, 0, out, status, d_last_idx,
+                         inner_iters);
+}
+
+extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                                  const icp_batch_item *items, size_t count, size_t max_iter, icp_pose *out, int *status,
+                                  uint32_t *last_idx, uint32_t *inner_iters) {
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, 0, out, status, last_idx, inner_iters);
+}
+
+// ---- section 15: the same two entries with the point-to-line residual (2-D batches, 3 <= k <= 16) ----
+extern "C" int icp_batch_estimate_point_to_line_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                       const double *d_dst, size_t dst_points, const icp_batch_item *items,
+                                                       size_t count, int k, size_t max_iter, icp_pose *out, int *status,
+                                                       uint32_t *d_last_idx, uint32_t *inner_iters) {
+  if (!line_args_ok(b, k)) return ICP_BAD_ARGUMENT;
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, k, out, status, d_last_idx,
+                         inner_iters);
+}
+
+extern "C" int icp_batch_estimate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                                size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                                size_t max_iter, icp_pose *out, int *status, uint32_t *last_idx,
+                                                uint32_t *inner_iters) {
+  if (!line_args_ok(b, k)) return ICP_BAD_ARGUMENT;
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, k, out, status, last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_line_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->lctr[q];
   return ICP_OK;
 }
 

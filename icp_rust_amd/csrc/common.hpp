@@ -541,6 +541,14 @@ size_t tiny_lds_bytes_of(int dim, unsigned m);
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
+// EXTENSION: batched point-to-line registration (p2line_batch.hip: k_line_estimate_batch; api_batch.hip drives it).  One
+// workgroup per item computes the item's line normals (k neighbours) and runs the whole registration; items, results,
+// inner counts and indices as for launch_tiny_estimate_batch.  Workgroups of 512 (n <= 512) or 1024 threads.
+constexpr unsigned kLineBatchMaxN = 1024, kLineBatchMaxM = 2048, kLineBatchMaxIter = 1024;
+inline unsigned line_batch_threads(size_t n) { return n <= 512 ? 512u : 1024u; }
+hipError_t launch_line_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                      const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                      TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
 // A record of the fold tree of section 9 (fold_device.hpp): SUMS sums that are doubles, the inlier count and whether some
 // residual was NaN.
 template <int SUMS>

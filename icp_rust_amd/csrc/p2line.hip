@@ -16,6 +16,7 @@
 //                    gate_plane.hip's k_plgate_place itself
 #include "api_internal.hpp"
 #include "compact_device.hpp"
+#include "p2line_device.hpp"
 #include "p2plane_device.hpp"
 
 using namespace icp;
@@ -32,7 +33,6 @@ __global__ __launch_bounds__(kCompactThreads) void k_plgate_place(const double2 
                                                                   uint32_t *__restrict__ out_pos,
                                                                   unsigned *__restrict__ h_total);
 
-constexpr int kLineKMax = 16;
 constexpr unsigned kLinePairWords = sizeof(PlanePair) / sizeof(double2);
 static_assert(sizeof(PlanePair) == 64 && kLinePairWords == 4, "a pair is four 16-byte words");
 
@@ -93,55 +93,8 @@ __global__ __launch_bounds__(64) void k_line_normals(const double *__restrict__ 
     cover -= 1e-9 * (g.scale + fabs(p[0]) + fabs(p[1]));
     if (cnt == k && cover > 0. && bd[k - 1] < cover * cover) break;
   }
-  double nrm[2] = {0., 0.};
-  if (cnt >= 3) {
-    double mean[2] = {0., 0.};
-    for (int j = 0; j < cnt; ++j)
-      for (int d = 0; d < 2; ++d) mean[d] = mean[d] + dst[(size_t)bi[j] * 2 + d];
-    for (int d = 0; d < 2; ++d) mean[d] = mean[d] / (double)cnt;
-    double a[2][2] = {{0., 0.}, {0., 0.}};
-    for (int j = 0; j < cnt; ++j) {
-      double e[2];
-      for (int d = 0; d < 2; ++d) e[d] = dst[(size_t)bi[j] * 2 + d] - mean[d];
-      for (int r = 0; r < 2; ++r)
-        for (int s = 0; s < 2; ++s) a[r][s] = a[r][s] + e[r] * e[s];
-    }
-    double v[2][2] = {{1., 0.}, {0., 1.}};
-    if (a[0][1] != 0.) {  // jacobi3's rotation of the pair (p, q) = (0, 1): it diagonalises a 2 x 2
-      const double theta = (a[1][1] - a[0][0]) / (2. * a[0][1]);
-      const double t = (theta >= 0. ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-      const double cs = 1. / sqrt(t * t + 1.), sn = t * cs;
-      for (int q = 0; q < 2; ++q) {  // A <- A J (columns 0, 1)
-        const double a0 = a[q][0], a1 = a[q][1];
-        a[q][0] = cs * a0 - sn * a1;
-        a[q][1] = sn * a0 + cs * a1;
-      }
-      for (int q = 0; q < 2; ++q) {  // A <- J^T A (rows 0, 1)
-        const double a0 = a[0][q], a1 = a[1][q];
-        a[0][q] = cs * a0 - sn * a1;
-        a[1][q] = sn * a0 + cs * a1;
-      }
-      for (int q = 0; q < 2; ++q) {
-        const double v0 = v[q][0], v1 = v[q][1];
-        v[q][0] = cs * v0 - sn * v1;
-        v[q][1] = sn * v0 + cs * v1;
-      }
-    }
-    const int col = a[1][1] < a[0][0] ? 1 : 0;  // the smaller eigenvalue; a tie: column 0
-    double n0 = v[0][col], n1 = v[1][col];
-    const double len = sqrt(n0 * n0 + n1 * n1);
-    if (len > 0.) {
-      n0 = n0 / len;
-      n1 = n1 / len;
-      const double lead = n1 != 0. ? n1 : n0;
-      if (lead < 0.) {
-        n0 = -n0;
-        n1 = -n1;
-      }
-      nrm[0] = n0;
-      nrm[1] = n1;
-    }
-  }
+  double nrm[2];  // (the tail behind the k best: p2line_device.hpp, shared with the batch kernel)
+  line_normal_of_neighbours(cnt, [&](int j, int d) { return dst[(size_t)bi[j] * 2 + d]; }, nrm);
   normals[(size_t)i * 3] = nrm[0];
   normals[(size_t)i * 3 + 1] = nrm[1];
   normals[(size_t)i * 3 + 2] = 0.;

@@ -845,6 +845,29 @@ int icp_estimate_point_to_line_gated_device(icp_handle *h, const double *d_src, 
                                             size_t max_iter, double max_dist, icp_pose *out, uint32_t *d_last_idx,
                                             uint32_t *inner_iters, uint32_t *inliers);
 
+/* ================================================================================
+ * 15. EXTENSION (not in the reference): many small point-to-line registrations in one call
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 8's call with section 14's residual,
+ * for 2-D batches: K pose hypotheses of one scan against one map, loop-closure candidates, a log replayed offline.
+ * Item i's out[i], status[i], indices and inner counts are what icp_create(2, dst + 2 dst_first, m) +
+ * icp_compute_target_line_normals(k) + icp_estimate_point_to_line(src + 2 src_first, n, &init, max_iter) return on a
+ * fresh handle, bit for bit (the ungated call; a first failing step's status is the item's).  Every item with
+ * 1 <= n <= 1024, 1 <= m <= 2048 and 1 <= max_iter <= 1024 runs as ONE workgroup that computes the item's line normals
+ * and the whole registration (one launch per workgroup size, at most two); the other items, and those a workgroup hands
+ * back, go through exactly those three entries one after another.  An item is never approximated.  DESIGN.md
+ * section 9j lists the hand-back reasons.
+ * Arguments, ranges, last_idx, inner_iters, per-item statuses and the call's own return value are section 8's; in
+ * addition ICP_BAD_ARGUMENT for a batch that is not 2-D and for k outside [3, 16] -- checked, like every argument,
+ * before the device is touched.  count == 0 is a successful no-op. */
+int icp_batch_estimate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                     size_t dst_points, const icp_batch_item *items, size_t count, int k, size_t max_iter,
+                                     icp_pose *out, int *status, uint32_t *last_idx, uint32_t *inner_iters);
+int icp_batch_estimate_point_to_line_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                            size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                            size_t max_iter, icp_pose *out, int *status, uint32_t *d_last_idx,
+                                            uint32_t *inner_iters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,212 @@
+"""CPU-side checks of the batched point-to-line registration (icp_batch_estimate_point_to_line*, include/icp_mi355x.h
+section 15): declared, exported and bound, the counters in the debug header; ABI version still 8; every argument error --
+a 3-D batch, k outside [3, 16], a range outside the packed arrays, null outputs -- rejected before the device is touched,
+count == 0 a successful no-op; the Python layer's refusals and return shapes (with a library that is not the real one); and
+the kernel's cross-compile for gfx950 with its register and scratch budget (the LDS plan is asserted at compile time)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import icp_rust_amd as I
+from icp_rust_amd import _lib
+from icp_rust_amd import api as api_module
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "icp_rust_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+NEW = ("icp_batch_estimate_point_to_line", "icp_batch_estimate_point_to_line_device")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    I.build()
+
+
+def declared(name):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+    return set(re.findall(r"\b(icp_[a-z0-9_]+)\s*\(", text))
+
+
+def test_symbols_are_declared_exported_and_bound():
+    public, debug = declared("icp_mi355x.h"), declared("icp_mi355x_debug.h")
+    L = C.CDLL(_lib.LIB_PATH)
+    for s in NEW:
+        assert s in public and s in _lib.SIGNATURES and hasattr(L, s), s
+    assert "icp_batch_line_counters" in debug and "icp_batch_line_counters" not in public
+    assert "icp_batch_line_counters" in _lib.SIGNATURES and hasattr(L, "icp_batch_line_counters")
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "p2line_batch.hip" in mk and "p2line_device.hpp" in mk
+    for name in ("estimate_point_to_line", "estimate_point_to_line_packed", "line_counters"):
+        assert callable(getattr(I.IcpBatch, name)), name
+
+
+def test_abi_version_is_still_8():
+    text = open(os.path.join(ROOT, "include", "icp_mi355x.h")).read()
+    assert int(re.search(r"#define\s+ICP_ABI_VERSION\s+(\d+)", text).group(1)) == 8
+    assert I.lib().icp_abi_version() == 8
+
+
+def _batch(dim=2):
+    b = C.c_void_p()
+    assert I.lib().icp_batch_create(C.byref(b), dim, -1) == _lib.OK  # (no device use: works without a GPU)
+    return b
+
+
+def _call(b, src, dst, items, k=8, max_iter=20, out=True, status=True, entry=NEW[0], count=None):
+    count = len(items) if count is None else count
+    arr = (_lib.BatchItem * max(len(items), 1))()
+    for i, (f, n, g, m) in enumerate(items):
+        arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = f, n, g, m
+        I.lib().icp_transform_identity(C.byref(arr[i].init))
+    o = (_lib.Pose * max(count, 1))() if out else None
+    st = np.zeros(max(count, 1), dtype=np.int32)
+    sp = C.c_void_p(src.ctypes.data) if src is not None else None
+    dp = C.c_void_p(dst.ctypes.data) if dst is not None else None
+    return getattr(I.lib(), entry)(b, sp, 0 if src is None else len(src), dp, 0 if dst is None else len(dst),
+                                   arr if items else None, count, k, max_iter, o,
+                                   C.c_void_p(st.ctypes.data) if status else None, None, None)
+
+
+@pytest.mark.parametrize("entry", NEW)
+def test_argument_errors_are_rejected_before_the_device_is_used(entry):
+    src, dst = np.zeros((10, 2)), np.zeros((20, 2))
+    good = [(0, 10, 0, 20), (3, 7, 0, 0), (10, 0, 20, 0)]
+    b, b3 = _batch(), _batch(3)
+    try:
+        assert _call(b3, np.zeros((10, 3)), np.zeros((20, 3)), good, entry=entry) == _lib.BAD_ARGUMENT  # a 3-D batch
+        assert _call(b3, None, None, [], count=0, entry=entry) == _lib.BAD_ARGUMENT
+        for k in (2, 17, 0, -1):
+            assert _call(b, src, dst, good, k=k, entry=entry) == _lib.BAD_ARGUMENT, k
+        bad = [
+            [(0, 11, 0, 20)],                     # source range past the array
+            [(5, 6, 0, 20)],
+            [(0, 10, 1, 20)],                     # target range past the array
+            [(0, 10, 21, 0)],                     # (an empty range that starts past the end)
+            [(0, 10, 0, 20), (2**63, 2**63, 0, 1)],  # (first + n overflows)
+        ]
+        for items in bad:
+            assert _call(b, src, dst, items, entry=entry) == _lib.BAD_ARGUMENT, items
+        assert _call(b, src, dst, good, out=False, entry=entry) == _lib.BAD_ARGUMENT
+        assert _call(b, src, dst, good, status=False, entry=entry) == _lib.BAD_ARGUMENT
+        assert _call(b, src, dst, [], count=3, entry=entry) == _lib.BAD_ARGUMENT  # items NULL, count > 0
+        assert getattr(I.lib(), entry)(None, None, 0, None, 0, None, 0, 8, 20, None, None, None, None) == _lib.BAD_ARGUMENT
+        # count == 0 is a successful no-op whatever the other pointers are, for k = 3 and k = 16 too
+        for k in (3, 8, 16):
+            assert _call(b, None, None, [], k=k, count=0, out=False, status=False, entry=entry) == _lib.OK
+        if I.lib().icp_device_count() == 0:  # valid arguments reach the device check only now
+            assert _call(b, src, dst, good, entry=entry) == _lib.NO_DEVICE
+            assert _call(b, src, dst, good, k=3, entry=entry) == _lib.NO_DEVICE
+            assert _call(b, src, dst, good, k=16, entry=entry) == _lib.NO_DEVICE
+        out = (C.c_uint64 * 4)(9, 9, 9, 9)
+        assert I.lib().icp_batch_line_counters(b, out) == _lib.OK and list(out) == [0, 0, 0, 0]
+        assert I.lib().icp_batch_line_counters(None, out) == _lib.BAD_ARGUMENT
+        assert I.lib().icp_batch_line_counters(b, None) == _lib.BAD_ARGUMENT
+    finally:
+        I.lib().icp_batch_destroy(b)
+        I.lib().icp_batch_destroy(b3)
+
+
+def test_python_layer_refuses_before_the_library_is_reached():
+    B3 = object.__new__(I.IcpBatch)  # (no batch object is reached: the dimension is checked first)
+    B3.DIM, B3._b, B3._device = 3, None, None
+    with pytest.raises(ValueError):
+        B3.estimate_point_to_line([np.zeros((3, 3))], [np.zeros((3, 3))], None, 20)
+    with pytest.raises(ValueError):
+        B3.estimate_point_to_line_packed(np.zeros((3, 3)), np.zeros((3, 3)), [], 20)
+    B = I.IcpBatch(2)
+    with pytest.raises(ValueError):
+        B.estimate_point_to_line([np.zeros((3, 2))], [], None, 20)
+    with pytest.raises(ValueError):
+        B.estimate_point_to_line([np.zeros((3, 2))], [np.zeros((3, 2))], [I.Transform(), I.Transform()], 20)
+    for k in (2, 17):
+        with pytest.raises(ValueError):
+            B.estimate_point_to_line([np.zeros((3, 2))], [np.zeros((3, 2))], None, 20, k=k)
+    assert B.estimate_point_to_line([], [], [], 20) == []
+    assert B.line_counters() == (0, 0, 0, 0)
+    B.close()
+
+
+class _FakeLib:
+    """Stands in for the library: records the host entry's arguments, answers item i with the pose (i, 0, 0), indices
+    i, i, ..., inner counts i + 1 and the statuses handed to it."""
+
+    def __init__(self, statuses):
+        self.statuses, self.calls, self.real = statuses, [], I.lib()
+
+    def __getattr__(self, name):  # (the host-only pose algebra stays the library's)
+        return getattr(self.real, name)
+
+    def icp_batch_estimate_point_to_line(self, b, src, src_points, dst, dst_points, arr, count, k, max_iter, out, status,
+                                         idx, inner):
+        self.calls.append((src_points, dst_points, count, k, max_iter))
+        st = np.ctypeslib.as_array(C.cast(status, C.POINTER(C.c_int32)), shape=(count,))
+        st[:] = self.statuses[:count]
+        ii = np.ctypeslib.as_array(C.cast(inner, C.POINTER(C.c_uint32)), shape=(count * max_iter,))
+        at = 0
+        for i in range(count):
+            out[i].r00, out[i].r10, out[i].r01, out[i].r11, out[i].tx, out[i].ty = 1.0, 0.0, 0.0, 1.0, float(i), 0.0
+            ii[i * max_iter:(i + 1) * max_iter] = i + 1
+            n = int(arr[i].n)
+            if idx is not None and n:
+                np.ctypeslib.as_array(C.cast(idx, C.POINTER(C.c_uint32)), shape=(at + n,))[at:] = i
+            at += n
+        return _lib.OK
+
+
+def test_python_return_shapes_with_a_fake_library(monkeypatch):
+    fake = _FakeLib([_lib.OK, _lib.NAN_INPUT, _lib.OK])
+    monkeypatch.setattr(api_module, "lib", lambda: fake)
+    B = object.__new__(I.IcpBatch)
+    B.DIM, B._b, B._device = 2, C.c_void_p(), None
+    srcs = [np.zeros((4, 2)), np.ones((2, 2)), np.zeros((0, 2))]
+    dsts = [np.zeros((5, 2)), np.ones((6, 2)), np.ones((3, 2))]
+    Ts, idxs, inner, status = B.estimate_point_to_line(srcs, dsts, None, 7, k=5, return_info=True, allow_failures=True)
+    assert fake.calls == [(6, 14, 3, 5, 7)]
+    assert [T is None for T in Ts] == [False, True, False] and Ts[2].as_array()[4] == 2.0
+    assert [len(x) for x in idxs] == [4, 2, 0] and idxs[1].tolist() == [1, 1]
+    assert inner.shape == (3, 7) and inner[:, 0].tolist() == [1, 2, 3] and status.tolist() == [0, _lib.NAN_INPUT, 0]
+    with pytest.raises(I.IcpError, match="item 1"):
+        B.estimate_point_to_line(srcs, dsts, None, 7)
+    fake.statuses = [_lib.OK] * 3
+    Ts = B.estimate_point_to_line_packed(np.zeros((4, 2)), np.zeros((9, 2)), [(0, 4, 0, 9, I.Transform())] * 3, 2)
+    assert len(Ts) == 3 and all(isinstance(T, I.Transform) for T in Ts)
+    assert fake.calls[-1] == (4, 9, 3, 10, 2)  # (k defaults to 10)
+    B._b = None  # (nothing to destroy)
+
+
+def _usage(src):
+    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
+                          "-I" + os.path.join(ROOT, "include"), "-c", os.path.join(CSRC, src), "-o", os.devnull,
+                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    use, name = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            use[name] = {}
+        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
+            m = re.search(pat, line)
+            if m and name:
+                use[name][key] = int(m.group(1))
+    return use
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+def test_batch_kernel_cross_compiles_within_its_budget():
+    """one instantiation per workgroup size; no spill at 512 threads, at 1024 (128 registers per thread) no more than the
+    point kernel may (tests/test_registers.py: 96 bytes per lane); no static LDS on top of the dynamic plan"""
+    use = _usage("p2line_batch.hip")
+    for b, cap in ((512, 0), (1024, 96)):
+        names = [k for k in use if "k_line_estimate_batchILj%dE" % b in k]
+        assert len(names) == 1, names
+        u = use[names[0]]
+        assert u["scratch"] <= cap, (names[0], u)
+        assert u["vgpr"] <= 512 // (b // 256), (names[0], u)  # (a workgroup must fit a CU at all)
+        assert u["lds"] == 0, (names[0], u)
