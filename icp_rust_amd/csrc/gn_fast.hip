@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "gn_device.hpp"
+#include "tiny_device.hpp"
 
 namespace icp {
 
@@ -21,86 +22,7 @@ namespace icp {
 // normal equations folded in exactly the multi-workgroup tree of reduce_geometry(n)
 // (1 or 2 virtual blocks of 512 threads, then the 512-thread second stage), so the bits are
 // the same as on the general path.
-// Bitonic sort of 2 x 1024 keys, one key of each array per thread.  The 45 compare-exchange stages
-// whose partner is in the same wave (j < 64) are register shuffles; only the 10 stages with
-// j >= 64 go through LDS, double-buffered so that each costs ONE workgroup barrier.  (The first
-// version ran all 55 stages through LDS with a barrier each, twice per evaluation: 48 us per
-// evaluation of a 650-point scan, 40 of them barriers.)  On return thread t holds the t-th
-// smallest key of each array.
-__device__ __forceinline__ void bitonic_sort2_1024(unsigned long long &ka, unsigned long long &kb,
-                                                   unsigned long long (*buf)[2][1024]) {
-  const unsigned tid = threadIdx.x;
-  int cur = 0;
-  for (unsigned k = 2; k <= 1024; k <<= 1)
-    for (unsigned j = k >> 1; j > 0; j >>= 1) {
-      unsigned long long pa, pb;
-      if (j >= 64) {
-        buf[cur][0][tid] = ka;
-        buf[cur][1][tid] = kb;
-        __syncthreads();
-        pa = buf[cur][0][tid ^ j];
-        pb = buf[cur][1][tid ^ j];
-        cur ^= 1;  // the next LDS stage writes the other buffer: nobody is still reading it
-      } else {
-        pa = __shfl_xor(ka, (int)j);
-        pb = __shfl_xor(kb, (int)j);
-      }
-      // ascending block (tid & k) == 0: the lower index keeps the smaller key
-      const bool keep_min = ((tid & j) == 0) == ((tid & k) == 0);
-      ka = keep_min ? (ka < pa ? ka : pa) : (ka > pa ? ka : pa);
-      kb = keep_min ? (kb < pb ? kb : pb) : (kb > pb ? kb : pb);
-    }
-}
-
-// The two middle order statistics of fl(|r - med|) over the n residuals whose keys are sorted in
-// S (src/stats.rs:30-37) WITHOUT sorting again: left of the median the distances fl(med - r) fall
-// with the index, right of it fl(r - med) rise (rounding is monotone), so "how many distances are
-// < d" and "<= d" are two binary searches on each side.  Every thread ranks its own distance; the
-// threads whose rank interval [less, leq) holds a wanted rank publish it (equal values: benign).
-__device__ __forceinline__ void mad_ranks(const unsigned long long *S, unsigned n, double med, unsigned lo_rank,
-                                          unsigned hi_rank, double *out /* LDS, [2] */) {
-  const unsigned tid = threadIdx.x;
-  if (tid >= n) return;
-  auto dist = [&](unsigned i) { return fabs(k2f(S[i]) - med); };
-  // p = first index with r >= med (NaN residuals are reported through nan_flag; the loops are bounded)
-  unsigned p;
-  {
-    unsigned lo = 0, hi = n;
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      if (k2f(S[mid]) < med) lo = mid + 1;
-      else hi = mid;
-    }
-    p = lo;
-  }
-  const double d = dist(tid);
-  // left part [0, p): distances non-increasing in i -> {d_i < d} and {d_i <= d} are suffixes
-  auto left_first = [&](bool strict) {
-    unsigned lo = 0, hi = p;
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      const double v = dist(mid);
-      if (strict ? (v < d) : (v <= d)) hi = mid;
-      else lo = mid + 1;
-    }
-    return lo;
-  };
-  // right part [p, n): non-decreasing -> prefixes
-  auto right_end = [&](bool strict) {
-    unsigned lo = p, hi = n;
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      const double v = dist(mid);
-      if (strict ? (v < d) : (v <= d)) lo = mid + 1;
-      else hi = mid;
-    }
-    return lo;
-  };
-  const unsigned less = (p - left_first(true)) + (right_end(true) - p);
-  const unsigned leq = (p - left_first(false)) + (right_end(false) - p);
-  if (less <= lo_rank && lo_rank < leq) out[0] = d;
-  if (less <= hi_rank && hi_rank < leq) out[1] = d;
-}
+// (the sort, the ranks and the median / sigma block: tiny_device.hpp)
 
 // src/stats.rs:18-27 on two order-preserving keys
 __device__ __forceinline__ double middle_of_host(unsigned n, unsigned long long klo, unsigned long long khi) {
@@ -152,31 +74,15 @@ __global__ __launch_bounds__(1024) void k_tiny_eval(const double2 *__restrict__ 
     if ((r0 != r0) | (r1 != r1)) s_nan = 1;
   }
   TSTAMP();
-  const unsigned lo_rank = (n - 1) / 2, hi_rank = n / 2;
-  // medians (src/stats.rs:11-28): sort the order-preserving keys, look the two middle ranks up
-  unsigned long long ka = has ? f2k(r0) : ~0ull, kb = has ? f2k(r1) : ~0ull;
-  bitonic_sort2_1024(ka, kb, buf);
+  // medians (src/stats.rs:11-28): sort the order-preserving keys, look the two middle ranks up; MADs
+  // (src/stats.rs:30-47): ranks of the distances to the median, from the sorted residuals
+  unsigned long long key[2] = {has ? f2k(r0) : ~0ull, has ? f2k(r1) : ~0ull};
+  tiny_bitonic_sort<1024, 2>(key, buf);
   TSTAMP();
   __syncthreads();  // (the last LDS stage's readers)
-  buf[0][0][tid] = ka;
-  buf[0][1][tid] = kb;
-  __syncthreads();
-  double med[2];
-  {
-    const double xl = k2f(buf[0][0][lo_rank]), xh = k2f(buf[0][0][hi_rank]);
-    const double yl = k2f(buf[0][1][lo_rank]), yh = k2f(buf[0][1][hi_rank]);
-    med[0] = (n & 1) ? xl : (xl + xh) / 2.;
-    med[1] = (n & 1) ? yl : (yl + yh) / 2.;
-  }
+  double med[2], sig[2];
+  tiny_sorted_median_sigma<1024, 2>(key, buf[0], n, s_mad, med, sig);
   TSTAMP();
-  // MADs (src/stats.rs:30-47): ranks of the distances to the median, from the sorted residuals
-  mad_ranks(buf[0][0], n, med[0], lo_rank, hi_rank, s_mad[0]);  // (both dimensions in lockstep: slower, measured)
-  mad_ranks(buf[0][1], n, med[1], lo_rank, hi_rank, s_mad[1]);
-  __syncthreads();
-  TSTAMP();
-  double sig[2];
-  sig[0] = ICP_PPF34 * ((n & 1) ? s_mad[0][0] : (s_mad[0][0] + s_mad[0][1]) / 2.);
-  sig[1] = ICP_PPF34 * ((n & 1) ? s_mad[1][0] : (s_mad[1][0] + s_mad[1][1]) / 2.);
   // weighted normal equations + Huber error (src/lib.rs:238-255, 45-50), one point per thread
   double acc[kNSum + 1];
 #pragma unroll
@@ -229,9 +135,9 @@ __global__ __launch_bounds__(1024) void k_tiny_eval(const double2 *__restrict__ 
 #ifdef ICP_TINY_DEBUG
   TSTAMP();
   if (tid == 0 && (seq % 64) == 5)
-    printf("[tiny] load %lld sort %lld lookup %lld mad %lld accumulate %lld reduce %lld fence %lld publish %lld (x10 ns)\n",
+    printf("[tiny] load %lld sort %lld median+mad %lld accumulate %lld reduce %lld fence %lld publish %lld (x10 ns)\n",
            tst[1] - tst[0], tst[2] - tst[1], tst[3] - tst[2], tst[4] - tst[3], tst[5] - tst[4], tst[6] - tst[5],
-           tst[7] - tst[6], tst[8] - tst[7]);
+           tst[7] - tst[6]);
 #endif
 }
 
@@ -570,22 +476,13 @@ hipError_t launch_tiny_estimate(icp_handle *h, const double *d_src, size_t n, co
   Workspace &w = h->ws;
   hipError_t e;
   // the 160 KB of dynamic LDS are granted once per process; if the runtime refuses, small clouds simply take the
-  // general path (*status stays -1) -- they must never launch with an LDS size that was not granted
-  static int lds_granted = 0;  // 0 not asked yet, 1 yes, -1 refused
-  if (lds_granted < 0) return hipSuccess;
-  if (lds_granted == 0) {
-    const void *kernels[] = {
-        reinterpret_cast<const void *>(&k_tiny_estimate<2, 512>),  reinterpret_cast<const void *>(&k_tiny_estimate<2, 768>),
-        reinterpret_cast<const void *>(&k_tiny_estimate<2, 1024>), reinterpret_cast<const void *>(&k_tiny_estimate<3, 512>),
-        reinterpret_cast<const void *>(&k_tiny_estimate<3, 768>),  reinterpret_cast<const void *>(&k_tiny_estimate<3, 1024>)};
-    lds_granted = 1;
-    for (const void *k : kernels)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) lds_granted = -1;
-    if (lds_granted < 0) {
-      (void)hipGetLastError();
-      return hipSuccess;
-    }
-  }
+  // general path (*status stays -1)
+  static TinyLdsGrant grant;
+  if (!grant.ask({reinterpret_cast<const void *>(&k_tiny_estimate<2, 512>), reinterpret_cast<const void *>(&k_tiny_estimate<2, 768>),
+                  reinterpret_cast<const void *>(&k_tiny_estimate<2, 1024>), reinterpret_cast<const void *>(&k_tiny_estimate<3, 512>),
+                  reinterpret_cast<const void *>(&k_tiny_estimate<3, 768>), reinterpret_cast<const void *>(&k_tiny_estimate<3, 1024>)},
+                 kTinyLdsGrant))
+    return hipSuccess;
   if (!w.h_tiny &&
       (e = hipHostMalloc(&w.h_tiny, sizeof(TinyResult) + kTinyMaxIter * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
     return e;
@@ -633,73 +530,10 @@ hipError_t launch_tiny_estimate(icp_handle *h, const double *d_src, size_t n, co
 
 // =======================================================================================
 // Batched small registrations (an extension beyond the reference, which has no batch call): one workgroup per item, the
-// body above unchanged.  A single call gets its targets' box from the handle's grid (build_grid); an item has no handle,
-// so its workgroup first reduces min / max over its own targets -- fmin / fmax exactly as k_grid_bbox and build_grid fold
-// them (NaN coordinates are skipped; exact and independent of the order), hence the same centre, bit for bit.  The screen's
-// margin needs a bound on |coordinate| no smaller than build_grid's GridParams::scale = max |lo|, |hi| + hh, hh its cell
-// size; hh <= max(2 emax, 1.26 emax, 1) <= 2 emax + 1 (emax the largest extent: the cell of ~2 targets has
-// (2 vol / m)^(1/k) <= 2^(1/k) emax, a degenerate cloud gets 1, and the growth loop stops by 1.26 emax at the latest), so
-// scale = max |lo|, |hi| + 2 emax + 1 serves; a larger margin only sends more candidates to the exact f64 test.  A box
-// that is not finite reports -1 (not served), as a single call whose handle builds no grid takes the general path.
-// Items are independent: no barrier, flag or atomic across workgroups.
-template <int DIM, unsigned B>
-__device__ __forceinline__ bool tiny_batch_box(const double *dst, unsigned m, double *cx, double *cy, double *cz,
-                                               double *scale) {
-  extern __shared__ unsigned char lds_raw[];
-  double *wpart = reinterpret_cast<double *>(lds_raw);  // [B / 64][6]; the body's carve-up overwrites it afterwards
-  const unsigned tid = threadIdx.x;
-  double v[6];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    v[d] = __builtin_huge_val();
-    v[3 + d] = -__builtin_huge_val();
-  }
-  for (unsigned k = tid; k < m; k += B)
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      const double x = dst[(size_t)k * DIM + d];
-      v[d] = fmin(v[d], x);
-      v[3 + d] = fmax(v[3 + d], x);
-    }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      v[d] = fmin(v[d], __shfl_xor(v[d], o));
-      v[3 + d] = fmax(v[3 + d], __shfl_xor(v[3 + d], o));
-    }
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < 6; ++q) wpart[(tid >> 6) * 6 + q] = v[q];
-  __syncthreads();
-  double lo[3], hi[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    lo[d] = wpart[d];
-    hi[d] = wpart[3 + d];
-    for (unsigned w = 1; w < B / 64; ++w) {
-      lo[d] = fmin(lo[d], wpart[w * 6 + d]);
-      hi[d] = fmax(hi[d], wpart[w * 6 + 3 + d]);
-    }
-  }
-  __syncthreads();  // (everybody has read the wave minima before the body carves the LDS up)
-  double emax = 0., amax = 0.;
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    if (d >= DIM) lo[d] = hi[d] = 0.;
-    ok = ok && __builtin_isfinite(lo[d]) && __builtin_isfinite(hi[d]);
-    emax = fmax(emax, hi[d] - lo[d]);
-    amax = fmax(amax, fmax(fabs(lo[d]), fabs(hi[d])));
-  }
-  ok = ok && __builtin_isfinite(emax);
-  *cx = 0.5 * (lo[0] + hi[0]);
-  *cy = 0.5 * (lo[1] + hi[1]);
-  *cz = 0.5 * (lo[2] + hi[2]);
-  *scale = amax + 2. * emax + 1.;
-  return ok;  // (the same in every thread)
-}
-
+// body above unchanged.  A single call gets its targets' box from the handle's grid; an item has no handle, so its
+// workgroup first finds the box of its own targets (tiny_device.hpp: tiny_batch_box; a box that is not finite reports -1,
+// not served, as a single call whose handle builds no grid takes the general path).  Items are independent: no barrier,
+// flag or atomic across workgroups.
 template <int DIM, unsigned B>
 __global__ __launch_bounds__(B) void k_tiny_estimate_batch(const double *__restrict__ src_all,
                                                               const double *__restrict__ dst_all,
@@ -714,7 +548,8 @@ __global__ __launch_bounds__(B) void k_tiny_estimate_batch(const double *__restr
   uint32_t *idx_out = idx_all ? idx_all + item.idx_first : nullptr;
   const Pose &T0 = item.init;
   double cx, cy, cz, scale;
-  if (!tiny_batch_box<DIM, B>(dst, m, &cx, &cy, &cz, &scale)) {
+  extern __shared__ unsigned char lds_raw[];  // (its start is the box's scratch; the body carves it up afterwards)
+  if (!tiny_batch_box<DIM, B>(dst, m, reinterpret_cast<double *>(lds_raw), &cx, &cy, &cz, &scale)) {
     if (threadIdx.x == 0) res->status = -1;
     return;
   }
@@ -726,22 +561,15 @@ size_t tiny_lds_bytes_of(int dim, unsigned m) { return tiny_lds_bytes(dim, m); }
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted) {
-  // the same grant as the single kernels', asked for these six once per process; refused: nothing launches with an LDS
-  // size that was not granted
-  static int lds_granted = 0;  // 0 not asked yet, 1 yes, -1 refused
-  if (lds_granted == 0) {
-    const void *kernels[] = {reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 512>),
-                             reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 768>),
-                             reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 1024>),
-                             reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 512>),
-                             reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 768>),
-                             reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 1024>)};
-    lds_granted = 1;
-    for (const void *k : kernels)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) lds_granted = -1;
-    if (lds_granted < 0) (void)hipGetLastError();
-  }
-  *granted = lds_granted > 0;
+  // the same grant as the single kernels', asked for these six once per process
+  static TinyLdsGrant grant;
+  *granted = grant.ask({reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 512>),
+                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 768>),
+                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 1024>),
+                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 512>),
+                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 768>),
+                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 1024>)},
+                       kTinyLdsGrant);
   if (!*granted || count == 0) return hipSuccess;
   const size_t lds = tiny_lds_bytes(dim, m_max);
 #define ICP_TINY_BATCH_LAUNCH(D, BB)                                                                                   \

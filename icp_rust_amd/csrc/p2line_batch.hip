@@ -3,32 +3,35 @@
 // return on a fresh handle, bit for bit (section 14; p2line.hip, p2plane.hip, api_ext.hip: p2pl_loop_on_pairs), or the
 // workgroup hands the item back (TinyResult::status = -1) and api_batch.hip serves it through exactly those entries.
 // Nothing crosses workgroups: no flag, no atomic, no barrier across them.  What a workgroup does:
-//   box        fmin / fmax over its own targets (gn_fast.hip: tiny_batch_box restated for two dimensions)
-//   targets    sorted by fl32(x - cx) into LDS, with the f32 screen records of tiny_estimate_body.inc
+// The pieces it has in common with the point kernels (gn_fast.hip, tiny_estimate_body.inc) are shared with them, each
+// one copy in tiny_device.hpp.
+//   box        fmin / fmax over its own targets (tiny_batch_box)
+//   targets    sorted by fl32(x - cx) into LDS, with the f32 screen records (tiny_sort_targets)
 //   normals    per target the k best by (d^2, index) from a sweep outwards over the sorted targets (exact: the k-nearest
 //              set under that order is unique), lists in LDS for as many targets per round as the grant allows, then
 //              line_normal_of_neighbours (p2line_device.hpp), the statement k_line_normals evaluates
-//   outer      transform, exact nearest neighbour (tiny_estimate_body.inc's sweep and prune), the pair of k_line_gather
-//   inner      plane_residual, exact median and MAD of r from one bitonic sort of the keys (ranks on the sorted keys, as
-//              k_tiny_eval's sorting path), the 13 sums of k_p2pl_accumulate in the tree of reduce_geometry(n) -- one or two
-//              blocks of 512 folded as block_reduce_store, then k_final_reduce's fold over the blocks -- solve_update, the
+//   outer      transform, exact nearest neighbour (tiny_nearest: sweep and prune), the pair of k_line_gather
+//   inner      plane_residual, exact median and MAD of r from one bitonic sort of the keys (tiny_bitonic_sort, ranks on the
+//              sorted keys, as k_tiny_eval's sorting path), the 13 sums of k_p2pl_accumulate in the tree of
+//              reduce_geometry(n) -- one or two blocks of 512 folded as block_reduce_store, then k_final_reduce's fold
+//              over the blocks -- solve_update, the
 //              three break tests in p2pl_loop_on_pairs' order, transform_new with the restated sin / cos
+//              (tiny_inner_decide); the composed pose and the fixed-point test (tiny_outer_tail)
 // Hand-back reasons: a box that is not finite; a NaN target coordinate; a rotation update outside the restated range of
 // sin / cos.  A NaN residual is the item's ICP_NAN_INPUT.
 #include "common.hpp"
 #include "gn_device.hpp"
 #include "p2line_device.hpp"
 #include "p2plane_device.hpp"
+#include "tiny_device.hpp"
 
 namespace icp {
 
 constexpr int kLineSums = kNAcc;  // jtj[9], jtr[3], huber error: what k_p2pl_accumulate folds
 
-struct LineCtl {
-  Pose Ti, T;
-  double mad[2];
-  int done, nan, bail, fixed;
-  unsigned applied, evals, pos0, pad;
+struct LineCtl : TinyCtl {
+  double mad[1][2];
+  unsigned pos0;  // the sorted position of the target of original index 0
 };
 
 // ---- the LDS plan of a launch ----
@@ -38,7 +41,6 @@ struct LineCtl {
 // normals ((8 + 4) B x 16 per list-holding thread), the estimator's two sort buffers and sorted keys (3 x 8 B x B).
 // Per-thread lists for every thread do not fit beside 2048 targets, so the normals run in rounds of `list_threads`
 // targets: as many as the grant leaves room for, up to one per thread and per target.
-constexpr size_t kLineLdsGrant = 160 * 1024 - 256;
 constexpr size_t kLineListBytes = kLineKMax * (sizeof(double) + sizeof(uint32_t));
 constexpr size_t line_fixed_bytes(unsigned m) {
   const size_t mp = (m + 63u) & ~63u;
@@ -46,8 +48,8 @@ constexpr size_t line_fixed_bytes(unsigned m) {
          sizeof(double) * 16 + 256;
 }
 static_assert(sizeof(LineCtl) <= 256, "LineCtl's share of the LDS");
-static_assert(line_fixed_bytes(kLineBatchMaxM) + 3 * 1024 * 8 <= kLineLdsGrant &&
-                  (kLineLdsGrant - line_fixed_bytes(kLineBatchMaxM)) / kLineListBytes >= 256,
+static_assert(line_fixed_bytes(kLineBatchMaxM) + 3 * 1024 * 8 <= kTinyLdsGrant &&
+                  (kTinyLdsGrant - line_fixed_bytes(kLineBatchMaxM)) / kLineListBytes >= 256,
               "2048 targets leave room for the sort buffers and for at least 256 lists");
 struct LinePlan {
   unsigned list_threads, shared_bytes;
@@ -57,7 +59,7 @@ constexpr LinePlan line_batch_plan(unsigned threads, unsigned m_max) {
   const size_t fixed = line_fixed_bytes(m_max);
   size_t keys = 64;
   while (keys < m_max) keys <<= 1;
-  const size_t fit = (kLineLdsGrant - fixed) / kLineListBytes / 64 * 64;
+  const size_t fit = (kTinyLdsGrant - fixed) / kLineListBytes / 64 * 64;
   size_t lists = (m_max + 63u) & ~63u;  // (a list per target is all a round can use)
   lists = lists < threads ? lists : threads;
   lists = lists < fit ? lists : fit;
@@ -71,133 +73,8 @@ static_assert(line_batch_plan(512, 1).list_threads == 64 && line_batch_plan(512,
 static_assert(line_batch_plan(1024, 668).list_threads == 640 && line_batch_plan(1024, 668).lds_bytes == 158784, "m = 668");
 static_assert(line_batch_plan(512, kLineBatchMaxM).list_threads == 320 && line_batch_plan(1024, kLineBatchMaxM).list_threads == 320 &&
                   line_batch_plan(1024, kLineBatchMaxM).lds_bytes == 161856 &&
-                  line_batch_plan(1024, kLineBatchMaxM).lds_bytes <= kLineLdsGrant,
+                  line_batch_plan(1024, kLineBatchMaxM).lds_bytes <= kTinyLdsGrant,
               "m = 2048");
-
-// gn_fast.hip's tiny_batch_box for two dimensions: the centre of the targets' box and a bound on the screen's margin,
-// false where the box is not finite.  Uses the start of the LDS as scratch (two barriers; free again on return).
-template <unsigned B>
-__device__ __forceinline__ bool line_batch_box(const double *dst, unsigned m, double *wpart, double *cx, double *cy,
-                                               double *scale) {
-  const unsigned tid = threadIdx.x;
-  double v[4] = {__builtin_huge_val(), __builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
-  for (unsigned k = tid; k < m; k += B)
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const double x = dst[(size_t)k * 2 + d];
-      v[d] = fmin(v[d], x);
-      v[2 + d] = fmax(v[2 + d], x);
-    }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      v[d] = fmin(v[d], __shfl_xor(v[d], o));
-      v[2 + d] = fmax(v[2 + d], __shfl_xor(v[2 + d], o));
-    }
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) wpart[(tid >> 6) * 4 + q] = v[q];
-  __syncthreads();
-  double lo[2], hi[2];
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    lo[d] = wpart[d];
-    hi[d] = wpart[2 + d];
-    for (unsigned w = 1; w < B / 64; ++w) {
-      lo[d] = fmin(lo[d], wpart[w * 4 + d]);
-      hi[d] = fmax(hi[d], wpart[w * 4 + 2 + d]);
-    }
-  }
-  __syncthreads();
-  double emax = 0., amax = 0.;
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    ok = ok && __builtin_isfinite(lo[d]) && __builtin_isfinite(hi[d]);
-    emax = fmax(emax, hi[d] - lo[d]);
-    amax = fmax(amax, fmax(fabs(lo[d]), fabs(hi[d])));
-  }
-  ok = ok && __builtin_isfinite(emax);
-  *cx = 0.5 * (lo[0] + hi[0]);
-  *cy = 0.5 * (lo[1] + hi[1]);
-  *scale = amax + 2. * emax + 1.;
-  return ok;  // (the same in every thread)
-}
-
-// Bitonic sort of B keys, one per thread (gn_fast.hip's bitonic_sort2_1024 for one array and B threads): stages whose
-// partner is in the same wave are register shuffles, the others go through LDS, double-buffered so that each costs one
-// workgroup barrier.  On return thread t holds the t-th smallest key.
-template <unsigned B>
-__device__ __forceinline__ void line_sort_keys(unsigned long long &key, unsigned long long (*buf)[B]) {
-  const unsigned tid = threadIdx.x;
-  int cur = 0;
-  for (unsigned k = 2; k <= B; k <<= 1)
-    for (unsigned j = k >> 1; j > 0; j >>= 1) {
-      unsigned long long p;
-      if (j >= 64) {
-        buf[cur][tid] = key;
-        __syncthreads();
-        p = buf[cur][tid ^ j];
-        cur ^= 1;  // the next LDS stage writes the other buffer: nobody is still reading it
-      } else {
-        p = __shfl_xor(key, (int)j);
-      }
-      const bool keep_min = ((tid & j) == 0) == ((tid & k) == 0);
-      key = keep_min ? (key < p ? key : p) : (key > p ? key : p);
-    }
-}
-
-// gn_fast.hip's mad_ranks: the two middle order statistics of fl(|r - med|) over the n residuals whose keys are sorted
-// in S, without sorting again (left of the median the distances fall with the index, right of it they rise: rounding is
-// monotone).  Every thread ranks its own distance; those whose rank interval holds a wanted rank publish it.
-__device__ __forceinline__ void line_mad_ranks(const unsigned long long *S, unsigned n, double med, unsigned lo_rank,
-                                               unsigned hi_rank, double *out /* LDS, [2] */) {
-  const unsigned tid = threadIdx.x;
-  if (tid >= n) return;
-  auto dist = [&](unsigned i) { return fabs(k2f(S[i]) - med); };
-  unsigned p;
-  {
-    unsigned lo = 0, hi = n;
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      if (k2f(S[mid]) < med) lo = mid + 1;
-      else hi = mid;
-    }
-    p = lo;
-  }
-  const double d = dist(tid);
-  auto left_first = [&](bool strict) {
-    unsigned lo = 0, hi = p;
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      const double v = dist(mid);
-      if (strict ? (v < d) : (v <= d)) hi = mid;
-      else lo = mid + 1;
-    }
-    return lo;
-  };
-  auto right_end = [&](bool strict) {
-    unsigned lo = p, hi = n;
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      const double v = dist(mid);
-      if (strict ? (v < d) : (v <= d)) lo = mid + 1;
-      else hi = mid;
-    }
-    return lo;
-  };
-  const unsigned less = (p - left_first(true)) + (right_end(true) - p);
-  const unsigned leq = (p - left_first(false)) + (right_end(false) - p);
-  if (less <= lo_rank && lo_rank < leq) out[0] = d;
-  if (less <= hi_rank && hi_rank < leq) out[1] = d;
-}
-
-// what the f32 screen compares against for a best (or k-th best) exact distance d: rounded up (nn_brute.hip)
-__device__ __forceinline__ float line_screen_bound(double d, double ec) {
-  const double rr = sqrt(d) + ec;
-  return (float)(rr * rr * 1.000004) * 1.000001f + 1e-37f;
-}
 
 template <unsigned B>
 __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restrict__ src_all,
@@ -217,8 +94,8 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
   const unsigned tid = threadIdx.x;
   const int wave = tid >> 6;
 
-  double cx, cy, scale;
-  if (!line_batch_box<B>(dst, m, reinterpret_cast<double *>(lds_raw), &cx, &cy, &scale)) {
+  double cx, cy, cz, scale;  // (cz: +0.0 in two dimensions)
+  if (!tiny_batch_box<2, B>(dst, m, reinterpret_cast<double *>(lds_raw), &cx, &cy, &cz, &scale)) {
     if (tid == 0) res->status = -1;
     return;
   }
@@ -238,61 +115,24 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
   double *tot = reinterpret_cast<double *>(p);
   p += sizeof(double) * 16;
   LineCtl *C = reinterpret_cast<LineCtl *>(p);
+  const TinyTargets tg = {tx, ty, nullptr, g4, m};
 
   if (tid == 0) {
     C->T = item.init;
     C->nan = C->bail = 0;
     C->evals = 0;
     C->pos0 = 0;
-    C->mad[0] = C->mad[1] = 0.;
+    C->mad[0][0] = C->mad[0][1] = 0.;
   }
   if (tid < 16) {  // (the wave sums of the waves a 512-thread workgroup does not have stay +0.0)
 #pragma unroll
     for (int q = 0; q < kLineSums; ++q) sm[tid][q] = 0.;
   }
-  // ---- targets sorted by x (tiny_estimate_body.inc): keys = (order-preserving bits of fl32(x - cx), index) ----
-  {
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(shared);
-    unsigned P = 64;
-    while (P < m) P <<= 1;
-    for (unsigned k = tid; k < P; k += B) {
-      unsigned long long key = ~0ull;
-      if (k < m) {
-        const unsigned u = __float_as_uint((float)(dst[(size_t)k * 2] - cx));
-        const unsigned o = (u >> 31) ? ~u : (u | 0x80000000u);
-        key = ((unsigned long long)o << 32) | k;
-      }
-      keys[k] = key;
-    }
-    __syncthreads();
-    for (unsigned k2 = 2; k2 <= P; k2 <<= 1)
-      for (unsigned j = k2 >> 1; j > 0; j >>= 1) {
-        for (unsigned t = tid; t < (P >> 1); t += B) {
-          const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-          const unsigned long long a = keys[i], c = keys[l];
-          const bool up = (i & k2) == 0;
-          if ((a > c) == up) {
-            keys[i] = c;
-            keys[l] = a;
-          }
-        }
-        __syncthreads();
-      }
-    for (unsigned j = tid; j < mp + 4; j += B) {
-      if (j < m) {
-        const unsigned k = (unsigned)(keys[j] & 0xffffffffull);
-        const double x = dst[(size_t)k * 2], y = dst[(size_t)k * 2 + 1];
-        tx[j] = x;
-        ty[j] = y;
-        g4[j] = make_float4((float)(x - cx), (float)(y - cy), 0.f, __uint_as_float(k));
-        if (k == 0) C->pos0 = j;
-        if ((x != x) | (y != y)) C->bail = 1;  // a NaN target: the single call decides what such a cloud is
-      } else {  // pads: beyond every bound
-        g4[j] = make_float4(__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf(), __uint_as_float(0xffffffffu));
-      }
-    }
-    __syncthreads();
-  }
+  tiny_sort_targets<2, B>(dst, cx, cy, cz, reinterpret_cast<unsigned long long *>(shared), tg,
+                          [&](unsigned j, unsigned k, double x, double y) {
+                            if (k == 0) C->pos0 = j;
+                            if ((x != x) | (y != y)) C->bail = 1;  // a NaN target: the single call decides what such a cloud is
+                          });
   if (C->bail) {  // (uniform)
     if (tid == 0) res->status = -1;
     return;
@@ -310,7 +150,7 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
         uint32_t *bi = li + tid;
         const double x = tx[j], y = ty[j];
         const float4 own = g4[j];
-        const double ec = (fmax(fabs(x - cx), fabs(y - cy)) + 2. * scale) * 1.2e-7 * 1.7320508075688774;
+        const double ec = tiny_screen_margin(x - cx, y - cy, 0., scale);
         // The k best are kept UNORDERED while the sweep runs, with the worst of them -- its (d^2, index) and its slot --
         // in registers: a candidate is refused without touching the list, an accepted one replaces the worst and the
         // new worst is found by k independent reads (a sorted insertion is a chain of dependent LDS accesses as long as
@@ -341,12 +181,12 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
                 wq = q;
               }
             }
-            thr = line_screen_bound(wd, ec);
+            thr = tiny_screen_bound(wd, ec);
           }
         };
         // outwards from the target's own position while a target's x alone does not rule it out: the f32 difference is
         // within ec of the true one and thr carries that margin, so fx^2 > thr  =>  strictly farther than the k-th best.
-        // Four targets per step, their LDS reads in flight together (tiny_estimate_body.inc); unlike a nearest-neighbour
+        // Four targets per step, their LDS reads in flight together (as tiny_nearest); unlike a nearest-neighbour
         // search a list must not be offered a target twice, so a step's slots past either end are masked, not repeated.
         auto visit = [&](const float4 g, unsigned jj, bool valid) {
           const float fx = own.x - g.x, fy = own.y - g.y;
@@ -399,8 +239,7 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
     }
     __syncthreads();
   }
-  unsigned long long(*sbuf)[B] = reinterpret_cast<unsigned long long(*)[B]>(shared);  // two sort buffers ...
-  unsigned long long *S = &sbuf[2][0];                                                 // ... and the sorted keys
+  unsigned long long(*sbuf)[1][B] = reinterpret_cast<unsigned long long(*)[1][B]>(shared);  // two sort buffers, then the sorted keys
   const bool has = tid < n;
   double px = 0., py = 0.;
   if (has) {
@@ -408,71 +247,17 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
     py = src[(size_t)tid * 2 + 1];
   }
   const int blocks = n > 512u ? 2 : 1;  // reduce_geometry(n) for n <= 1024: 512-thread blocks
-  const unsigned lo_rank = (n - 1) / 2, hi_rank = n / 2;
   unsigned bi = 0xffffffffu;
   for (unsigned it = 0; it < max_iter; ++it) {
     const Pose T = C->T;
-    // ---- transform + exact nearest neighbour (tiny_estimate_body.inc), the pair of k_line_gather ----
+    // ---- transform + exact nearest neighbour, the pair of k_line_gather ----
     PlanePair pr;
     pr.ax = pr.ay = pr.qx = pr.qy = pr.dz = pr.nx = pr.ny = pr.nz = 0.;
     if (has) {
       const double qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24
       const double qy = (T.r10 * px + T.r11 * py) + T.ty;
-      const double ox = qx - cx, oy = qy - cy;
-      const float hx = (float)ox, hy = (float)oy;
-      const double ec = (fmax(fabs(ox), fabs(oy)) + 2. * scale) * 1.2e-7 * 1.7320508075688774;
-      double best = __builtin_huge_val();
-      float thr = __builtin_huge_valf();
-      unsigned nb = 0xffffffffu, nbo = 0xffffffffu;  // sorted position / original index of the best so far
-      auto exact = [&](unsigned j, unsigned orig) {
-        const double dx = qx - tx[j], dy = qy - ty[j];
-        const double d = dx * dx + dy * dy;
-        if (d < best || (d == best && orig < nbo)) {  // ties -> lowest ORIGINAL index
-          best = d;
-          nb = j;
-          nbo = orig;
-          thr = line_screen_bound(d, ec);
-        }
-      };
-      // start: the previous match (warm), else the first target at or right of the query's x
-      unsigned start;
-      if (bi != 0xffffffffu) {
-        start = bi;
-        exact(bi, __float_as_uint(g4[bi].w));
-      } else {
-        unsigned lo = 0, hi = m;
-        while (lo < hi) {
-          const unsigned mid = (lo + hi) >> 1;
-          if (g4[mid].x < hx) lo = mid + 1;
-          else hi = mid;
-        }
-        start = lo < m ? lo : m - 1;
-      }
-      auto visit = [&](const float4 g, unsigned j) {  // (beyond the x bound: s2 > thr as well)
-        const float fx = hx - g.x, fy = hy - g.y;
-        const float s2 = __builtin_fmaf(fy, fy, fx * fx);
-        if (!(s2 > thr) && j < m) exact(j, __float_as_uint(g.w));
-      };
-      for (unsigned j = start; j < m; j += 4) {  // (g4 carries four +inf pads past mp)
-        const float4 g0 = g4[j], g1 = g4[j + 1], g2 = g4[j + 2], g3 = g4[j + 3];
-        const float f0 = hx - g0.x;
-        if (f0 * f0 > thr) break;  // sorted by x: everything further right is farther still
-        visit(g0, j);
-        visit(g1, j + 1);
-        visit(g2, j + 2);
-        visit(g3, j + 3);
-      }
-      for (unsigned j = start; j > 0;) {
-        const unsigned j0 = j - 1, j1 = j > 1 ? j - 2 : 0, j2 = j > 2 ? j - 3 : 0, j3 = j > 3 ? j - 4 : 0;
-        const float4 g0 = g4[j0], g1 = g4[j1], g2 = g4[j2], g3 = g4[j3];  // (a repeated target is harmless)
-        const float f0 = hx - g0.x;
-        if (f0 * f0 > thr) break;
-        visit(g0, j0);
-        visit(g1, j1);
-        visit(g2, j2);
-        visit(g3, j3);
-        j = j3;
-      }
+      unsigned nb, nbo;  // sorted position / original index of the nearest target
+      tiny_nearest<2>(tg, qx, qy, 0., cx, cy, cz, scale, bi, &nb, &nbo);
       bi = nb;
       if (nb == 0xffffffffu) {  // no finite distance (NaN query): index 0, as a scan from 0 would
         nb = C->pos0;
@@ -492,8 +277,8 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
       C->Ti = transform_identity();
       C->done = n < 2u ? 1 : 0;  // fewer than two pairs: the identity, no update
       C->applied = 0;
+      C->prev_error = 1.7976931348623157e308;  // DBL_MAX
     }
-    double prev_error = 1.7976931348623157e308;  // DBL_MAX (thread 0 only)
     __syncthreads();
     for (int k = 0; k < ICP_INNER_MAX_ITER && !C->done; ++k) {
       const Pose Ti = C->Ti;
@@ -504,15 +289,11 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
       }
       // exact median and MAD of r (launch_stddevs on ((r, 0), (0, 0)) under the identity: dimension 0's statistics of
       // ((1 r + 0 0) + 0) - 0 = r, which plane_residual's trailing + nz dz = + 0.0 has already rid of a -0.0)
-      unsigned long long key = has ? f2k(r) : ~0ull;
-      line_sort_keys<B>(key, sbuf);
-      S[tid] = key;
-      __syncthreads();
-      const double xl = k2f(S[lo_rank]), xh = k2f(S[hi_rank]);
-      const double med = (n & 1) ? xl : (xl + xh) / 2.;  // src/stats.rs:18-27
-      line_mad_ranks(S, n, med, lo_rank, hi_rank, C->mad);
-      __syncthreads();
-      const double sigma = ICP_PPF34 * ((n & 1) ? C->mad[0] : (C->mad[0] + C->mad[1]) / 2.);  // src/stats.rs:42-46
+      unsigned long long key[1] = {has ? f2k(r) : ~0ull};
+      double med[1], sig[1];
+      tiny_bitonic_sort<B, 1>(key, sbuf);
+      tiny_sorted_median_sigma<B, 1>(key, sbuf[2], n, C->mad, med, sig);  // (a third buffer: no barrier behind the sort)
+      const double sigma = sig[0];
       // k_p2pl_accumulate's terms, one pair per thread, folded as block_reduce_store folds a 512-thread block
       {
         double acc[kLineSums];
@@ -556,47 +337,10 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
         tot[tid] = ((0. + p0) + p1) + 0.;
       }
       __syncthreads();
-      if (tid == 0) {
-        ++C->evals;
-        double delta[3];
-        if (C->nan) {
-          C->done = 1;  // ICP_NAN_INPUT
-        } else if (!solve_update(tot, tot + 9, delta)) {
-          C->done = 1;
-        } else if ((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < ICP_DELTA_NORM_THRESHOLD) {
-          C->done = 1;
-        } else if (tot[12] > prev_error) {
-          C->done = 1;
-        } else {
-          prev_error = tot[12];
-          bool in_range;
-          const Pose D = transform_new_in_range(delta, &in_range);
-          if (!in_range) {
-            C->bail = 1;  // a rotation beyond the restated range of sin / cos: the single call's host serves
-            C->done = 1;
-          } else {
-            C->Ti = transform_mul(D, Ti);
-            ++C->applied;
-          }
-        }
-      }
+      if (tid == 0) tiny_inner_decide(C, tot);
       __syncthreads();
     }
-    if (tid == 0) {
-      if (inner_out) inner_out[it] = C->applied;
-      C->T = transform_mul(C->Ti, T);
-      // An outer iteration that leaves the pose as it found it, bit for bit, is a fixed point of the loop: every later
-      // iteration repeats it (tiny_estimate_body.inc).  Only the last one still runs: it reports the correspondences.
-      const Pose &Tn = C->T;
-      C->fixed = C->applied == 0 && __double_as_longlong(Tn.tx) == __double_as_longlong(T.tx) &&
-                 __double_as_longlong(Tn.ty) == __double_as_longlong(T.ty) &&
-                 __double_as_longlong(Tn.r00) == __double_as_longlong(T.r00) &&
-                 __double_as_longlong(Tn.r01) == __double_as_longlong(T.r01) &&
-                 __double_as_longlong(Tn.r10) == __double_as_longlong(T.r10) &&
-                 __double_as_longlong(Tn.r11) == __double_as_longlong(T.r11);
-      if (C->fixed && it + 2 < max_iter && inner_out)
-        for (unsigned k = it + 1; k + 1 < max_iter; ++k) inner_out[k] = 0;
-    }
+    if (tid == 0) tiny_outer_tail(C, it, max_iter, inner_out);
     __syncthreads();
     if (C->nan | C->bail) break;
     if (C->fixed && it + 2 < max_iter) it = max_iter - 2;  // (uniform: the flag is the workgroup's)
@@ -613,16 +357,10 @@ hipError_t launch_line_estimate_batch(unsigned threads, unsigned m_max, const do
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
                                       TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted) {
   // the grant above 64 KB of dynamic LDS, asked for both kernels once per process; refused: nothing launches
-  static int lds_granted = 0;  // 0 not asked yet, 1 yes, -1 refused
-  if (lds_granted == 0) {
-    const void *kernels[] = {reinterpret_cast<const void *>(&k_line_estimate_batch<512>),
-                             reinterpret_cast<const void *>(&k_line_estimate_batch<1024>)};
-    lds_granted = 1;
-    for (const void *kn : kernels)
-      if (hipFuncSetAttribute(kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLineLdsGrant) != hipSuccess) lds_granted = -1;
-    if (lds_granted < 0) (void)hipGetLastError();
-  }
-  *granted = lds_granted > 0;
+  static TinyLdsGrant grant;
+  *granted = grant.ask({reinterpret_cast<const void *>(&k_line_estimate_batch<512>),
+                        reinterpret_cast<const void *>(&k_line_estimate_batch<1024>)},
+                       kTinyLdsGrant);
   if (!*granted || count == 0) return hipSuccess;
   const LinePlan plan = line_batch_plan(threads, m_max);
   if (threads == 512u)

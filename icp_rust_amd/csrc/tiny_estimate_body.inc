@@ -1,7 +1,7 @@
 // The body of the one-workgroup registration (Icp{2,3}d::estimate of up to 1024 source / 2048 target points), textually
 // included by both kernels that run it -- k_tiny_estimate (one problem per launch) and k_tiny_estimate_batch (one problem
-// per workgroup), gn_fast.hip -- so that the two cannot drift apart and the single kernel compiles exactly as it did when
-// the body was written inline.  The including function has in scope, under these names:
+// per workgroup), gn_fast.hip -- so that the two cannot drift apart.  The pieces k_line_estimate_batch (p2line_batch.hip)
+// runs too are functions of tiny_device.hpp.  The including function has in scope, under these names:
 //   DIM, B                 template parameters (dimension; threads per workgroup, a multiple of 64)
 //   src, n                 the source points (DIM doubles each) and their count, 1 <= n <= B
 //   dst, m                 the target points and their count, 1 <= m <= 2048
@@ -27,13 +27,12 @@
   p += sizeof(double) * 16 * (kNSum + 1);
   double(*part)[kNSum + 1] = reinterpret_cast<double(*)[kNSum + 1]>(p);
   p += sizeof(double) * 2 * (kNSum + 1);
-  struct Ctl {
-    Pose Ti, T;
+  struct Ctl : TinyCtl {
     double s_mad[2][2];
-    int done, nan, bail, fixed;
-    unsigned applied, evals, sorted;
+    unsigned sorted;
   };
   Ctl *C = reinterpret_cast<Ctl *>(p);
+  const TinyTargets tg = {tx, ty, tz, g4, m};
 
   const unsigned tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -51,52 +50,8 @@
 #else
 #define TINY_STAMP(slot) ((void)0)
 #endif
-  // Targets sorted by x (once per call): keys = (order-preserving bits of fl32(x - cx), index), bitonic
-  // sort of the next power of two in LDS.  A sweep then visits only targets whose x lies within the
-  // current best distance of the query's -- a few of them instead of all m (sweep and prune; exact:
-  // a target with |dx| > sqrt(best) is strictly farther).
-  {
-    unsigned long long *keys = &sbuf[0][0][0];  // 4096 slots: room for 2048 keys
-    unsigned P = 64;
-    while (P < m) P <<= 1;
-    for (unsigned k = tid; k < P; k += B) {
-      unsigned long long key = ~0ull;
-      if (k < m) {
-        const unsigned u = __float_as_uint((float)(dst[(size_t)k * DIM] - cx));
-        const unsigned o = (u >> 31) ? ~u : (u | 0x80000000u);
-        key = ((unsigned long long)o << 32) | k;
-      }
-      keys[k] = key;
-    }
-    __syncthreads();
-    for (unsigned kk = 2; kk <= P; kk <<= 1)
-      for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-        for (unsigned t = tid; t < (P >> 1); t += B) {
-          const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-          const unsigned long long a = keys[i], c = keys[l];
-          const bool up = (i & kk) == 0;
-          if ((a > c) == up) {
-            keys[i] = c;
-            keys[l] = a;
-          }
-        }
-        __syncthreads();
-      }
-    for (unsigned j = tid; j < mp + 4; j += B) {
-      if (j < m) {
-        const unsigned k = (unsigned)(keys[j] & 0xffffffffull);
-        const double x = dst[(size_t)k * DIM], y = dst[(size_t)k * DIM + 1];
-        const double z = DIM == 3 ? dst[(size_t)k * DIM + 2] : 0.;
-        tx[j] = x;
-        ty[j] = y;
-        if (DIM == 3) tz[j] = z;
-        g4[j] = make_float4((float)(x - cx), (float)(y - cy), DIM == 3 ? (float)(z - cz) : 0.f, __uint_as_float(k));
-      } else {  // pads: beyond every bound
-        g4[j] = make_float4(__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf(), __uint_as_float(0xffffffffu));
-      }
-    }
-    __syncthreads();
-  }
+  // (the sorting path's buffers hold the target sort's keys meanwhile: 4096 slots, room for 2048 keys)
+  tiny_sort_targets<DIM, B>(dst, cx, cy, cz, &sbuf[0][0][0], tg, [](unsigned, unsigned, double, double) {});
   double px = 0., py = 0., pz = 0.;
   if (has) {
     px = src[(size_t)tid * DIM];
@@ -116,7 +71,6 @@
 
   __syncthreads();
   const int blocks = n > 512u ? 2 : 1;  // reduce_geometry(n) for n <= 1024: 512-thread blocks
-  const unsigned lo_rank = (n - 1) / 2, hi_rank = n / 2;
   unsigned bi = 0xffffffffu;
   TINY_STAMP(0);
   for (unsigned it = 0; it < max_iter; ++it) {
@@ -127,75 +81,8 @@
       const double qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24
       const double qy = (T.r10 * px + T.r11 * py) + T.ty;
       const double qz = pz;
-      const double ox = qx - cx, oy = qy - cy, oz = DIM == 3 ? qz - cz : 0.;
-      const float hx = (float)ox, hy = (float)oy, hz = (float)oz;
-      const double ec = (fmax(fmax(fabs(ox), fabs(oy)), fabs(oz)) + 2. * scale) * 1.2e-7 * 1.7320508075688774;
-      double best = __builtin_huge_val();
-      float thr = __builtin_huge_valf();
-      unsigned nb = 0xffffffffu, nbo = 0xffffffffu;  // sorted position / original index of the best so far
-      auto exact = [&](unsigned j, unsigned orig) {
-        const double dx = qx - tx[j], dy = qy - ty[j];
-        double d = dx * dx + dy * dy;
-        if (DIM == 3) {
-          const double dz = qz - tz[j];
-          d = d + dz * dz;
-        }
-        if (d < best || (d == best && orig < nbo)) {  // ties -> lowest ORIGINAL index
-          best = d;
-          nb = j;
-          nbo = orig;
-          const double rr = sqrt(d) + ec;
-          thr = (float)(rr * rr * 1.000004) * 1.000001f + 1e-37f;  // rounded up (nn_brute.hip)
-        }
-      };
-      // start: the previous match (warm), else the first target at or right of the query's x
-      unsigned start;
-      if (bi != 0xffffffffu) {
-        start = bi;
-        exact(bi, __float_as_uint(g4[bi].w));
-      } else {
-        unsigned lo = 0, hi = m;
-        while (lo < hi) {
-          const unsigned mid = (lo + hi) >> 1;
-          if (g4[mid].x < hx) lo = mid + 1;
-          else hi = mid;
-        }
-        start = lo < m ? lo : m - 1;
-      }
-      // outwards in both directions while a target's x alone does not rule it out.  The f32 x
-      // difference is within ec of the true one, so (|dx| - ec)^2 > best is what rules out; thr already
-      // carries that margin: dx^2 > thr  =>  strictly farther.
-      auto visit = [&](const float4 g, unsigned j) {  // (beyond the x bound: s2 > thr as well)
-        const float fx = hx - g.x, fy = hy - g.y;
-        float s2 = __builtin_fmaf(fy, fy, fx * fx);
-        if (DIM == 3) {
-          const float fz = hz - g.z;
-          s2 = __builtin_fmaf(fz, fz, s2);
-        }
-        if (!(s2 > thr) && j < m) exact(j, __float_as_uint(g.w));
-      };
-      // four targets per step (their LDS reads in flight together: one CU has little else to hide the
-      // latency with, and a wave is as slow as its lane with the widest window)
-      for (unsigned j = start; j < m; j += 4) {  // (g4 carries four +inf pads past mp)
-        const float4 g0 = g4[j], g1 = g4[j + 1], g2 = g4[j + 2], g3 = g4[j + 3];
-        const float f0 = hx - g0.x;
-        if (f0 * f0 > thr) break;  // sorted by x: everything further right is farther still
-        visit(g0, j);
-        visit(g1, j + 1);
-        visit(g2, j + 2);
-        visit(g3, j + 3);
-      }
-      for (unsigned j = start; j > 0;) {
-        const unsigned j0 = j - 1, j1 = j > 1 ? j - 2 : 0, j2 = j > 2 ? j - 3 : 0, j3 = j > 3 ? j - 4 : 0;
-        const float4 g0 = g4[j0], g1 = g4[j1], g2 = g4[j2], g3 = g4[j3];  // (a repeated target is harmless)
-        const float f0 = hx - g0.x;
-        if (f0 * f0 > thr) break;
-        visit(g0, j0);
-        visit(g1, j1);
-        visit(g2, j2);
-        visit(g3, j3);
-        j = j3;
-      }
+      unsigned nb, nbo;  // sorted position / original index of the nearest target
+      tiny_nearest<DIM>(tg, qx, qy, qz, cx, cy, cz, scale, bi, &nb, &nbo);
       bi = nb;
       ax = qx;
       ay = qy;
@@ -214,8 +101,8 @@
       C->Ti = transform_identity();
       C->done = n < 2u ? 1 : 0;  // check_input_size, src/lib.rs:186-189
       C->applied = 0;
+      C->prev_error = 1.7976931348623157e308;  // f64::MAX
     }
-    double prev_error = 1.7976931348623157e308;  // f64::MAX (thread 0 only)
     __syncthreads();
     TINY_STAMP(1);
     for (int k = 0; k < ICP_INNER_MAX_ITER && !C->done; ++k) {
@@ -248,24 +135,13 @@
       }
       if (!ok) {  // (uniform: every thread saw the same list counts)
         if constexpr (B == 1024) {  // the sorting path of k_tiny_eval
-          unsigned long long ka = has ? f2k(r0) : ~0ull, kb = has ? f2k(r1) : ~0ull;
+          unsigned long long key[2] = {has ? f2k(r0) : ~0ull, has ? f2k(r1) : ~0ull};
           __syncthreads();
-          bitonic_sort2_1024(ka, kb, sbuf);
+          tiny_bitonic_sort<1024, 2>(key, sbuf);
           __syncthreads();
-          sbuf[0][0][tid] = ka;
-          sbuf[0][1][tid] = kb;
-          __syncthreads();
-          const double xl = k2f(sbuf[0][0][lo_rank]), xh = k2f(sbuf[0][0][hi_rank]);
-          const double yl = k2f(sbuf[0][1][lo_rank]), yh = k2f(sbuf[0][1][hi_rank]);
-          med[0] = (n & 1) ? xl : (xl + xh) / 2.;
-          med[1] = (n & 1) ? yl : (yl + yh) / 2.;
-          mad_ranks(sbuf[0][0], n, med[0], lo_rank, hi_rank, C->s_mad[0]);
-          mad_ranks(sbuf[0][1], n, med[1], lo_rank, hi_rank, C->s_mad[1]);
-          __syncthreads();
-          sig[0] = ICP_PPF34 * ((n & 1) ? C->s_mad[0][0] : (C->s_mad[0][0] + C->s_mad[0][1]) / 2.);
-          sig[1] = ICP_PPF34 * ((n & 1) ? C->s_mad[1][0] : (C->s_mad[1][0] + C->s_mad[1][1]) / 2.);
+          tiny_sorted_median_sigma<1024, 2>(key, sbuf[0], n, C->s_mad, med, sig);
           if (tid == 0) ++C->sorted;
-        } else {  // the sort is written for 1024 threads: hand the call back, the host-driven path serves
+        } else {  // the sorting path runs at 1024 threads only: hand the call back, the host-driven path serves
           med[0] = med[1] = sig[0] = sig[1] = 0.;
           if (tid == 0) C->bail = 1;
         }
@@ -315,50 +191,11 @@
       __syncthreads();
       if (tid < kNAcc) sm[1][tid] = combine_sum(sm[0], (int)tid, sig);
       __syncthreads();
-      if (tid == 0) {
-        const double *tot = sm[1];
-        ++C->evals;
-        double delta[3];
-        if (C->nan | C->bail) {
-          C->done = 1;
-        } else if (!solve_update(tot, tot + 9, delta)) {
-          C->done = 1;  // None, src/lib.rs:67-69
-        } else if ((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < ICP_DELTA_NORM_THRESHOLD) {
-          C->done = 1;  // src/lib.rs:71-73
-        } else if (tot[12] > prev_error) {
-          C->done = 1;  // src/lib.rs:75-78
-        } else {
-          prev_error = tot[12];
-          bool in_range;
-          const Pose D = transform_new_in_range(delta, &in_range);
-          if (!in_range) {
-            C->bail = 1;  // a rotation beyond the restated range of sin / cos: the host-driven path serves
-            C->done = 1;
-          } else {
-            C->Ti = transform_mul(D, Ti);  // src/lib.rs:81
-            ++C->applied;
-          }
-        }
-      }
+      if (tid == 0) tiny_inner_decide(C, sm[1]);
       __syncthreads();
       TINY_STAMP(4);
     }
-    if (tid == 0) {
-      if (inner_out) inner_out[it] = C->applied;
-      C->T = transform_mul(C->Ti, T);  // src/lib.rs:127, 170
-      // An outer iteration that leaves the pose as it found it, bit for bit, is a fixed point of the loop: every
-      // later iteration repeats it (correspondences and updates are functions of the pose and the two clouds).  Only
-      // the last one still runs -- it is the one that reports the correspondences.
-      const Pose &Tn = C->T;
-      C->fixed = C->applied == 0 && __double_as_longlong(Tn.tx) == __double_as_longlong(T.tx) &&
-                 __double_as_longlong(Tn.ty) == __double_as_longlong(T.ty) &&
-                 __double_as_longlong(Tn.r00) == __double_as_longlong(T.r00) &&
-                 __double_as_longlong(Tn.r01) == __double_as_longlong(T.r01) &&
-                 __double_as_longlong(Tn.r10) == __double_as_longlong(T.r10) &&
-                 __double_as_longlong(Tn.r11) == __double_as_longlong(T.r11);
-      if (C->fixed && it + 2 < max_iter && inner_out)
-        for (unsigned k = it + 1; k + 1 < max_iter; ++k) inner_out[k] = 0;
-    }
+    if (tid == 0) tiny_outer_tail(C, it, max_iter, inner_out);
     __syncthreads();
     if (C->nan | C->bail) break;
     if (C->fixed && it + 2 < max_iter) it = max_iter - 2;  // (uniform: the flag is the workgroup's)

@@ -8,6 +8,7 @@ allocation granule 8):
   * the stage kernels of a sharded evaluation (k_win_compact) run beside three search waves.
 A few registers more in any of these kernels silently turns the overlap back into a queue, so the budget is pinned
 here (hipcc cross-compiles without a GPU; -Rpass-analysis prints the allocation)."""
+import functools
 import os
 import re
 import shutil
@@ -34,6 +35,7 @@ BUDGET = {  # demangled-name fragment -> max VGPRs
 }
 
 
+@functools.lru_cache(maxsize=None)
 def usage(src):
     out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
                           "-I" + os.path.join(ROOT, "include"), "-c", os.path.join(CSRC, src), "-o", os.devnull,
@@ -87,3 +89,30 @@ def test_small_cloud_kernel_does_not_spill_in_the_workgroup_sizes_the_reference_
         names = [k for k in regs if "k_tiny_estimateILi2ELj%dE" % b in k and not k.endswith("#scratch")]
         assert len(names) == 1, names
         assert regs.get(names[0] + "#scratch", 0) <= spill_cap, (names[0], regs.get(names[0] + "#scratch"))
+
+
+# (VGPRs, scratch bytes per lane) of every one-workgroup estimator as the build before csrc/tiny_device.hpp reported
+# them through usage(): the pieces these kernels share may not cost any of them a register or a spilled byte
+ONE_WORKGROUP_BEFORE_SHARING = {
+    "gn_fast.hip": {
+        "k_tiny_evalE": (111, 0),
+        "k_tiny_estimateILi2ELj512E": (142, 0), "k_tiny_estimateILi2ELj768E": (139, 0), "k_tiny_estimateILi2ELj1024E": (128, 72),
+        "k_tiny_estimateILi3ELj512E": (147, 0), "k_tiny_estimateILi3ELj768E": (144, 0), "k_tiny_estimateILi3ELj1024E": (128, 100),
+        "k_tiny_estimate_batchILi2ELj512E": (143, 0), "k_tiny_estimate_batchILi2ELj768E": (143, 0),
+        "k_tiny_estimate_batchILi2ELj1024E": (128, 92),
+        "k_tiny_estimate_batchILi3ELj512E": (148, 0), "k_tiny_estimate_batchILi3ELj768E": (148, 0),
+        "k_tiny_estimate_batchILi3ELj1024E": (128, 104),
+    },
+    "p2line_batch.hip": {"k_line_estimate_batchILj512E": (135, 0), "k_line_estimate_batchILj1024E": (128, 48)},
+}
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+@pytest.mark.parametrize("src", sorted(ONE_WORKGROUP_BEFORE_SHARING))
+def test_one_workgroup_estimators_need_no_more_registers_or_scratch_than_before_their_pieces_were_shared(src):
+    regs = usage(src)
+    for frag, (vgprs, scratch) in ONE_WORKGROUP_BEFORE_SHARING[src].items():
+        names = [k for k in regs if frag in k and not k.endswith("#scratch")]
+        assert len(names) == 1, (frag, names)
+        assert regs[names[0]] <= vgprs, f"{names[0]}: {regs[names[0]]} VGPRs > {vgprs}"
+        assert regs.get(names[0] + "#scratch", 0) <= scratch, f"{names[0]}: {regs.get(names[0] + '#scratch')} B of scratch > {scratch}"
