@@ -1374,56 +1374,131 @@ __device__ __forceinline__ void warm_wave(const unsigned k, const unsigned n, co
   // box (half of the vector instructions of the first version of this kernel: profiles/r04_search_coop.txt).  A row
   // is taken over the whole x range of the box: clipping it to the ball per row (warm_query) saved fewer records than
   // its sqrt, two floors and eleven registers cost here, where the records are spread over the wave anyway.
+  //
+  // (round 8) The tile is evaluated as far as the WAVE needs it.  The queries are cell-sorted, so a wave is homogeneous:
+  // on the benchmark pair most waves hold boxes of 1-2 x 1 rows, the rest 3 x 3, and the sixteen entries cost every one
+  // of them eight slab distances and sixteen combinations.  An entry (jy, jz) with ty + jy > hi_c[1] or tz + jz > hi_c[2]
+  // has a zero bit whatever its slab distance is; ny / nz (1, 2 or 4: two ballots per axis, scalar registers) bound the
+  // entries that some lane of the call can have valid, and the others are skipped under wave-uniform branches -- their
+  // bits stay 0, the arithmetic of every entry that is evaluated is what it was.  Lanes outside `on` run along and keep
+  // their mask.
   int ty = lo_c[1], tz = lo_c[2];
   unsigned mask = 0;
-  auto make_mask = [&]() {
+  auto make_mask = [&](const bool on) {
+    int ny = 1, nz = 1;
+    if (__ballot(on && ty + 1 <= hi_c[1]) != 0ull) ny = 2;
+    if (__ballot(on && ty + 2 <= hi_c[1]) != 0ull) ny = 4;
+    if (DIM == 3) {
+      if (__ballot(on && tz + 1 <= hi_c[2]) != 0ull) nz = 2;
+      if (__ballot(on && tz + 2 <= hi_c[2]) != 0ull) nz = 4;
+    }
     bool vy[4], vz[4];
     float sy[4], sz[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    unsigned m = 0;
+    auto ey = [&](const int j) {
       vy[j] = ty + j <= hi_c[1];
       sy[j] = wide ? 0.f : slab2(1, ty + j);
+    };
+    auto ez = [&](const int j) {
       vz[j] = tz + j <= hi_c[2];
       sz[j] = (DIM == 3 && !wide) ? slab2(2, tz + j) : 0.f;
+    };
+    auto row = [&](const int jz) {  // the entries of one z: as many as the wave has in y
+      auto bit = [&](const int jy) {
+        if (vy[jy] && vz[jz] && !(sy[jy] + sz[jz] > bf)) m |= 1u << (jz * 4 + jy);
+      };
+      bit(0);
+      if (ny > 1) bit(1);
+      if (ny > 2) {
+        bit(2);
+        bit(3);
+      }
+    };
+    ey(0);
+    if (ny > 1) ey(1);
+    if (ny > 2) {
+      ey(2);
+      ey(3);
     }
-    mask = 0;
-#pragma unroll
-    for (int jz = 0; jz < (DIM == 3 ? 4 : 1); ++jz)
-#pragma unroll
-      for (int jy = 0; jy < 4; ++jy)
-        if (vy[jy] && vz[jz] && !(sy[jy] + sz[jz] > bf)) mask |= 1u << (jz * 4 + jy);
+    ez(0);
+    row(0);
+    if (DIM == 3 && nz > 1) {
+      ez(1);
+      row(1);
+      if (nz > 2) {
+        ez(2);
+        ez(3);
+        row(2);
+        row(3);
+      }
+    }
+    if (on) mask = m;
   };
-  if (alive) make_mask();
+  make_mask(alive);  // (a lane that is not alive keeps the empty mask)
+  // boxes of more than one tile: rare (none in most waves of the benchmark pair), and the only ones that ever need the next tile
+  const bool wave_tiles = __ballot(alive && (hi_c[1] - lo_c[1] >= 4 || hi_c[2] - lo_c[2] >= 4)) != 0ull;
 #ifdef ICP_COOP_PROFILE
   unsigned rows_total = 0;
 #endif
   for (;;) {
     // ---- owner: the next rows of its box ----
+    // (round 8) Straight-line code and registers: "lowest bit of the mask -> row base" as many times as the wave's fullest
+    // mask asks for, kCoopRows at most, the bases kept in rlo / rhi for the loads of the bounds below (they used to travel
+    // through S.rows_d / S.rows_o and back, behind a loop that ran as long as the wave's slowest lane).  A lane fills its
+    // slots from 0 upwards; a slot without a row holds cell 0 (a cached address, no branch).  A lane that is not alive
+    // has an empty mask.
+    // (44.96 -> 42.76 us per warm search at 1M, 1 097 -> 1 017 vector instructions per wave; kCoopRows passes in every round
+    // ran MORE of them than the loop and gained nothing: profiles/r08_search_owner_phase_ab.txt)
     int nr = 0;
-    S.rows_d[lane][0] = 0u;  // (a lane without rows reads the bounds of cell 0 below: a cached address, no branch)
-    S.rows_o[lane][0] = 0u;
-    while (alive && nr < kCoopRows) {
-      if (mask == 0) {  // the next tile of the box: along y, then z
-        ty += 4;
-        if (ty > hi_c[1]) {
-          ty = lo_c[1];
-          tz += 4;
-        }
-        if (tz > hi_c[2]) {
-          alive = false;
-          break;
-        }
-        make_mask();
-        continue;
-      }
+    uint32_t rlo[kCoopRows], rhi[kCoopRows];
+#pragma unroll
+    for (int r = 0; r < kCoopRows; ++r) rlo[r] = rhi[r] = 0u;
+    auto pick = [&](const bool on, uint32_t &d, uint32_t &o) -> bool {  // the lane's next row, if its tile has one left
+      const bool take = on && mask != 0u;
       const int r = __ffs((int)mask) - 1;
-      mask &= mask - 1u;
+      if (on) mask &= mask - 1u;
       const int jy = r & 3, jz = r >> 2;
       const uint32_t rb = ((uint32_t)(tz + jz) * g.n[1] + (uint32_t)(ty + jy)) * g.n[0];
-      S.rows_d[lane][nr] = rb + lo_c[0];  // (the tables of the round are written after these have been read back)
-      S.rows_o[lane][nr] = rb + hi_c[0] + 1;
-      ++nr;
+      if (take) {
+        d = rb + lo_c[0];
+        o = rb + hi_c[0] + 1;
+      }
+      return take;
+    };
+#pragma unroll
+    for (int r = 0; r < kCoopRows; ++r) {
+      if (__ballot(mask != 0u) == 0ull) break;
+      nr += pick(true, rlo[r], rhi[r]) ? 1 : 0;
     }
+    // The tile is used up and the round has room: the next tile of the box, along y, then z, until the round is full or
+    // the box is done -- one step of the former loop per pass (a new tile, or one more row into slot nr), for the lanes
+    // that need it.  Only a wave that holds a box of more than one tile comes here: a lane whose box is one tile is done
+    // when its mask is empty, alive or not.
+    if (wave_tiles)
+      for (bool need = alive && nr < kCoopRows; __ballot(need) != 0ull; need = alive && nr < kCoopRows) {
+        const bool adv = need && mask == 0u;
+        if (adv) {
+          ty += 4;
+          if (ty > hi_c[1]) {
+            ty = lo_c[1];
+            tz += 4;
+          }
+          if (tz > hi_c[2]) alive = false;
+        }
+        if (__ballot(adv && alive) != 0ull) make_mask(adv && alive);
+        const bool more = need && !adv;  // a row of the tile made by the pass before
+        if (__ballot(more) != 0ull) {
+          uint32_t d = 0u, o = 0u;
+          const bool take = pick(more, d, o);
+#pragma unroll
+          for (int r = 0; r < kCoopRows; ++r)
+            if (take && nr == r) {
+              rlo[r] = d;
+              rhi[r] = o;
+            }
+          nr += take ? 1 : 0;
+        }
+      }
     if (__ballot(nr > 0) == 0ull) break;
 #ifdef ICP_COOP_PROFILE
     rows_total += (unsigned)nr;
@@ -1433,9 +1508,8 @@ __device__ __forceinline__ void warm_wave(const unsigned k, const unsigned n, co
     uint32_t sb[kCoopRows], se[kCoopRows];
 #pragma unroll
     for (int r = 0; r < kCoopRows; ++r) {
-      const int rr = r < nr ? r : 0;  // unused slots repeat row 0 (a cached address)
-      sb[r] = start[S.rows_d[lane][rr]];
-      se[r] = start[S.rows_o[lane][rr]];
+      sb[r] = start[rlo[r]];
+      se[r] = start[rhi[r]];
     }
     uint32_t rd[kCoopRows], ro[kCoopRows], Q = 0;
 #pragma unroll
