@@ -231,6 +231,7 @@ hipError_t launch_target_normals(icp_handle *h, int k, double *d_normals, size_t
 
 hipError_t launch_p2pl_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
                               const double *d_normals, void *d_pairs) {
+  if (n == 0) return hipSuccess;  // (an empty scan: no pair, and a grid of no workgroups is not a launch)
   hipLaunchKernelGGL(k_p2pl_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_src, (unsigned)n, T,
                      d_idx, h->d_dst, d_normals, (PlanePair *)d_pairs);
   return hipGetLastError();

@@ -486,7 +486,10 @@ int icp_read_targets(icp_handle *h, size_t first, size_t k, double *out);
  * grid; after an append call it again, or icp_update_target_normals: only the appended targets get a
  * normal (from the cloud as it is now), the older ones keep theirs ("normals at insertion time": what a
  * map that grows frame by frame uses; same k as before).  icp_estimate_point_to_plane*: Icp3d::estimate
- * with the scalar residual n_q . (T p - q) in place of the two-row point-to-point residual. */
+ * with the scalar residual n_q . (T p - q) in place of the two-row point-to-point residual.  The pairs are
+ * folded in the caller's order (no snapshot order) in the tree of icp_reduce_geometry(n); the pose is bit-equal
+ * to the CPU restatement folded that way (tests/test_gpu_plane_parity.py).  An empty source cloud (n == 0)
+ * returns *init with every inner count 0, as Icp3d::estimate does on an empty scan. */
 int icp_compute_target_normals(icp_handle *h, int k);
 int icp_update_target_normals(icp_handle *h, int k);
 int icp_read_target_normals(icp_handle *h, size_t first, size_t count, double *out_xyz);

@@ -480,6 +480,17 @@ static void tree_combine(const double S[NACC], const double stddevs[2], double j
   }
 }
 
+/* second stage: ONE block of `threads` threads over `rows` rows of sums -- thread t left-folds rows t, t + threads, ...
+ * from zero, then the block's tree.  thr: scratch of `threads` rows. */
+static void tree_fold_rows(const double *rows, size_t nrows, int threads, double (*thr)[NACC], double total[NACC]) {
+  for (int t = 0; t < threads; ++t) {
+    for (int k = 0; k < NACC; ++k) thr[t][k] = 0.;
+    for (size_t i = (size_t)t; i < nrows; i += (size_t)threads)
+      for (int k = 0; k < NACC; ++k) thr[t][k] = thr[t][k] + rows[i * NACC + k];
+  }
+  tree_block_reduce(thr, threads, total);
+}
+
 int orc_weighted_gauss_newton_update_tree(const orc_pose *T, const double *a, const double *b,
                                           size_t n, int blocks, int threads, double delta[3],
                                           double *huber_err) {
@@ -495,7 +506,6 @@ int orc_weighted_gauss_newton_update_tree(const orc_pose *T, const double *a, co
   }
   size_t G = (size_t)blocks * (size_t)threads;
   double(*thr)[NACC] = (double(*)[NACC])malloc((size_t)threads * sizeof(*thr));
-  int stage2_threads = threads;
   size_t part_n = (size_t)blocks;
   double(*part)[NACC] = (double(*)[NACC])malloc(part_n * sizeof(*part));
   for (int blk = 0; blk < blocks; ++blk) {
@@ -509,12 +519,7 @@ int orc_weighted_gauss_newton_update_tree(const orc_pose *T, const double *a, co
   }
   /* stage 2: one block over the block sums */
   double total[NACC];
-  for (int t = 0; t < stage2_threads; ++t) {
-    for (int k = 0; k < NACC; ++k) thr[t][k] = 0.;
-    for (size_t i = t; i < part_n; i += stage2_threads)
-      for (int k = 0; k < NACC; ++k) thr[t][k] = thr[t][k] + part[i][k];
-  }
-  tree_block_reduce(thr, stage2_threads, total);
+  tree_fold_rows(&part[0][0], part_n, threads, thr, total);
   free(thr);
   free(part);
   free(res);
@@ -557,12 +562,7 @@ int orc_wgn_tree_fold(const double *partials /* blocks x 19, block order */, int
   if (threads % 64 != 0 || blocks < 1) return -1;
   double(*thr)[NACC] = (double(*)[NACC])malloc((size_t)threads * sizeof(*thr));
   double total[NACC];
-  for (int t = 0; t < threads; ++t) {
-    for (int k = 0; k < NACC; ++k) thr[t][k] = 0.;
-    for (int i = t; i < blocks; i += threads)
-      for (int k = 0; k < NACC; ++k) thr[t][k] = thr[t][k] + partials[(size_t)i * NACC + k];
-  }
-  tree_block_reduce(thr, threads, total);
+  tree_fold_rows(partials, (size_t)blocks, threads, thr, total);
   free(thr);
   if (huber_err) *huber_err = total[18];
   double jtj[9], jtr[3];
@@ -840,9 +840,10 @@ int orc_icp_estimate(int dim, const double *dst, size_t m, const double *src, si
  * restate from the reference here and NO parity claim is attached to these functions: they are an
  * independent CPU statement of the definition the library documents (include/icp_mi355x.h section
  * 7, icp_rust_amd/csrc/p2plane.hip) -- brute-force k nearest neighbours instead of the device's grid
- * walk, the reference's own left-fold sums instead of the device's tree -- used by
- * tests/test_p2plane.py for self-consistency.  Everything around the residual follows the cited
- * reference lines (inner loop lib.rs:59-84, weights :236-255, huber.rs, stats.rs, linalg.rs).
+ * walk, the reference's own left-fold sums or (sum_mode 1) the device's tree -- used by
+ * tests/test_p2plane.py for self-consistency and by tests/test_gpu_plane_parity.py for equality of
+ * bits.  Everything around the residual follows the cited reference lines (inner loop lib.rs:59-84,
+ * weights :236-255, huber.rs, stats.rs, linalg.rs).
  * ==================================================================================== */
 
 static void p2pl_jacobi3(double a[3][3], double v[3][3]) {
@@ -947,15 +948,93 @@ int orc_p2pl_normals_range(const double *dst, size_t m, size_t first, int k_, do
   return ORC_OK;
 }
 
-/* Icp3d::estimate (lib.rs:148-173) with the scalar residual n_q . (T p - q); sums as left folds */
+/* One pair's terms of the scalar-residual normal equations, added into acc[0..8] = jtj, acc[9..11] = jtr,
+ * acc[12] = Huber error (the slots of the device's k_p2pl_accumulate; the rest of the 19-wide row stays 0).
+ * The factor drho * (1 / sigma) is applied to every term, all nine products are evaluated, and with sigma == 0 only
+ * the Huber error is summed (lib.rs:243-245). */
+static inline void p2pl_accumulate_pair(const orc_pose *Ti, const double *st_i, const double *nq, double r,
+                                        double sigma, double acc[NACC]) {
+  double e = r * r;
+  if (sigma != 0.) {
+    double s2[2] = {st_i[0], st_i[1]}, J2[2][3];
+    jacobian(Ti, s2, J2);
+    double J[3];
+    for (int c = 0; c < 3; ++c) J[c] = nq[0] * J2[0][c] + nq[1] * J2[1][c];
+    double wg = orc_huber_drho(e, ORC_HUBER_K) * (1. / sigma);
+    for (int c = 0; c < 3; ++c) acc[9 + c] = acc[9 + c] + (wg * J[c]) * r;
+    for (int p = 0; p < 3; ++p)
+      for (int q2 = 0; q2 < 3; ++q2) acc[3 * p + q2] = acc[3 * p + q2] + (wg * J[p]) * J[q2];
+  }
+  acc[12] = acc[12] + orc_huber_rho(e, ORC_HUBER_K);
+}
+
+/* One evaluation of the inner loop: the residuals of the n pairs (st[i], dst[idx[i]]) under the inner pose Ti, their
+ * sigma = 1.4826 MAD, the thirteen sums and the solve.  sum_mode 0: the sums as left folds over i = 0 .. n-1 (the
+ * reference's way with its own sums).  sum_mode 1: the device's tree (k_p2pl_accumulate + k_final_reduce) -- thread
+ * g = block * threads + t folds pairs g, g + G, ... (G = blocks * threads) from zero, tree_block_reduce per block,
+ * then one block over the block sums; the thirteen sums ride in the tree's 19-wide rows.
+ * ORC_OK: delta is the update; ORC_NONE: fewer than two pairs or a singular solve (no update); ORC_NAN: a NaN
+ * residual.  sigma and huber_err are set whenever the status is not ORC_NAN and n >= 2. */
+int orc_p2pl_update(const orc_pose *Ti, const double *st, size_t n, const uint32_t *idx, const double *dst,
+                    const double *normals, int sum_mode, int reduce_blocks, int reduce_threads, double *sigma_out,
+                    double delta[3], double *huber_err) {
+  if (!check_input_size(n)) return ORC_NONE;
+  if (sum_mode == 1 && (reduce_threads < 64 || reduce_threads % 64 != 0 || reduce_blocks < 1)) return -1;
+  double *r = (double *)malloc(n * sizeof(double));
+  double *tmp = (double *)malloc(n * sizeof(double));
+  for (size_t i = 0; i < n; ++i) {
+    const double *q = dst + 3 * (size_t)idx[i], *nq = normals + 3 * (size_t)idx[i];
+    double a[2] = {st[3 * i], st[3 * i + 1]}, ta[2];
+    orc_transform_apply(Ti, a, ta);
+    r[i] = (nq[0] * (ta[0] - q[0]) + nq[1] * (ta[1] - q[1])) + nq[2] * (st[3 * i + 2] - q[2]);
+  }
+  memcpy(tmp, r, n * sizeof(double));
+  double sigma;
+  int rc = orc_standard_deviation(tmp, n, &sigma);
+  free(tmp);
+  if (rc != ORC_OK) {
+    free(r);
+    return rc;
+  }
+  double total[NACC];
+  for (int k = 0; k < NACC; ++k) total[k] = 0.;
+  if (sum_mode != 1) {
+    for (size_t i = 0; i < n; ++i)
+      p2pl_accumulate_pair(Ti, st + 3 * i, normals + 3 * (size_t)idx[i], r[i], sigma, total);
+  } else {
+    int blocks = reduce_blocks, threads = reduce_threads;
+    size_t G = (size_t)blocks * (size_t)threads;
+    double(*thr)[NACC] = (double(*)[NACC])malloc((size_t)threads * sizeof(*thr));
+    double(*part)[NACC] = (double(*)[NACC])malloc((size_t)blocks * sizeof(*part));
+    for (int blk = 0; blk < blocks; ++blk) {
+      for (int t = 0; t < threads; ++t) {
+        for (int k = 0; k < NACC; ++k) thr[t][k] = 0.;
+        for (size_t i = (size_t)blk * threads + t; i < n; i += G)
+          p2pl_accumulate_pair(Ti, st + 3 * i, normals + 3 * (size_t)idx[i], r[i], sigma, thr[t]);
+      }
+      tree_block_reduce(thr, threads, part[blk]);
+    }
+    tree_fold_rows(&part[0][0], (size_t)blocks, threads, thr, total);
+    free(thr);
+    free(part);
+  }
+  free(r);
+  if (sigma_out) *sigma_out = sigma;
+  if (huber_err) *huber_err = total[12];
+  return solve_update(total, total + 9, delta);
+}
+
+/* Icp3d::estimate (lib.rs:148-173) with the scalar residual n_q . (T p - q); opts (nullable) selects the order of the
+ * sums as for orc_icp_estimate: sum_mode 0 (or no opts) left folds, 1 the device's tree.  The search is the kd-tree's
+ * either way (use_kdtree is not read). */
 int orc_p2pl_estimate(const orc_kdtree *tree, const double *dst, size_t m, const double *normals,
-                      const double *src, size_t n, const orc_pose *init, size_t max_iter, orc_pose *out,
-                      uint32_t *last_idx, uint32_t *inner_iters) {
+                      const double *src, size_t n, const orc_pose *init, size_t max_iter, const orc_icp_opts *opts,
+                      orc_pose *out, uint32_t *last_idx, uint32_t *inner_iters) {
   if (!tree || tree->dim != 3) return -1;
+  const int sum_mode = opts ? opts->sum_mode : 0;
   orc_pose T = *init;
   size_t nn = n ? n : 1;
   double *st = (double *)malloc(nn * 3 * sizeof(double));
-  double *r = (double *)malloc(nn * sizeof(double));
   uint32_t *idx = (uint32_t *)malloc(nn * sizeof(uint32_t));
   int rc = ORC_OK;
   for (size_t it = 0; it < max_iter && rc == ORC_OK; ++it) {
@@ -964,44 +1043,21 @@ int orc_p2pl_estimate(const orc_kdtree *tree, const double *dst, size_t m, const
       if (m == 0) { rc = ORC_EMPTY_DST; break; }
       rc = orc_kdtree_search(tree, st, n, idx);
       if (rc != ORC_OK) break;
+      /* a query that compares with nothing (a NaN coordinate) has no neighbour: the reference's tree panics on it */
+      for (size_t i = 0; i < n; ++i)
+        if ((size_t)idx[i] >= m) rc = ORC_NAN;
+      if (rc != ORC_OK) break;
     }
     orc_pose Ti;
     orc_transform_identity(&Ti);
     int applied = 0;
     double prev_error = 1.7976931348623157e308;
     for (int k = 0; k < ORC_INNER_MAX_ITER && n >= 2; ++k) {
-      for (size_t i = 0; i < n; ++i) {
-        const double *q = dst + 3 * (size_t)idx[i], *nq = normals + 3 * (size_t)idx[i];
-        double a[2] = {st[3 * i], st[3 * i + 1]}, ta[2];
-        orc_transform_apply(&Ti, a, ta);
-        r[i] = (nq[0] * (ta[0] - q[0]) + nq[1] * (ta[1] - q[1])) + nq[2] * (st[3 * i + 2] - q[2]);
-      }
-      double sigma;
-      {
-        double *tmp = (double *)malloc(nn * sizeof(double));
-        memcpy(tmp, r, n * sizeof(double));
-        int src_ = orc_standard_deviation(tmp, n, &sigma);
-        free(tmp);
-        if (src_ == ORC_NAN) { rc = ORC_NAN; break; }
-      }
-      double jtr[3] = {0., 0., 0.}, jtj[9] = {0.}, err = 0.;
-      for (size_t i = 0; i < n; ++i) {
-        const double *nq = normals + 3 * (size_t)idx[i];
-        double e = r[i] * r[i];
-        if (sigma != 0.) {
-          double s2[2] = {st[3 * i], st[3 * i + 1]}, J2[2][3];
-          jacobian(&Ti, s2, J2);
-          double J[3];
-          for (int c = 0; c < 3; ++c) J[c] = nq[0] * J2[0][c] + nq[1] * J2[1][c];
-          double wg = orc_huber_drho(e, ORC_HUBER_K) * (1. / sigma);
-          for (int c = 0; c < 3; ++c) jtr[c] = jtr[c] + (wg * J[c]) * r[i];
-          for (int p = 0; p < 3; ++p)
-            for (int q2 = 0; q2 < 3; ++q2) jtj[3 * p + q2] = jtj[3 * p + q2] + (wg * J[p]) * J[q2];
-        }
-        err = err + orc_huber_rho(e, ORC_HUBER_K);
-      }
-      double delta[3];
-      if (solve_update(jtj, jtr, delta) != ORC_OK) break;
+      double sigma, delta[3], err;
+      int urc = orc_p2pl_update(&Ti, st, n, idx, dst, normals, sum_mode, opts ? opts->reduce_blocks : 0,
+                                opts ? opts->reduce_threads : 0, &sigma, delta, &err);
+      if (urc == ORC_NAN || urc < 0) { rc = urc == ORC_NAN ? ORC_NAN : -1; break; }
+      if (urc != ORC_OK) break;
       if ((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < ORC_DELTA_NORM_THRESHOLD) break;
       if (err > prev_error) break;
       prev_error = err;
@@ -1020,7 +1076,6 @@ int orc_p2pl_estimate(const orc_kdtree *tree, const double *dst, size_t m, const
   if (last_idx && rc == ORC_OK && max_iter > 0) memcpy(last_idx, idx, n * sizeof(uint32_t));
   *out = T;
   free(st);
-  free(r);
   free(idx);
   return rc;
 }

@@ -128,9 +128,16 @@ int orc_wgn_tree_fold(const double *partials_blocks_x_19, int blocks, int thread
  * include/icp_mi355x.h section 7 defines them; see the block comment in icp_oracle.c */
 int orc_p2pl_normals(const double *dst, size_t m, int k, double *normals_out);
 int orc_p2pl_normals_range(const double *dst, size_t m, size_t first, int k, double *normals_out);
+/* one evaluation of the estimator's inner loop on the pairs (st[i], dst[idx[i]]): st = the source moved by the outer
+ * pose (n x 3), Ti the inner pose.  sum_mode 0: left folds; 1: the device's tree (reduce_blocks x reduce_threads).
+ * Returns ORC_OK (delta set), ORC_NONE (fewer than two pairs, or a singular solve) or ORC_NAN. */
+int orc_p2pl_update(const orc_pose *Ti, const double *st, size_t n, const uint32_t *idx, const double *dst,
+                    const double *normals, int sum_mode, int reduce_blocks, int reduce_threads, double *sigma,
+                    double delta[3], double *huber_err);
+/* opts (nullable): sum_mode / reduce_blocks / reduce_threads as for orc_icp_estimate; use_kdtree is not read */
 int orc_p2pl_estimate(const orc_kdtree *tree, const double *dst, size_t m, const double *normals,
-                      const double *src, size_t n, const orc_pose *init, size_t max_iter, orc_pose *out,
-                      uint32_t *last_idx, uint32_t *inner_iters);
+                      const double *src, size_t n, const orc_pose *init, size_t max_iter, const orc_icp_opts *opts,
+                      orc_pose *out, uint32_t *last_idx, uint32_t *inner_iters);
 
 #ifdef __cplusplus
 }

@@ -104,7 +104,8 @@ def lib():
     sig("orc_wgn_tree_fold", C.c_int, dp, C.c_int, C.c_int, dp, dp, dp)
     sig("orc_p2pl_normals", C.c_int, dp, sz, C.c_int, dp)
     sig("orc_p2pl_normals_range", C.c_int, dp, sz, sz, C.c_int, dp)
-    sig("orc_p2pl_estimate", C.c_int, C.c_void_p, dp, sz, dp, dp, sz, pp, sz, pp, u32p, u32p)
+    sig("orc_p2pl_update", C.c_int, pp, dp, sz, u32p, dp, dp, C.c_int, C.c_int, C.c_int, dp, dp, dp)
+    sig("orc_p2pl_estimate", C.c_int, C.c_void_p, dp, sz, dp, dp, sz, pp, sz, C.POINTER(IcpOpts), pp, u32p, u32p)
     _lib = L
     return L
 
@@ -339,7 +340,8 @@ def p2pl_normals_update(dst, first, k, normals_prev):
     return out
 
 
-def p2pl_estimate(tree, normals, src, init, max_iter):
+def p2pl_estimate(tree, normals, src, init, max_iter, sum_mode=0, reduce_blocks=0, reduce_threads=0):
+    """sum_mode 0: the sums as left folds; 1: in the device's tree of reduce_blocks x reduce_threads"""
     src, sp = _d(src)
     normals, np_ = _d(normals)
     _, dp_ = _d(tree.dst)
@@ -347,8 +349,25 @@ def p2pl_estimate(tree, normals, src, init, max_iter):
     idx, ip = _u32(n)
     inner, inp = _u32(max_iter)
     o = Pose()
-    rc = lib().orc_p2pl_estimate(tree.h, dp_, tree.dst.shape[0], np_, sp, n, C.byref(init), max_iter, C.byref(o), ip, inp)
+    opts = IcpOpts(1, int(sum_mode), int(reduce_blocks), int(reduce_threads))
+    rc = lib().orc_p2pl_estimate(tree.h, dp_, tree.dst.shape[0], np_, sp, n, C.byref(init), max_iter, C.byref(opts),
+                                 C.byref(o), ip, inp)
     return rc, o, idx[:n], inner[:max_iter]
+
+
+def p2pl_update(Ti, st, idx, dst, normals, sum_mode=0, reduce_blocks=0, reduce_threads=0):
+    """one evaluation of the scalar-residual inner loop on the pairs (st[i], dst[idx[i]]): (rc, sigma, delta, Huber
+    error).  st: the source moved by the outer pose, n x 3; Ti: the inner pose."""
+    st, sp = _d(st)
+    dst, dp_ = _d(dst)
+    normals, np_ = _d(normals)
+    ix = np.ascontiguousarray(idx, dtype=np.uint32)
+    delta = np.zeros(3)
+    sigma, err = C.c_double(0.0), C.c_double(0.0)
+    rc = lib().orc_p2pl_update(C.byref(Ti), sp, st.shape[0], ix.ctypes.data_as(C.POINTER(C.c_uint32)), dp_, np_,
+                               int(sum_mode), int(reduce_blocks), int(reduce_threads), C.byref(sigma),
+                               delta.ctypes.data_as(C.POINTER(C.c_double)), C.byref(err))
+    return rc, sigma.value, delta, err.value
 
 
 # ---- halves of the tree-order evaluation (checking sharded evaluations) -------------------------

@@ -24,6 +24,22 @@ def oracle_in_device_order(icp, dim, dst, src, init, max_iter, use_kdtree=True):
     return rc, oT, oidx, oinner
 
 
+def oracle_plane_in_device_order(icp, dst, normals, src, init, max_iter):
+    """The CPU statement of the scalar-residual estimator (orc_p2pl_estimate) with its thirteen sums folded in the
+    tree of icp_reduce_geometry(len(src)): the bits of Icp3d.estimate_point_to_plane and, on lifted clouds [x, y, 0]
+    with normals [nx, ny, 0], of Icp2d.estimate_point_to_line.  Unlike `estimate`, these calls fold in the CALLER's
+    order: the pairs are gathered from d_src and idx as given (k_p2pl_gather / k_line_gather write pair i from source
+    point i, and k_p2pl_accumulate's thread g folds pairs g, g + G, ...), so no permutation is taken from `icp` -- it
+    is accepted only so that the call reads like oracle_in_device_order.  `dst`: the targets (m x 3) or an O.KdTree
+    of them; `init`: an oracle pose or a Transform.  Returns (rc, pose, idx, inner) like O.p2pl_estimate."""
+    src = np.ascontiguousarray(src, dtype=np.float64)
+    tree = dst if isinstance(dst, O.KdTree) else O.KdTree(dst)
+    init = O.Pose(*init.pose.as_tuple()) if hasattr(init, "pose") else init
+    blocks, threads = I.reduce_geometry(len(src))
+    return O.p2pl_estimate(tree, normals, src, init, max_iter, sum_mode=1, reduce_blocks=blocks,
+                           reduce_threads=threads)
+
+
 def check_fold_order(perm, cell):
     """a permutation, ascending by (sort key, original index): the stable order the header documents"""
     n = len(perm)
@@ -161,3 +177,56 @@ def _solve3_longdouble(H, g):
             c[i, j] = (-1) ** (i + j) * (m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0])
     det = np.sum(H[0] * c[0])
     return (c.T @ g) / det
+
+
+def plane_residuals_identity(st, idx, dst, normals):
+    """n_q . (p - q) of the pairs (st[i], dst[idx[i]]) at the identity inner pose, in f64 with every operation
+    rounded on its own and in the kernel's order: (nx ex + ny ey) + nz ez."""
+    q, nq = dst[idx], normals[idx]
+    return (nq[:, 0] * (st[:, 0] - q[:, 0]) + nq[:, 1] * (st[:, 1] - q[:, 1])) + nq[:, 2] * (st[:, 2] - q[:, 2])
+
+
+def reference_plane_update(st, idx, dst, normals, skeel=False):
+    """One update of the scalar-residual estimator at the identity inner pose, written from the definition at the
+    top of icp_rust_amd/csrc/p2plane.hip (not from the oracle): residual r = n_q . (p - q), sigma = 1.4826 MAD(r),
+    g = 1 / sigma, w = drho(r^2, 1.345), Jacobian row J = n_xy^T [I | (-p_y, p_x)^T] = (nx, ny, ny p_x - nx p_y),
+    delta = -(sum w g J^T J)^-1 (sum w g J^T r), Huber error = sum rho(r^2).
+    The residuals are taken in f64 (plane_residuals_identity) and sigma from their exact order statistics, both shared
+    with the code under test; the weights, the twelve sums, the error and the adjugate solve are in np.longdouble.
+    Returns (delta as longdouble[3], sigma, Huber error as longdouble); with `skeel`, also the Skeel condition number
+    || |H^-1| (|H|_abs |delta| + |g|_abs) ||_inf / ||delta||_inf, where |.|_abs sum the terms' magnitudes with
+    |J_2| taken as |ny p_x| + |nx p_y| (what the rounding of J_2's two products and their sum is relative to): a
+    relative perturbation eps of every term's factors moves delta by at most eps times it.  sigma == 0: delta None."""
+    L = np.longdouble
+    st, dst, normals = (np.asarray(x, dtype=np.float64) for x in (st, dst, normals))
+    idx = np.asarray(idx, dtype=np.int64)
+    r = plane_residuals_identity(st, idx, dst, normals)
+    col = np.ascontiguousarray(r)
+    sigma = PPF34 * _median_f64(np.abs(col - _median_f64(col)))
+    k = L(HUBER_K)
+    rl = r.astype(L)
+    e = rl * rl
+    big = e > k * k
+    root = np.sqrt(np.maximum(e, k * k))
+    err = np.sum(np.where(big, 2 * k * root - k * k, e))
+    if sigma == 0.0:
+        return (None, sigma, err, None) if skeel else (None, sigma, err)
+    wg = np.where(big, k / root, L(1)) / L(sigma)
+    nq = normals[idx].astype(L)
+    px, py = st[:, 0].astype(L), st[:, 1].astype(L)
+    J = (nq[:, 0], nq[:, 1], nq[:, 1] * px - nq[:, 0] * py)
+    Jabs = (np.abs(nq[:, 0]), np.abs(nq[:, 1]), np.abs(nq[:, 1] * px) + np.abs(nq[:, 0] * py))
+    H, Habs = np.zeros((3, 3), dtype=L), np.zeros((3, 3), dtype=L)
+    g, gabs = np.zeros(3, dtype=L), np.zeros(3, dtype=L)
+    for p in range(3):
+        g[p] = np.sum(wg * J[p] * rl)
+        gabs[p] = np.sum(wg * Jabs[p] * np.abs(rl))
+        for q in range(p, 3):
+            H[p, q] = H[q, p] = np.sum(wg * J[p] * J[q])
+            Habs[p, q] = Habs[q, p] = np.sum(wg * Jabs[p] * Jabs[q])
+    delta = -_solve3_longdouble(H, g)
+    if not skeel:
+        return delta, sigma, err
+    Hinv = np.stack([_solve3_longdouble(H, c) for c in np.eye(3, dtype=L)], axis=1)
+    cond = np.max(np.abs(Hinv) @ (Habs @ np.abs(delta) + gabs)) / np.max(np.abs(delta))
+    return delta, sigma, err, float(cond)

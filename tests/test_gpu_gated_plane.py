@@ -11,6 +11,7 @@ import pytest
 
 import icp_rust_amd as I
 import oracle_ffi as O
+from parity_util import oracle_plane_in_device_order
 from test_p2plane import moved, room
 
 pytestmark = pytest.mark.gpu
@@ -217,6 +218,15 @@ def test_a_finite_bound_tracks_the_cpu_statement(scene5):
     err = np.max(np.abs(T.as_array() - oT.as_array()))
     print("against the CPU statement:", err)
     assert err < 1e-9  # tests/test_p2plane.py's bar for tree sums against left folds
+
+    def tree_step(kept, Tk):  # the same step with its sums in the tree of reduce_geometry(kept): equal to the bit
+        rc, tT, _, tinner = oracle_plane_in_device_order(icp, tree, normals, kept, Tk, 1)
+        assert rc == O.OK
+        return I.Transform.from_pose(tT), tinner[0]
+
+    tT, tinner, tinl = chain(icp, src, 10, 0.25, tree_step)
+    assert np.array_equal(inl, tinl) and np.array_equal(inner, tinner), (inner, tinner)
+    assert np.array_equal(bits(T), bits(tT)), (T.as_array(), tT.as_array())
 
 
 @pytest.mark.parametrize("seed", [5, 6, 7])

@@ -14,6 +14,7 @@ import pytest
 import icp_rust_amd as I
 import oracle_ffi as O
 from icp_rust_amd import _lib
+from parity_util import oracle_plane_in_device_order
 from test_gpu_gated_plane import chain
 from test_line_abi import (GOLDEN_K, SEEDS, lift, line_normals_numpy, load_golden, moved2, oracle_point_to_line, outline,
                            outline_pair, pose_error)
@@ -161,6 +162,10 @@ def test_device_point_to_line_equals_the_cpu_statement(case):
     assert np.array_equal(inner, oinner)  # (the CPU statement: [8, 5, 3, 0, ...] and [8, 5, 4, 1, 0, ...] on the golden pairs)
     assert inner.sum() > 0
     assert err < 1e-9                     # tree sums vs left folds
+    # ... and the same statement with its sums folded in the device's tree: equal to the bit
+    trc, tT, tidx, tinner = oracle_plane_in_device_order(icp, lift(dst), lift(normals), lift(src), I.Transform(), iters)
+    assert trc == O.OK and np.array_equal(idx, tidx) and np.array_equal(inner, tinner)
+    assert np.array_equal(bits(T), bits(tT)), (T.as_array(), tT.as_array())
     # device-resident source: same bits as the host-buffer call
     T2, idx2, inner2 = icp.estimate_point_to_line(torch.from_numpy(src).cuda(), I.Transform(), iters, return_info=True)
     assert np.array_equal(bits(T), bits(T2)) and np.array_equal(idx, idx2) and np.array_equal(inner, inner2)
@@ -284,6 +289,15 @@ def test_a_finite_bound_tracks_the_chained_cpu_statement(gate_handle, n):
     assert np.array_equal(inl, oinl), (inl, oinl)
     assert np.array_equal(inner, oinner), (inner, oinner)
     assert err < 1e-9
+
+    def tree_step(kept3, Tk):  # the same step with its sums in the tree of reduce_geometry(kept): equal to the bit
+        rc, tT, _, tinner = oracle_plane_in_device_order(icp, tree, normals3, kept3, Tk, 1)
+        assert rc == O.OK
+        return I.Transform.from_pose(tT), tinner[0]
+
+    tT, tinner, tinl = chain(_Lifted(icp), lift(src), 10, 0.25, tree_step)
+    assert np.array_equal(inl, tinl) and np.array_equal(inner, tinner), (inner, tinner)
+    assert np.array_equal(bits(T), bits(tT)), (T.as_array(), tT.as_array())
     assert np.all(inl < n) and np.all(inl > 0) and inner.sum() > 0  # the gate removes the blob, not the walls
     print(f"n={n}: pose error gated {pose_error(T, Tt):.3g}, ungated "
           f"{pose_error(icp.estimate_point_to_line(src, I.Transform(), 10), Tt):.3g}")

@@ -370,11 +370,17 @@ def test_cpu_statement_returns_the_identity_on_a_single_wall():
 
 def test_cpu_statement_on_the_golden_scans_gives_the_documented_inner_counts(threads):
     src = load_golden(1)
+    # (the poses: the left fold's bits, recorded before one update became orc_p2pl_update)
+    bits = {2: [0x3feffff9eaca0d20, 0xbf63bb11cece1558, 0x3f63bb11cece1558, 0x3feffff9eaca0d20, 0xbfd8d0227359d12a,
+                0xbfdbfde9d6520519],
+            10: [0x3feffff9875e0687, 0xbf6459d2050cbf77, 0x3f6459d2050cbf77, 0x3feffff9875e0687, 0xbfe3c7e1054a9e52,
+                 0x3fcb5bb17c1fce82]}
     for k, want in ((2, [8, 5, 3]), (10, [8, 5, 4, 1])):
         dst = load_golden(k)
         rc, T, _, inner = oracle_point_to_line(dst, line_normals_numpy(dst, GOLDEN_K), src, I.Transform(), 20)
         assert rc == O.OK
         assert inner.tolist() == want + [0] * (20 - len(want)), (k, inner.tolist())
+        assert T.as_array().view(np.uint64).tolist() == bits[k], k
 
 
 # ------------------------------------------------------------------ the kernels' resources

@@ -9,6 +9,7 @@ import pytest
 import icp_rust_amd as I
 import oracle_ffi as O
 from icp_rust_amd import _lib
+from parity_util import oracle_plane_in_device_order
 
 
 def room(rng, m):
@@ -53,6 +54,10 @@ def test_cpu_checker_point_to_plane_recovers_a_pose_and_ignores_sliding():
     rc, T, _, inner = O.p2pl_estimate(tree, normals, src, O.transform_identity(), 10)
     assert rc == O.OK and inner.sum() > 0
     assert np.allclose(T.as_array(), Tt.as_array(), atol=5e-3)
+    # the left fold (sum_mode 0), to the bit what it returned before one update became orc_p2pl_update
+    assert T.as_array().view(np.uint64).tolist() == [0x3feffe5c955efae2, 0x3f947a87f6b8d802, 0xbf947a87f6b8d802,
+                                                     0x3feffe5c955efae2, 0x3fa4a1d9446fade4, 0xbf9e4ed3e6a08867]
+    assert inner.tolist() == [1, 1, 0, 0, 0, 0, 0, 0, 0, 0]
 
 
 gpu = pytest.mark.gpu
@@ -93,12 +98,16 @@ def test_device_point_to_plane_registration_tracks_the_cpu_statement():
     O.set_threads(16)
     try:
         rc, oT, oidx, oinner = O.p2pl_estimate(tree, normals, src, O.transform_identity(), 8)
+        trc, tT, tidx, tinner = oracle_plane_in_device_order(icp, tree, normals, src, O.transform_identity(), 8)
     finally:
         O.set_threads(1)
     assert rc == O.OK
     assert np.array_equal(idx, oidx)          # correspondences are the reference's exact 3-D NN either way
     assert np.array_equal(inner, oinner)
     assert np.max(np.abs(T.as_array() - oT.as_array())) < 1e-9  # tree sums vs left folds
+    # ... and the same statement with its sums folded in the device's tree: equal to the bit
+    assert trc == O.OK and np.array_equal(idx, tidx) and np.array_equal(inner, tinner)
+    assert np.array_equal(T.as_array().view(np.uint64), tT.as_array().view(np.uint64)), (T.as_array(), tT.as_array())
     assert np.allclose(T.as_array(), Tt.as_array(), atol=3e-3)
     # device-resident source: same bits as the host-buffer call
     import torch
