@@ -51,6 +51,16 @@ class PlaneQualityStruct(C.Structure):
                 ("translation_eig", C.c_double * 2)]
 
 
+class LineQualityStruct(C.Structure):
+    """`icp_line_quality` (include/icp_mi355x.h section 16): the quality of a pose under the point-to-line residual;
+    icp_rust_amd.LineQuality wraps it."""
+
+    _fields_ = [("n", C.c_uint64), ("inliers", C.c_uint64), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("inlier_sum_d2", C.c_double), ("line_rmse", C.c_double), ("line_sum_r2", C.c_double),
+                ("error", C.c_double), ("huber_error", C.c_double), ("information", C.c_double * 9),
+                ("translation_eig", C.c_double * 2)]
+
+
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)]
@@ -230,6 +240,12 @@ SIGNATURES = {
     "icp_batch_estimate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, _vp, _vp, _vp,
                                                           _vp]),
     "icp_batch_line_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_evaluate_point_to_line": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
+    "icp_evaluate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
+    "icp_batch_evaluate_point_to_line": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp, _vp]),
+    "icp_batch_evaluate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp,
+                                                          _vp]),
+    "icp_batch_line_quality_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

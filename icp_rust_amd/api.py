@@ -388,6 +388,44 @@ class PlaneQuality:
                 f"translation_eig=({self.translation_eig[0]:.6g}, {self.translation_eig[1]:.6g}))")
 
 
+class LineQuality:
+    """The quality of a pose under the point-to-line residual (`icp_line_quality`, include/icp_mi355x.h section 16) -- an
+    extension beyond the reference.  n, inliers, fitness, inlier_rmse and inlier_sum_d2 as in Quality (same bits at the
+    same pose and bound); line_rmse and line_sum_r2 of the inliers' squared line residuals; error and huber_error, the
+    folds of p2 and rho(p2) over all points; information, the 3 x 3 SE(2) information matrix the line residual gives on
+    the inlier pairs in (x, y, theta), rank-deficient where the scene is; translation_eig, the eigenvalues (lmin, lmax)
+    of its 2 x 2 translation block."""
+
+    __slots__ = ("n", "inliers", "fitness", "inlier_rmse", "inlier_sum_d2", "line_rmse", "line_sum_r2", "error",
+                 "huber_error", "information", "translation_eig")
+
+    def __init__(self, q):
+        self.n, self.inliers = int(q.n), int(q.inliers)
+        self.fitness, self.inlier_rmse, self.inlier_sum_d2 = q.fitness, q.inlier_rmse, q.inlier_sum_d2
+        self.line_rmse, self.line_sum_r2 = q.line_rmse, q.line_sum_r2
+        self.error, self.huber_error = q.error, q.huber_error
+        self.information = np.array(q.information[:], dtype=np.float64).reshape(3, 3)
+        self.translation_eig = np.array(q.translation_eig[:], dtype=np.float64)
+
+    def as_array(self):
+        """the float fields in struct order (fitness, inlier_rmse, inlier_sum_d2, line_rmse, line_sum_r2, error,
+        huber_error, information row-major, translation_eig): what a bit-for-bit comparison compares, next to n and
+        inliers"""
+        return np.array([self.fitness, self.inlier_rmse, self.inlier_sum_d2, self.line_rmse, self.line_sum_r2,
+                         self.error, self.huber_error, *self.information.ravel(), *self.translation_eig])
+
+    def weak_direction(self):
+        """the unit vector of the xy plane along which the translation is observed least: the eigenvector of lmin of the
+        2 x 2 translation block (numpy.linalg.eigh; a convenience, no bit claim)"""
+        _, vecs = np.linalg.eigh(self.information[:2, :2])
+        return vecs[:, 0]
+
+    def __repr__(self):
+        return (f"LineQuality(n={self.n}, inliers={self.inliers}, fitness={self.fitness:.6g}, "
+                f"inlier_rmse={self.inlier_rmse:.6g}, line_rmse={self.line_rmse:.6g}, "
+                f"translation_eig=({self.translation_eig[0]:.6g}, {self.translation_eig[1]:.6g}))")
+
+
 class _Icp:
     DIM = 0
 
@@ -924,6 +962,35 @@ class _Icp:
         idx = idx[:n].cpu().numpy().view(np.uint32) if on_device else idx[:n]
         return (o, idx, inner[:max_iter], inl[:max_iter]) if gated else (o, idx, inner[:max_iter])
 
+    # -- EXTENSION (not in the reference): the quality of a pose under the line residual, section 16 --
+    def evaluate_point_to_line(self, src, transform, max_correspondence_distance=float("inf"), return_indices=False):
+        """The LineQuality of `transform` (icp_evaluate_point_to_line[_device]; 2-D handles, needs current line
+        normals): the handle's exact correspondences at that pose, the inliers within max_correspondence_distance, the
+        line residual's RMSE, error / huber_error and the SE(2) information matrix it gives.  The handle's registration
+        state is left as it was.  return_indices=True also returns the correspondences (caller order).  numpy arrays or
+        contiguous float64 CUDA tensors (used in place)."""
+        self._need_2d("evaluate_point_to_line")
+        q = _lib.LineQualityStruct()
+        r = float(max_correspondence_distance)
+        if _is_device_tensor(src):
+            import torch
+
+            self._dev(src, "src")
+            n = src.shape[0]
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_indices else None
+            check(lib().icp_evaluate_point_to_line_device(self._h, C.c_void_p(src.data_ptr()), n,
+                                                          C.byref(transform.pose), r, C.byref(q),
+                                                          C.c_void_p(idx.data_ptr()) if return_indices else None),
+                  "icp_evaluate_point_to_line_device")
+            return (LineQuality(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else LineQuality(q)
+        s = _host(src, self.DIM)
+        n = s.shape[0]
+        idx = np.zeros(max(n, 1), dtype=np.uint32) if return_indices else None
+        check(lib().icp_evaluate_point_to_line(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
+                                               C.c_void_p(idx.ctypes.data) if return_indices else None),
+              "icp_evaluate_point_to_line")
+        return (LineQuality(q), idx[:n]) if return_indices else LineQuality(q)
+
     def profile_enable(self, every=1):
         """Time every `every`-th NN search launch with HIP events (0 / False: off)."""
         check(lib().icp_profile_enable(self._h, int(every)), "icp_profile_enable")
@@ -1280,6 +1347,79 @@ class IcpBatch:
             else:
                 qs.append(Quality(out[i]))
         return (qs, status) if return_status else qs
+
+    # -- the same under the point-to-line residual (icp_batch_evaluate_point_to_line*, section 16) --
+    def evaluate_point_to_line(self, srcs, dsts, transforms, k=10, max_correspondence_distance=float("inf"),
+                               allow_failures=False, return_status=False):
+        """The LineQuality of transforms[i] for srcs[i] against dsts[i] (a list, one Transform for all, or None:
+        identity): item i equals what Icp2d(dsts[i]) returns after compute_line_normals(k) from
+        evaluate_point_to_line(srcs[i], transforms[i], max_correspondence_distance), bit for bit; items of up to 1024
+        source and 2048 target points run as one workgroup each of a single launch (normals included), the others one
+        by one.  A failed item raises IcpError naming it, unless allow_failures=True (its LineQuality is then None);
+        return_status=True also returns the statuses."""
+        self._need_2d("evaluate_point_to_line")
+        srcs, dsts = list(srcs), list(dsts)
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
+        src, sf, sn = self._pack(srcs, "src")
+        dst, df, dm = self._pack(dsts, "dst")
+        items = list(zip(sf, sn, df, dm, self._inits(transforms, len(srcs))))
+        return self.evaluate_point_to_line_packed(src, dst, items, k, max_correspondence_distance, allow_failures,
+                                                  return_status)
+
+    def evaluate_point_to_line_packed(self, src, dst, items, k=10, max_correspondence_distance=float("inf"),
+                                      allow_failures=False, return_status=False):
+        """The same over pre-packed clouds (`items` as for evaluate_packed; K hypotheses share one src and one dst
+        range).  numpy arrays go through icp_batch_evaluate_point_to_line; contiguous float64 CUDA tensors through
+        icp_batch_evaluate_point_to_line_device, in place."""
+        self._need_2d("evaluate_point_to_line_packed")
+        if not 3 <= int(k) <= 16:
+            raise ValueError(f"k must be in [3, 16], got {k!r}")
+        r = float(max_correspondence_distance)
+        if not r >= 0.0:  # (also a NaN)
+            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
+        count = len(items)
+        arr = (_lib.BatchItem * max(count, 1))()
+        for i, (f, n, g, m, T) in enumerate(items):
+            arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
+            C.memmove(C.byref(arr[i].init), C.byref(T.pose), C.sizeof(Pose))
+        out = (_lib.LineQualityStruct * max(count, 1))()
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        if _is_device_tensor(src) or _is_device_tensor(dst):
+            import torch
+
+            if self._device is None:
+                self._device = src.device.index
+            _dev_points(src, self.DIM, self._device, "src")
+            _dev_points(dst, self.DIM, self._device, "dst")
+            for t in (src, dst):  # (the batch's own stream is not ordered against the producer's)
+                torch.cuda.current_stream(t.device).synchronize()
+            check(lib().icp_batch_evaluate_point_to_line_device(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
+                                                                C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count,
+                                                                int(k), r, out, C.c_void_p(status.ctypes.data)),
+                  "icp_batch_evaluate_point_to_line_device")
+        else:
+            s, d = _host(src, self.DIM), _host(dst, self.DIM)
+            check(lib().icp_batch_evaluate_point_to_line(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count,
+                                                         int(k), r, out, C.c_void_p(status.ctypes.data)),
+                  "icp_batch_evaluate_point_to_line")
+        status = status[:count]
+        qs = []
+        for i in range(count):
+            if status[i] != _lib.OK:
+                if not allow_failures:
+                    raise IcpError(int(status[i]), f"icp_batch_evaluate_point_to_line item {i}")
+                qs.append(None)
+            else:
+                qs.append(LineQuality(out[i]))
+        return (qs, status) if return_status else qs
+
+    def line_quality_counters(self):
+        """(items scored in a batch launch, items scored one by one, launches, launches not made for want of LDS) of
+        evaluate_point_to_line*"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_line_quality_counters(self._b, out), "icp_batch_line_quality_counters")
+        return tuple(int(x) for x in out)
 
     def evaluate_counters(self):
         """(items evaluated in a batch launch, items evaluated one by one, launches)"""

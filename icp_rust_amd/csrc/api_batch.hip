@@ -5,6 +5,8 @@
 // Section 15, the same call with the point-to-line residual of section 14: k_line_estimate_batch (p2line_batch.hip), one
 // workgroup per item in at most two launches; one by one: icp_create_device + icp_compute_target_line_normals +
 // icp_estimate_point_to_line_device.
+// Sections 9 and 16, the quality of many poses: k_quality_batch (quality.hip) and, with the line residual,
+// k_line_quality_batch (quality_line.hip), one workgroup per item in one launch; one by one: the single calls.
 #include <cstring>
 #include <new>
 #include <vector>
@@ -38,6 +40,10 @@ struct icp_batch {
   QualityPart *h_qres = nullptr;
   size_t cap_qres = 0;
   uint64_t qctr[3] = {0, 0, 0};  // icp_batch_evaluate_counters
+  // icp_batch_evaluate_point_to_line (section 16): the item list above, and its own records (pinned)
+  LineQualityPart *h_lqres = nullptr;
+  size_t cap_lqres = 0;
+  uint64_t lqctr[4] = {0, 0, 0, 0};  // icp_batch_line_quality_counters
 };
 
 namespace {
@@ -242,6 +248,7 @@ extern "C" void icp_batch_destroy(icp_batch *b) {
     (void)hipFree(b->d_qitems);
     if (b->h_qitems) (void)hipHostFree(b->h_qitems);
     if (b->h_qres) (void)hipHostFree(b->h_qres);
+    if (b->h_lqres) (void)hipHostFree(b->h_lqres);
     (void)hipStreamDestroy(b->stream);
   }
   delete b;
@@ -416,6 +423,25 @@ int run_quality(icp_batch *b, const double *d_src, const double *d_dst, const ic
   return ICP_OK;
 }
 
+// the host entries' clouds, staged through the batch's buffers: *d_src / *d_dst are what run_quality and
+// run_line_quality read (null for an empty array)
+int stage_clouds(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                 const double **d_src, const double **d_dst) {
+  if (src_points > 0) {
+    HIP_TRY(reserve(b->d_src, b->cap_src, src_points * b->dim));
+    HIP_TRY(hipMemcpyAsync(b->d_src, src, src_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
+  if (dst_points > 0) {
+    HIP_TRY(reserve(b->d_dst, b->cap_dst, dst_points * b->dim));
+    HIP_TRY(hipMemcpyAsync(b->d_dst, dst, dst_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  }
+  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  *d_src = src_points > 0 ? b->d_src : nullptr;
+  *d_dst = dst_points > 0 ? b->d_dst : nullptr;
+  return ICP_OK;
+}
+
 }  // namespace
 
 extern "C" int icp_batch_evaluate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
@@ -433,22 +459,132 @@ extern "C" int icp_batch_evaluate(icp_batch *b, const double *src, size_t src_po
   ICP_TRY_RC(check_quality_args(b, src, src_points, dst, dst_points, items, count, max_dist, out, status));
   if (count == 0) return ICP_OK;
   ICP_TRY_RC(ensure_device(b));
-  if (src_points > 0) {
-    HIP_TRY(reserve(b->d_src, b->cap_src, src_points * b->dim));
-    HIP_TRY(hipMemcpyAsync(b->d_src, src, src_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  }
-  if (dst_points > 0) {
-    HIP_TRY(reserve(b->d_dst, b->cap_dst, dst_points * b->dim));
-    HIP_TRY(hipMemcpyAsync(b->d_dst, dst, dst_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  }
-  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  return run_quality(b, src_points > 0 ? b->d_src : nullptr, dst_points > 0 ? b->d_dst : nullptr, items, count, max_dist,
-                     out, status);
+  const double *d_src, *d_dst;
+  ICP_TRY_RC(stage_clouds(b, src, src_points, dst, dst_points, &d_src, &d_dst));
+  return run_quality(b, d_src, d_dst, items, count, max_dist, out, status);
 }
 
 extern "C" int icp_batch_evaluate_counters(icp_batch *b, uint64_t out[3]) {
   if (!b || !out) return ICP_BAD_ARGUMENT;
   for (int q = 0; q < 3; ++q) out[q] = b->qctr[q];
+  return ICP_OK;
+}
+
+// ---- icp_batch_evaluate_point_to_line (include/icp_mi355x.h section 16): the same with the point-to-line residual ----
+// The items that fit one workgroup run as k_line_quality_batch (quality_line.hip), one workgroup each, in one launch;
+// the rest, and those a workgroup hands back, go one by one through a handle of the pool: icp_create_device +
+// icp_compute_target_line_normals + icp_evaluate_point_to_line_device, exactly as single calls serve them.
+namespace {
+
+bool line_quality_fits(const icp_batch_item &it) {
+  return it.n >= 1 && it.n <= kLineQualityMaxN && it.m >= 1 && it.m <= kLineQualityMaxM;
+}
+
+// (the first failing step's status is the item's: ICP_EMPTY_DST and ICP_BAD_ARGUMENT -- targets section 14 refuses --
+// come from the normals, ICP_NAN_INPUT from the evaluation; *out then holds n and zeros)
+int serve_line_quality_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, int k,
+                           double max_dist, icp_line_quality *out, int *status) {
+  line_quality_clear((size_t)it.n, out);
+  icp_handle *h = nullptr;
+  int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
+  if (rc == ICP_OK) {
+    rc = icp_compute_target_line_normals(h, k);
+    if (rc == ICP_OK)
+      rc = icp_evaluate_point_to_line_device(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr, (size_t)it.n, &it.init,
+                                             max_dist, out, nullptr);
+    icp_destroy(h);
+  }
+  if (rc == ICP_OK || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT || rc == ICP_BAD_ARGUMENT) {
+    *status = rc;
+    return ICP_OK;
+  }
+  return rc;
+}
+
+int run_line_quality(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
+                     int k, double max_dist, icp_line_quality *out, int *status) {
+  std::vector<size_t> fit, one_by_one;
+  unsigned m_max = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if (line_quality_fits(items[i])) {
+      fit.push_back(i);
+      if (items[i].m > m_max) m_max = (unsigned)items[i].m;
+    } else {
+      one_by_one.push_back(i);
+    }
+  }
+  if (!fit.empty()) {
+    HIP_TRY(reserve_pinned(b->h_qitems, b->cap_h_qitems, fit.size()));
+    HIP_TRY(reserve(b->d_qitems, b->cap_qitems, fit.size()));
+    HIP_TRY(reserve_pinned(b->h_lqres, b->cap_lqres, count));
+    for (size_t j = 0; j < fit.size(); ++j) {
+      const icp_batch_item &it = items[fit[j]];
+      QualityBatchItem &d = b->h_qitems[j];
+      d.src_first = it.src_first;
+      d.dst_first = it.dst_first;
+      d.n = (unsigned)it.n;
+      d.m = (unsigned)it.m;
+      d.slot = (unsigned)fit[j];
+      d.pad = 0;
+      d.T = it.init;
+      b->h_lqres[fit[j]].pad = 1;  // handed back, unless its workgroup writes the record
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_qitems, b->h_qitems, fit.size() * sizeof(QualityBatchItem), hipMemcpyHostToDevice,
+                           b->stream));
+    bool granted = true;
+    // (r * r in f64 on the host, as icp_evaluate_point_to_line_device forms it)
+    HIP_TRY(launch_line_quality_batch(m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist, k,
+                                      b->h_lqres, b->stream, &granted));
+    ++b->lqctr[granted ? 2 : 3];
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (size_t i : fit) {
+      if (!granted || b->h_lqres[i].pad != 0) {
+        one_by_one.push_back(i);
+        continue;
+      }
+      status[i] = line_quality_result((size_t)items[i].n, b->h_lqres[i], &out[i]);
+      ++b->lqctr[0];
+    }
+  }
+  for (size_t i : one_by_one) {
+    ICP_TRY_RC(serve_line_quality_one(b, d_src, d_dst, items[i], k, max_dist, &out[i], &status[i]));
+    ++b->lqctr[1];
+  }
+  return ICP_OK;
+}
+
+int check_line_quality_args(const icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                            const icp_batch_item *items, size_t count, int k, double max_dist, const icp_line_quality *out,
+                            const int *status) {
+  if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, nullptr);
+}
+
+}  // namespace
+
+extern "C" int icp_batch_evaluate_point_to_line_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                       const double *d_dst, size_t dst_points, const icp_batch_item *items,
+                                                       size_t count, int k, double max_dist, icp_line_quality *out,
+                                                       int *status) {
+  ICP_TRY_RC(check_line_quality_args(b, d_src, src_points, d_dst, dst_points, items, count, k, max_dist, out, status));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  return run_line_quality(b, d_src, d_dst, items, count, k, max_dist, out, status);
+}
+
+extern "C" int icp_batch_evaluate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                                size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                                double max_dist, icp_line_quality *out, int *status) {
+  ICP_TRY_RC(check_line_quality_args(b, src, src_points, dst, dst_points, items, count, k, max_dist, out, status));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  const double *d_src, *d_dst;
+  ICP_TRY_RC(stage_clouds(b, src, src_points, dst, dst_points, &d_src, &d_dst));
+  return run_line_quality(b, d_src, d_dst, items, count, k, max_dist, out, status);
+}
+
+extern "C" int icp_batch_line_quality_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->lqctr[q];
   return ICP_OK;
 }

@@ -577,6 +577,20 @@ struct QualityBatchItem {
 hipError_t launch_quality_batch(int dim, unsigned m_max, const double *d_src, const double *d_dst,
                                 const QualityBatchItem *d_items, unsigned count, double r2, QualityPart *res,
                                 hipStream_t stream);
+// EXTENSION: the quality of a pose under the point-to-line residual (quality_line.hip; include/icp_mi355x.h section 16).
+// Its ten sums: inlier d2, inlier p2, p2, rho(p2), and the six entries of the inlier pairs' J^T J, J = (nx, ny, c).
+constexpr int kLineQualitySums = 10;
+using LineQualityPart = FoldPart<kLineQualitySums>;
+void line_quality_clear(size_t n, icp_line_quality *q);
+int line_quality_result(size_t n, const LineQualityPart &p, icp_line_quality *q);
+// icp_batch_evaluate_point_to_line (api_batch.hip): items of up to kLineQualityMaxN source and kLineQualityMaxM target
+// points run as one workgroup of 1024 threads each (k_line_quality_batch), which computes the item's line normals from k
+// neighbours and writes res[slot] with pad = 0; a workgroup that hands its item back leaves res[slot] alone (the host
+// presets pad != 0).  *granted as for launch_tiny_estimate_batch.
+constexpr unsigned kLineQualityMaxN = 1024, kLineQualityMaxM = 2048;
+hipError_t launch_line_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
+                                     const QualityBatchItem *d_items, unsigned count, double r2, int k,
+                                     LineQualityPart *res, hipStream_t stream, bool *granted);
 // three launches around a predicted window (gn_win.hip); h_res->overflow == 2 when it missed
 bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind = 2, bool any_n = false,
                    double f_override = 0.);

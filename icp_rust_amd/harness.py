@@ -14,7 +14,8 @@ from .scans import PacketFile, load_scan2d, write_packets
 from .synth import PACKETS_PER_FRAME, remove_invalid_values
 
 
-def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None, point_to_line=None):
+def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None, point_to_line=None, qualities=None,
+               quality_distance=None):
     """examples/scan2d.rs:62-115.  `index` starts at 0 and is incremented BEFORE use, so
     000.txt is never read and 001.txt is the fixed source (:63,69-77); every later frame k
     loads dst = k.txt, builds Icp2d::new(&dst) and estimates warm-started from the previous
@@ -23,6 +24,9 @@ def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None, point_t
     `point_to_line=k` (EXTENSION, not in the reference; include/icp_mi355x.h section 14): every frame's handle computes
     the line normals of its targets from their k nearest (compute_line_normals(k)) and registers with the point-to-line
     residual (estimate_point_to_line) instead; None calls exactly what it always called.
+    `qualities=[]` (EXTENSION; sections 9 and 16): after each frame's estimate the list gets the score of the estimated
+    pose on that frame's handle, within quality_distance (None: +inf) -- evaluate_point_to_line (a LineQuality) when
+    point_to_line is set, evaluate (a Quality) otherwise; None calls neither.
     Returns (transforms, inverse_transforms, path_xy)."""
     icp_factory = icp_factory or Icp2d
     index = 0
@@ -44,6 +48,10 @@ def run_scan2d(scan_dir, max_iter=20, icp_factory=None, max_frames=None, point_t
             transform = icp.estimate_point_to_line(src, transform, max_iter)
         else:
             transform = icp.estimate(src, transform, max_iter)
+        if qualities is not None:
+            r = float("inf") if quality_distance is None else quality_distance
+            score = icp.evaluate_point_to_line if point_to_line else icp.evaluate
+            qualities.append(score(src, transform, r))
         inv = transform.inverse()
         transforms.append(transform)
         inverses.append(inv)

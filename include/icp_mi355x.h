@@ -65,7 +65,9 @@ extern "C" {
  * (icp_crop_targets, icp_multi_crop_targets; icp_grid_crop_counters in icp_mi355x_debug.h); so was section 12
  * (icp_estimate_point_to_plane_gated*, icp_gate_plane_pairs_device, icp_multi_estimate_point_to_plane_gated); so was
  * section 13 (icp_plane_quality, icp_evaluate_point_to_plane*); so was section 14 (icp_*_target_line_normals,
- * icp_estimate_point_to_line*) */
+ * icp_estimate_point_to_line*); so was section 15 (icp_batch_estimate_point_to_line*; icp_batch_line_counters in
+ * icp_mi355x_debug.h); so was section 16 (icp_line_quality, icp_evaluate_point_to_line*,
+ * icp_batch_evaluate_point_to_line*; icp_batch_line_quality_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -870,6 +872,87 @@ int icp_batch_estimate_point_to_line_device(icp_batch *b, const double *d_src, s
                                             size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                             size_t max_iter, icp_pose *out, int *status, uint32_t *d_last_idx,
                                             uint32_t *inner_iters);
+
+/* ================================================================================
+ * 16. EXTENSION (not in the reference): the quality of a pose under the point-to-line residual, single and batched
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 13 for 2-D handles: the score of a
+ * pose under the residual sections 14 and 15 register with.  Section 9's score uses the point residual: its translation
+ * information is c * I whatever the scene looks like, so it cannot see a corridor, and its RMSE measures the sample
+ * spacing of the two scans along the walls rather than the fit.  This section gives the line-residual RMSE (the sensor
+ * noise where the pose is right) and the unweighted jtj of section 14's accumulation at the pose, rank-deficient
+ * exactly where the scene is: what ranks K registered hypotheses and what a pose graph takes as their information.
+ * The reference has no such thing: no parity claim; DESIGN.md section 9k restates the definition.
+ *
+ * It is section 13's definition with the third coordinate removed.  For a 2-D handle with targets dst (m points) and
+ * their current line normals nrm (section 14), a source cloud src (n points, caller order), a pose T and max_dist r
+ * (r >= 0, or +inf), for every source point p (no FMA anywhere):
+ *   qx = (r00 px + r01 py) + tx, qy = (r10 px + r11 py) + ty               (Transform::transform)
+ *   j  = the handle's exact 2-D nearest neighbour of (qx, qy); b = dst[j], (nx, ny) = nrm[j]
+ *   ex = qx - bx, ey = qy - by
+ *   d2 = ex ex + ey ey                                                     (the 2-D icp_evaluate's d2)
+ *   inlier = d2 <= r * r (r * r in f64; a NaN d2 is never an inlier)
+ *   rp = nx ex + ny ey                          (section 14's line residual at the identity inner pose; the estimator's
+ *                                               plane_residual adds a trailing + nz dz = + 0.0, which only turns a
+ *                                               -0.0 into +0.0: the square below does not see it)
+ *   p2 = rp rp
+ *   c  = (nx * (-qy)) + (ny * qx)               (the third entry of section 14's Jacobian row (nx, ny, c) at identity)
+ * Ten sums, each by section 9's fold over the n values in caller order (n == 1: the one value); a point that is not an
+ * inlier adds +0.0 to the inlier-only sums -- section 13's sums in section 13's order:
+ *   S_d2 = fold(inlier ? d2)     S_p2 = fold(inlier ? p2)     E = fold(p2)     H = fold(rho(p2))  (huber.rs)
+ *   Ixx = fold(inlier ? nx nx)   Ixy = fold(inlier ? nx ny)   Iyy = fold(inlier ? ny ny)
+ *   Ixt = fold(inlier ? nx c)    Iyt = fold(inlier ? ny c)    Itt = fold(inlier ? c c)
+ * and the fields from them, on the host, exactly as section 13 forms icp_plane_quality's:
+ *   inliers        the count (exact)                  fitness      inliers / n
+ *   inlier_sum_d2  S_d2                               inlier_rmse  sqrt(S_d2 / inliers) (0 without inliers): the bits
+ *                                                                  icp_evaluate gives at the same T and r
+ *   line_sum_r2    S_p2                               line_rmse    sqrt(S_p2 / inliers) (0 without inliers)
+ *   error          E                                  huber_error  H (what section 14's evaluation reports as its error)
+ *   information    row-major [[Ixx, Ixy, Ixt], [Ixy, Iyy, Iyt], [Ixt, Iyt, Itt]]
+ *   translation_eig  lmin, lmax of [[Ixx, Ixy], [Ixy, Iyy]] with + - * sqrt only: h = (Ixx + Iyy) * 0.5,
+ *                  g = (Ixx - Iyy) * 0.5, s = sqrt(g g + Ixy Ixy), lmin = h - s, lmax = h + s
+ * A target with fewer than three neighbours has the zero normal (section 14): its pairs add zeros, the result is valid.
+ *
+ * icp_evaluate_point_to_line[_device].  Statuses, decided in this order: ICP_BAD_ARGUMENT (h, T or out NULL; src NULL
+ * with n > 0; r NaN or negative; n >= 2^32 - 1: before any device use and before the handle is read); n == 0 -> ICP_OK
+ * and zeros; ICP_NO_DEVICE; then the handle: ICP_BAD_ARGUMENT (not a 2-D handle; line normals not current),
+ * ICP_EMPTY_DST (no targets); ICP_NAN_INPUT (some p2 is NaN).  *out is the result when the call returns ICP_OK;
+ * otherwise it holds n and zeros.  idx / d_idx (nullable): the n correspondences at T, caller order.  The handle's
+ * registration state is not touched: an estimate after an evaluation gives the bits it gives without one.
+ *
+ * icp_batch_evaluate_point_to_line[_device]: section 9's batch call with this residual, for 2-D batches.  Item i's
+ * out[i] and status[i] are what icp_create(2, dst + 2 dst_first, m) + icp_compute_target_line_normals(k) +
+ * icp_evaluate_point_to_line(src + 2 src_first, n, &items[i].init, max_dist) give on a fresh handle, bit for bit; the
+ * first failing step's status is the item's (ICP_EMPTY_DST without targets, ICP_BAD_ARGUMENT where section 14 refuses
+ * the targets, ICP_NAN_INPUT), and out[i] then holds n and zeros.  Every item with 1 <= n <= 1024 and 1 <= m <= 2048 runs as ONE
+ * workgroup that computes the item's line normals and the score, all of them in one launch; the other items, and those
+ * a workgroup hands back, go through exactly those three entries one after another.  An item is
+ * never approximated.  Arguments and ranges are section 8's and section 9's: ICP_BAD_ARGUMENT for b, items, out or
+ * status NULL with count > 0, a range outside the packed arrays, max_dist NaN or negative, a batch that is not 2-D and
+ * k outside [3, 16] -- all before the device is touched; count == 0 is a successful no-op. */
+typedef struct icp_line_quality {
+  uint64_t n;                 /* source points                                          */
+  uint64_t inliers;           /* points with d2 <= max_dist^2                           */
+  double fitness;             /* inliers / n                                            */
+  double inlier_rmse;         /* sqrt(inlier_sum_d2 / inliers): section 9's             */
+  double inlier_sum_d2;       /* fold of the inliers' squared distances                 */
+  double line_rmse;           /* sqrt(line_sum_r2 / inliers), 0 without inliers         */
+  double line_sum_r2;         /* fold of the inliers' squared line residuals            */
+  double error;               /* fold of p2 over all points                             */
+  double huber_error;         /* fold of rho(p2) over all points                        */
+  double information[9];      /* row-major SE(2) information of the inlier pairs        */
+  double translation_eig[2];  /* lmin, lmax of the 2 x 2 translation block              */
+} icp_line_quality;
+int icp_evaluate_point_to_line(icp_handle *h, const double *src, size_t n, const icp_pose *T, double max_dist,
+                               icp_line_quality *out, uint32_t *idx);
+int icp_evaluate_point_to_line_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, double max_dist,
+                                      icp_line_quality *out, uint32_t *d_idx);
+int icp_batch_evaluate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                     size_t dst_points, const icp_batch_item *items, size_t count, int k, double max_dist,
+                                     icp_line_quality *out, int *status);
+int icp_batch_evaluate_point_to_line_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                            size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                            double max_dist, icp_line_quality *out, int *status);
 
 #ifdef __cplusplus
 }
