@@ -350,7 +350,48 @@ class Quality:
                 f"inlier_rmse={self.inlier_rmse:.6g}, error={self.error:.6g}, huber_error={self.huber_error:.6g})")
 
 
-class PlaneQuality:
+class _NormalQuality:
+    """What PlaneQuality and LineQuality share; `_RESIDUAL` ("plane" / "line") names the residual and with it the two
+    attributes <residual>_rmse and <residual>_sum_r2, which the code here reaches as _rmse and _sum_r2."""
+
+    __slots__ = ()
+    _RESIDUAL = None
+
+    def __init_subclass__(cls):
+        # (the subclass's two slot descriptors under a second name: plain attribute access, nothing looked up by name
+        # per object -- a batch builds one object per item)
+        cls._FIELDS = (cls._RESIDUAL + "_rmse", cls._RESIDUAL + "_sum_r2")
+        cls._rmse, cls._sum_r2 = (cls.__dict__[name] for name in cls._FIELDS)
+
+    def __init__(self, q):
+        rmse, sum_r2 = self._FIELDS
+        self.n, self.inliers = int(q.n), int(q.inliers)
+        self.fitness, self.inlier_rmse, self.inlier_sum_d2 = q.fitness, q.inlier_rmse, q.inlier_sum_d2
+        self._rmse, self._sum_r2 = getattr(q, rmse), getattr(q, sum_r2)
+        self.error, self.huber_error = q.error, q.huber_error
+        self.information = np.array(q.information[:], dtype=np.float64).reshape(3, 3)
+        self.translation_eig = np.array(q.translation_eig[:], dtype=np.float64)
+
+    def as_array(self):
+        """the float fields in struct order (fitness, inlier_rmse, inlier_sum_d2, <residual>_rmse, <residual>_sum_r2,
+        error, huber_error, information row-major, translation_eig): what a bit-for-bit comparison compares, next to n
+        and inliers"""
+        return np.array([self.fitness, self.inlier_rmse, self.inlier_sum_d2, self._rmse, self._sum_r2, self.error,
+                         self.huber_error, *self.information.ravel(), *self.translation_eig])
+
+    def weak_direction(self):
+        """the unit vector of the xy plane along which the translation is observed least: the eigenvector of lmin of the
+        2 x 2 translation block (numpy.linalg.eigh; a convenience, no bit claim)"""
+        _, vecs = np.linalg.eigh(self.information[:2, :2])
+        return vecs[:, 0]
+
+    def __repr__(self):
+        return (f"{type(self).__name__}(n={self.n}, inliers={self.inliers}, fitness={self.fitness:.6g}, "
+                f"inlier_rmse={self.inlier_rmse:.6g}, {self._FIELDS[0]}={self._rmse:.6g}, "
+                f"translation_eig=({self.translation_eig[0]:.6g}, {self.translation_eig[1]:.6g}))")
+
+
+class PlaneQuality(_NormalQuality):
     """The quality of a pose under the point-to-plane residual (`icp_plane_quality`, include/icp_mi355x.h section 13) --
     an extension beyond the reference.  n, inliers, fitness, inlier_rmse and inlier_sum_d2 as in Quality (same bits at
     the same pose and bound); plane_rmse and plane_sum_r2 of the inliers' squared plane residuals; error and
@@ -360,35 +401,10 @@ class PlaneQuality:
 
     __slots__ = ("n", "inliers", "fitness", "inlier_rmse", "inlier_sum_d2", "plane_rmse", "plane_sum_r2", "error",
                  "huber_error", "information", "translation_eig")
-
-    def __init__(self, q):
-        self.n, self.inliers = int(q.n), int(q.inliers)
-        self.fitness, self.inlier_rmse, self.inlier_sum_d2 = q.fitness, q.inlier_rmse, q.inlier_sum_d2
-        self.plane_rmse, self.plane_sum_r2 = q.plane_rmse, q.plane_sum_r2
-        self.error, self.huber_error = q.error, q.huber_error
-        self.information = np.array(q.information[:], dtype=np.float64).reshape(3, 3)
-        self.translation_eig = np.array(q.translation_eig[:], dtype=np.float64)
-
-    def as_array(self):
-        """the float fields in struct order (fitness, inlier_rmse, inlier_sum_d2, plane_rmse, plane_sum_r2, error,
-        huber_error, information row-major, translation_eig): what a bit-for-bit comparison compares, next to n and
-        inliers"""
-        return np.array([self.fitness, self.inlier_rmse, self.inlier_sum_d2, self.plane_rmse, self.plane_sum_r2,
-                         self.error, self.huber_error, *self.information.ravel(), *self.translation_eig])
-
-    def weak_direction(self):
-        """the unit vector of the xy plane along which the translation is observed least: the eigenvector of lmin of the
-        2 x 2 translation block (numpy.linalg.eigh; a convenience, no bit claim)"""
-        _, vecs = np.linalg.eigh(self.information[:2, :2])
-        return vecs[:, 0]
-
-    def __repr__(self):
-        return (f"PlaneQuality(n={self.n}, inliers={self.inliers}, fitness={self.fitness:.6g}, "
-                f"inlier_rmse={self.inlier_rmse:.6g}, plane_rmse={self.plane_rmse:.6g}, "
-                f"translation_eig=({self.translation_eig[0]:.6g}, {self.translation_eig[1]:.6g}))")
+    _RESIDUAL = "plane"
 
 
-class LineQuality:
+class LineQuality(_NormalQuality):
     """The quality of a pose under the point-to-line residual (`icp_line_quality`, include/icp_mi355x.h section 16) -- an
     extension beyond the reference.  n, inliers, fitness, inlier_rmse and inlier_sum_d2 as in Quality (same bits at the
     same pose and bound); line_rmse and line_sum_r2 of the inliers' squared line residuals; error and huber_error, the
@@ -398,32 +414,7 @@ class LineQuality:
 
     __slots__ = ("n", "inliers", "fitness", "inlier_rmse", "inlier_sum_d2", "line_rmse", "line_sum_r2", "error",
                  "huber_error", "information", "translation_eig")
-
-    def __init__(self, q):
-        self.n, self.inliers = int(q.n), int(q.inliers)
-        self.fitness, self.inlier_rmse, self.inlier_sum_d2 = q.fitness, q.inlier_rmse, q.inlier_sum_d2
-        self.line_rmse, self.line_sum_r2 = q.line_rmse, q.line_sum_r2
-        self.error, self.huber_error = q.error, q.huber_error
-        self.information = np.array(q.information[:], dtype=np.float64).reshape(3, 3)
-        self.translation_eig = np.array(q.translation_eig[:], dtype=np.float64)
-
-    def as_array(self):
-        """the float fields in struct order (fitness, inlier_rmse, inlier_sum_d2, line_rmse, line_sum_r2, error,
-        huber_error, information row-major, translation_eig): what a bit-for-bit comparison compares, next to n and
-        inliers"""
-        return np.array([self.fitness, self.inlier_rmse, self.inlier_sum_d2, self.line_rmse, self.line_sum_r2,
-                         self.error, self.huber_error, *self.information.ravel(), *self.translation_eig])
-
-    def weak_direction(self):
-        """the unit vector of the xy plane along which the translation is observed least: the eigenvector of lmin of the
-        2 x 2 translation block (numpy.linalg.eigh; a convenience, no bit claim)"""
-        _, vecs = np.linalg.eigh(self.information[:2, :2])
-        return vecs[:, 0]
-
-    def __repr__(self):
-        return (f"LineQuality(n={self.n}, inliers={self.inliers}, fitness={self.fitness:.6g}, "
-                f"inlier_rmse={self.inlier_rmse:.6g}, line_rmse={self.line_rmse:.6g}, "
-                f"translation_eig=({self.translation_eig[0]:.6g}, {self.translation_eig[1]:.6g}))")
+    _RESIDUAL = "line"
 
 
 class _Icp:
@@ -609,24 +600,29 @@ class _Icp:
         inliers within max_correspondence_distance, the reference's error / huber_error and the SE(2) information
         matrix.  The handle's registration state is left as it was.  return_indices=True also returns the
         correspondences (caller order).  numpy arrays or contiguous float64 CUDA tensors (used in place)."""
-        q = _lib.QualityStruct()
-        r = float(max_correspondence_distance)
+        return self._evaluate(_lib.QualityStruct, Quality, "icp_evaluate", src, transform,
+                              max_correspondence_distance, return_indices)
+
+    def _evaluate(self, struct, wrap, symbol, src, transform, r, return_indices):
+        """evaluate, evaluate_point_to_plane and evaluate_point_to_line behind their guards: `symbol` (host arrays) or
+        `symbol`_device (device tensors) fills a `struct`, returned as a `wrap`"""
+        q, r = struct(), float(r)
         if _is_device_tensor(src):
             import torch
 
             self._dev(src, "src")
             n = src.shape[0]
             idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_indices else None
-            check(lib().icp_evaluate_device(self._h, C.c_void_p(src.data_ptr()), n, C.byref(transform.pose), r,
-                                            C.byref(q), C.c_void_p(idx.data_ptr()) if return_indices else None),
-                  "icp_evaluate_device")
-            return (Quality(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else Quality(q)
+            check(getattr(lib(), symbol + "_device")(self._h, C.c_void_p(src.data_ptr()), n, C.byref(transform.pose), r,
+                                                     C.byref(q), C.c_void_p(idx.data_ptr()) if return_indices else None),
+                  symbol + "_device")
+            return (wrap(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else wrap(q)
         s = _host(src, self.DIM)
         n = s.shape[0]
         idx = np.zeros(max(n, 1), dtype=np.uint32) if return_indices else None
-        check(lib().icp_evaluate(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
-                                 C.c_void_p(idx.ctypes.data) if return_indices else None), "icp_evaluate")
-        return (Quality(q), idx[:n]) if return_indices else Quality(q)
+        check(getattr(lib(), symbol)(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
+                                     C.c_void_p(idx.ctypes.data) if return_indices else None), symbol)
+        return (wrap(q), idx[:n]) if return_indices else wrap(q)
 
     def set_single_launch(self, enable=True):
         """small clouds: whole estimate in one launch (default on); off = the general host-driven path"""
@@ -852,26 +848,8 @@ class _Icp:
         contiguous float64 CUDA tensors (used in place)."""
         if self.DIM != 3:
             raise ValueError("evaluate_point_to_plane needs a 3-D handle (Icp3d): a 2-D cloud has no normals")
-        q = _lib.PlaneQualityStruct()
-        r = float(max_correspondence_distance)
-        if _is_device_tensor(src):
-            import torch
-
-            self._dev(src, "src")
-            n = src.shape[0]
-            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_indices else None
-            check(lib().icp_evaluate_point_to_plane_device(self._h, C.c_void_p(src.data_ptr()), n,
-                                                           C.byref(transform.pose), r, C.byref(q),
-                                                           C.c_void_p(idx.data_ptr()) if return_indices else None),
-                  "icp_evaluate_point_to_plane_device")
-            return (PlaneQuality(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else PlaneQuality(q)
-        s = _host(src, self.DIM)
-        n = s.shape[0]
-        idx = np.zeros(max(n, 1), dtype=np.uint32) if return_indices else None
-        check(lib().icp_evaluate_point_to_plane(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
-                                                C.c_void_p(idx.ctypes.data) if return_indices else None),
-              "icp_evaluate_point_to_plane")
-        return (PlaneQuality(q), idx[:n]) if return_indices else PlaneQuality(q)
+        return self._evaluate(_lib.PlaneQualityStruct, PlaneQuality, "icp_evaluate_point_to_plane", src, transform,
+                              max_correspondence_distance, return_indices)
 
     def gate_plane_pairs_device(self, d_src, transform, d_idx, r, d_pairs, d_kept=None):
         """The gate of a gated point-to-plane registration alone (icp_gate_plane_pairs_device): for the inliers of the
@@ -970,26 +948,8 @@ class _Icp:
         state is left as it was.  return_indices=True also returns the correspondences (caller order).  numpy arrays or
         contiguous float64 CUDA tensors (used in place)."""
         self._need_2d("evaluate_point_to_line")
-        q = _lib.LineQualityStruct()
-        r = float(max_correspondence_distance)
-        if _is_device_tensor(src):
-            import torch
-
-            self._dev(src, "src")
-            n = src.shape[0]
-            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_indices else None
-            check(lib().icp_evaluate_point_to_line_device(self._h, C.c_void_p(src.data_ptr()), n,
-                                                          C.byref(transform.pose), r, C.byref(q),
-                                                          C.c_void_p(idx.data_ptr()) if return_indices else None),
-                  "icp_evaluate_point_to_line_device")
-            return (LineQuality(q), idx[:n].cpu().numpy().view(np.uint32)) if return_indices else LineQuality(q)
-        s = _host(src, self.DIM)
-        n = s.shape[0]
-        idx = np.zeros(max(n, 1), dtype=np.uint32) if return_indices else None
-        check(lib().icp_evaluate_point_to_line(self._h, _ptr(s), n, C.byref(transform.pose), r, C.byref(q),
-                                               C.c_void_p(idx.ctypes.data) if return_indices else None),
-              "icp_evaluate_point_to_line")
-        return (LineQuality(q), idx[:n]) if return_indices else LineQuality(q)
+        return self._evaluate(_lib.LineQualityStruct, LineQuality, "icp_evaluate_point_to_line", src, transform,
+                              max_correspondence_distance, return_indices)
 
     def profile_enable(self, every=1):
         """Time every `every`-th NN search launch with HIP events (0 / False: off)."""
@@ -1163,6 +1123,15 @@ class IcpBatch:
         packed = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, self.DIM))
         return packed, firsts, counts
 
+    def _pack_items(self, srcs, dsts, inits):
+        """what the calls over lists of clouds hand to their *_packed twins: (src, dst, items)"""
+        srcs, dsts = list(srcs), list(dsts)
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
+        src, sf, sn = self._pack(srcs, "src")
+        dst, df, dm = self._pack(dsts, "dst")
+        return src, dst, list(zip(sf, sn, df, dm, self._inits(inits, len(srcs))))
+
     @staticmethod
     def _inits(inits, count):
         if inits is None:
@@ -1178,12 +1147,7 @@ class IcpBatch:
         """Register srcs[i] against dsts[i] from inits[i] (a list, one Transform for all, or None: identity).  Returns
         the list of Transforms; with return_info also the per-item indices, the inner counts (count x max_iter) and the
         statuses.  A failed item raises IcpError naming it, unless allow_failures=True (its Transform is then None)."""
-        srcs, dsts = list(srcs), list(dsts)
-        if len(srcs) != len(dsts):
-            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
-        src, sf, sn = self._pack(srcs, "src")
-        dst, df, dm = self._pack(dsts, "dst")
-        items = list(zip(sf, sn, df, dm, self._inits(inits, len(srcs))))
+        src, dst, items = self._pack_items(srcs, dsts, inits)
         return self.estimate_packed(src, dst, items, max_iter, return_info, allow_failures)
 
     def estimate_packed(self, src, dst, items, max_iter, return_info=False, allow_failures=False):
@@ -1269,12 +1233,7 @@ class IcpBatch:
         compute_line_normals(k) from estimate_point_to_line(srcs[i], inits[i], max_iter), bit for bit; items of up to
         1024 source and 2048 target points run as one workgroup each (normals included), the others one by one."""
         self._need_2d("estimate_point_to_line")
-        srcs, dsts = list(srcs), list(dsts)
-        if len(srcs) != len(dsts):
-            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
-        src, sf, sn = self._pack(srcs, "src")
-        dst, df, dm = self._pack(dsts, "dst")
-        items = list(zip(sf, sn, df, dm, self._inits(inits, len(srcs))))
+        src, dst, items = self._pack_items(srcs, dsts, inits)
         return self.estimate_point_to_line_packed(src, dst, items, max_iter, k, return_info, allow_failures)
 
     def estimate_point_to_line_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False):
@@ -1300,12 +1259,7 @@ class IcpBatch:
         item i equals Icp{2,3}d(dsts[i]).evaluate(srcs[i], transforms[i], max_correspondence_distance), bit for bit.
         A failed item raises IcpError naming it, unless allow_failures=True (its Quality is then None);
         return_status=True also returns the statuses."""
-        srcs, dsts = list(srcs), list(dsts)
-        if len(srcs) != len(dsts):
-            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
-        src, sf, sn = self._pack(srcs, "src")
-        dst, df, dm = self._pack(dsts, "dst")
-        items = list(zip(sf, sn, df, dm, self._inits(transforms, len(srcs))))
+        src, dst, items = self._pack_items(srcs, dsts, transforms)
         return self.evaluate_packed(src, dst, items, max_correspondence_distance, allow_failures, return_status)
 
     def evaluate_packed(self, src, dst, items, max_correspondence_distance=float("inf"), allow_failures=False,
@@ -1313,14 +1267,19 @@ class IcpBatch:
         """The same over pre-packed clouds: `items` = [(src_first, n, dst_first, m, Transform), ...] ranges of `src` /
         `dst` (ranges may overlap).  numpy arrays go through icp_batch_evaluate; contiguous float64 CUDA tensors through
         icp_batch_evaluate_device, in place."""
+        return self._evaluate_packed(_lib.QualityStruct, Quality, "icp_batch_evaluate", src, dst, items, [],
+                                     float(max_correspondence_distance), allow_failures, return_status)
+
+    def _evaluate_packed(self, struct, wrap, symbol, src, dst, items, kargs, r, allow_failures, return_status):
+        """evaluate_packed and evaluate_point_to_line_packed (kargs: the normals' neighbours) behind their guards:
+        `symbol` (host arrays) or `symbol`_device (device tensors) fills one `struct` per item, returned as `wrap`s"""
         count = len(items)
         arr = (_lib.BatchItem * max(count, 1))()
         for i, (f, n, g, m, T) in enumerate(items):
             arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
             C.memmove(C.byref(arr[i].init), C.byref(T.pose), C.sizeof(Pose))
-        out = (_lib.QualityStruct * max(count, 1))()
+        out = (struct * max(count, 1))()
         status = np.zeros(max(count, 1), dtype=np.int32)
-        r = float(max_correspondence_distance)
         if _is_device_tensor(src) or _is_device_tensor(dst):
             import torch
 
@@ -1330,22 +1289,22 @@ class IcpBatch:
             _dev_points(dst, self.DIM, self._device, "dst")
             for t in (src, dst):  # (the batch's own stream is not ordered against the producer's)
                 torch.cuda.current_stream(t.device).synchronize()
-            check(lib().icp_batch_evaluate_device(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
-                                                  C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count, r, out,
-                                                  C.c_void_p(status.ctypes.data)), "icp_batch_evaluate_device")
+            check(getattr(lib(), symbol + "_device")(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
+                                                     C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count, *kargs, r,
+                                                     out, C.c_void_p(status.ctypes.data)), symbol + "_device")
         else:
             s, d = _host(src, self.DIM), _host(dst, self.DIM)
-            check(lib().icp_batch_evaluate(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, r, out,
-                                           C.c_void_p(status.ctypes.data)), "icp_batch_evaluate")
+            check(getattr(lib(), symbol)(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, *kargs, r, out,
+                                         C.c_void_p(status.ctypes.data)), symbol)
         status = status[:count]
         qs = []
         for i in range(count):
             if status[i] != _lib.OK:
                 if not allow_failures:
-                    raise IcpError(int(status[i]), f"icp_batch_evaluate item {i}")
+                    raise IcpError(int(status[i]), f"{symbol} item {i}")
                 qs.append(None)
             else:
-                qs.append(Quality(out[i]))
+                qs.append(wrap(out[i]))
         return (qs, status) if return_status else qs
 
     # -- the same under the point-to-line residual (icp_batch_evaluate_point_to_line*, section 16) --
@@ -1358,12 +1317,7 @@ class IcpBatch:
         by one.  A failed item raises IcpError naming it, unless allow_failures=True (its LineQuality is then None);
         return_status=True also returns the statuses."""
         self._need_2d("evaluate_point_to_line")
-        srcs, dsts = list(srcs), list(dsts)
-        if len(srcs) != len(dsts):
-            raise ValueError(f"{len(srcs)} source clouds for {len(dsts)} target clouds")
-        src, sf, sn = self._pack(srcs, "src")
-        dst, df, dm = self._pack(dsts, "dst")
-        items = list(zip(sf, sn, df, dm, self._inits(transforms, len(srcs))))
+        src, dst, items = self._pack_items(srcs, dsts, transforms)
         return self.evaluate_point_to_line_packed(src, dst, items, k, max_correspondence_distance, allow_failures,
                                                   return_status)
 
@@ -1378,41 +1332,8 @@ class IcpBatch:
         r = float(max_correspondence_distance)
         if not r >= 0.0:  # (also a NaN)
             raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
-        count = len(items)
-        arr = (_lib.BatchItem * max(count, 1))()
-        for i, (f, n, g, m, T) in enumerate(items):
-            arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
-            C.memmove(C.byref(arr[i].init), C.byref(T.pose), C.sizeof(Pose))
-        out = (_lib.LineQualityStruct * max(count, 1))()
-        status = np.zeros(max(count, 1), dtype=np.int32)
-        if _is_device_tensor(src) or _is_device_tensor(dst):
-            import torch
-
-            if self._device is None:
-                self._device = src.device.index
-            _dev_points(src, self.DIM, self._device, "src")
-            _dev_points(dst, self.DIM, self._device, "dst")
-            for t in (src, dst):  # (the batch's own stream is not ordered against the producer's)
-                torch.cuda.current_stream(t.device).synchronize()
-            check(lib().icp_batch_evaluate_point_to_line_device(self._b, C.c_void_p(src.data_ptr()), src.shape[0],
-                                                                C.c_void_p(dst.data_ptr()), dst.shape[0], arr, count,
-                                                                int(k), r, out, C.c_void_p(status.ctypes.data)),
-                  "icp_batch_evaluate_point_to_line_device")
-        else:
-            s, d = _host(src, self.DIM), _host(dst, self.DIM)
-            check(lib().icp_batch_evaluate_point_to_line(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count,
-                                                         int(k), r, out, C.c_void_p(status.ctypes.data)),
-                  "icp_batch_evaluate_point_to_line")
-        status = status[:count]
-        qs = []
-        for i in range(count):
-            if status[i] != _lib.OK:
-                if not allow_failures:
-                    raise IcpError(int(status[i]), f"icp_batch_evaluate_point_to_line item {i}")
-                qs.append(None)
-            else:
-                qs.append(LineQuality(out[i]))
-        return (qs, status) if return_status else qs
+        return self._evaluate_packed(_lib.LineQualityStruct, LineQuality, "icp_batch_evaluate_point_to_line", src, dst,
+                                     items, [int(k)], r, allow_failures, return_status)
 
     def line_quality_counters(self):
         """(items scored in a batch launch, items scored one by one, launches, launches not made for want of LDS) of

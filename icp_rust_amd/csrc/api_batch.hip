@@ -8,6 +8,7 @@
 // Sections 9 and 16, the quality of many poses: k_quality_batch (quality.hip) and, with the line residual,
 // k_line_quality_batch (quality_line.hip), one workgroup per item in one launch; one by one: the single calls.
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -92,28 +93,35 @@ bool line_fits(const icp_batch_item &it, size_t max_iter) {
          max_iter <= kLineBatchMaxIter;
 }
 
-// Item i the way a single call serves it: a handle of the pool on the item's targets, icp_estimate_device on its
-// sources.  Per-item outcomes land in *status; anything else (HIP, memory, device) is the call's failure.
-// line_k > 0 (section 15): the handle's line normals from line_k neighbours, then icp_estimate_point_to_line_device.
-int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter, int line_k,
-              icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner) {
+// An item the way single calls serve it: a handle of the pool on the item's targets, serve(h, the item's sources) on it.
+// The outcomes in `per_item` land in *status; anything else (HIP, memory, device) is the call's failure.
+template <typename Serve>
+int with_pool_handle(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it,
+                     std::initializer_list<int> per_item, int *status, Serve serve) {
   icp_handle *h = nullptr;
   int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
   if (rc == ICP_OK) {
-    const double *s = it.n > 0 ? d_src + it.src_first * b->dim : nullptr;
-    if (line_k > 0) {
-      rc = icp_compute_target_line_normals(h, line_k);
-      if (rc == ICP_OK) rc = icp_estimate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
-    } else {
-      rc = icp_estimate_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
-    }
+    rc = serve(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr);
     icp_destroy(h);
   }
-  if (rc == ICP_OK || rc == ICP_NONE || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT) {
-    *status = rc;
-    return ICP_OK;
-  }
+  for (const int s : per_item)
+    if (rc == s) {
+      *status = rc;
+      return ICP_OK;
+    }
   return rc;
+}
+
+// icp_estimate_device on the item's handle; line_k > 0 (section 15): the handle's line normals from line_k neighbours,
+// then icp_estimate_point_to_line_device.
+int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter, int line_k,
+              icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner) {
+  return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_NONE, ICP_EMPTY_DST, ICP_NAN_INPUT}, status,
+                          [&](icp_handle *h, const double *s) {
+                            if (line_k == 0) return icp_estimate_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
+                            ICP_TRY_RC(icp_compute_target_line_normals(h, line_k));
+                            return icp_estimate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
+                          });
 }
 
 // line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line residual, normals from line_k neighbours)
@@ -268,15 +276,10 @@ int estimate_device(icp_batch *b, const double *d_src, size_t src_points, const 
   return run(b, d_src, d_dst, items, count, max_iter, line_k, out, status, d_last_idx, inner_iters);
 }
 
-// the entries that take host clouds: staged through the batch's buffers, the last indices read back
-int estimate_host(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
-                  const icp_batch_item *items, size_t count, size_t max_iter, int line_k, icp_pose *out, int *status,
-                  uint32_t *last_idx, uint32_t *inner_iters) {
-  ICP_TRY_RC(check_args(b, src, src_points, dst, dst_points, items, count, max_iter, out, status, inner_iters));
-  if (count == 0) return ICP_OK;
-  ICP_TRY_RC(ensure_device(b));
-  size_t total_n = 0;
-  for (size_t i = 0; i < count; ++i) total_n += items[i].n;
+// the host entries' clouds, staged through the batch's buffers: *d_src / *d_dst are what run, run_quality
+// and run_line_quality read (null for an empty array)
+int stage_clouds(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                 const double **d_src, const double **d_dst) {
   if (src_points > 0) {
     HIP_TRY(reserve(b->d_src, b->cap_src, src_points * b->dim));
     HIP_TRY(hipMemcpyAsync(b->d_src, src, src_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
@@ -285,13 +288,29 @@ int estimate_host(icp_batch *b, const double *src, size_t src_points, const doub
     HIP_TRY(reserve(b->d_dst, b->cap_dst, dst_points * b->dim));
     HIP_TRY(hipMemcpyAsync(b->d_dst, dst, dst_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
   }
+  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  *d_src = src_points > 0 ? b->d_src : nullptr;
+  *d_dst = dst_points > 0 ? b->d_dst : nullptr;
+  return ICP_OK;
+}
+
+// the entries that take host clouds: staged, the last indices read back
+int estimate_host(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                  const icp_batch_item *items, size_t count, size_t max_iter, int line_k, icp_pose *out, int *status,
+                  uint32_t *last_idx, uint32_t *inner_iters) {
+  ICP_TRY_RC(check_args(b, src, src_points, dst, dst_points, items, count, max_iter, out, status, inner_iters));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  const double *d_src, *d_dst;
+  ICP_TRY_RC(stage_clouds(b, src, src_points, dst, dst_points, &d_src, &d_dst));
+  size_t total_n = 0;
+  for (size_t i = 0; i < count; ++i) total_n += items[i].n;
   // (as icp_estimate: no outer iteration, no correspondences -- last_idx is left as it was)
   const bool want_idx = last_idx && total_n > 0 && max_iter > 0;
   if (want_idx) HIP_TRY(reserve(b->d_idx, b->cap_idx, total_n));
-  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  const int rc = run(b, src_points > 0 ? b->d_src : nullptr, dst_points > 0 ? b->d_dst : nullptr, items, count, max_iter,
-                     line_k, out, status, want_idx ? b->d_idx : nullptr, inner_iters);
+  const int rc = run(b, d_src, d_dst, items, count, max_iter, line_k, out, status, want_idx ? b->d_idx : nullptr,
+                     inner_iters);
   if (rc != ICP_OK) return rc;
   if (want_idx) {
     HIP_TRY(hipMemcpyAsync(last_idx, b->d_idx, total_n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
@@ -361,51 +380,39 @@ bool quality_fits(const icp_batch_item &it) {
   return it.n >= 1 && it.n <= kQualityMaxN && it.m >= 1 && it.m <= kQualityMaxM;
 }
 
-int serve_quality_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, double max_dist,
-                      icp_quality *out, int *status) {
-  icp_handle *h = nullptr;
-  int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
-  if (rc == ICP_OK) {
-    rc = icp_evaluate_device(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr, (size_t)it.n, &it.init, max_dist,
-                             out, nullptr);
-    icp_destroy(h);
+// What both evaluations do before their launch: the items that fit a workgroup (fits) -> fit, the others -> one_by_one;
+// fit's QualityBatchItems (slot: the item's index in the call) copied to b->d_qitems; *m_max: their most targets.
+int stage_quality_items(icp_batch *b, const icp_batch_item *items, size_t count, bool (*fits)(const icp_batch_item &),
+                        std::vector<size_t> *fit, std::vector<size_t> *one_by_one, unsigned *m_max) {
+  *m_max = 0;
+  for (size_t i = 0; i < count; ++i) (fits(items[i]) ? fit : one_by_one)->push_back(i);
+  if (fit->empty()) return ICP_OK;
+  HIP_TRY(reserve_pinned(b->h_qitems, b->cap_h_qitems, fit->size()));
+  HIP_TRY(reserve(b->d_qitems, b->cap_qitems, fit->size()));
+  for (size_t k = 0; k < fit->size(); ++k) {
+    const icp_batch_item &it = items[(*fit)[k]];
+    QualityBatchItem &d = b->h_qitems[k];
+    d.src_first = it.src_first;
+    d.dst_first = it.dst_first;
+    d.n = (unsigned)it.n;
+    d.m = (unsigned)it.m;
+    d.slot = (unsigned)(*fit)[k];
+    d.pad = 0;
+    d.T = it.init;
+    if (d.m > *m_max) *m_max = d.m;
   }
-  if (rc == ICP_OK || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT) {
-    *status = rc;
-    return ICP_OK;
-  }
-  return rc;
+  HIP_TRY(hipMemcpyAsync(b->d_qitems, b->h_qitems, fit->size() * sizeof(QualityBatchItem), hipMemcpyHostToDevice,
+                         b->stream));
+  return ICP_OK;
 }
 
 int run_quality(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
                 double max_dist, icp_quality *out, int *status) {
   std::vector<size_t> fit, one_by_one;
-  unsigned m_max = 0;
-  for (size_t i = 0; i < count; ++i) {
-    if (quality_fits(items[i])) {
-      fit.push_back(i);
-      if (items[i].m > m_max) m_max = (unsigned)items[i].m;
-    } else {
-      one_by_one.push_back(i);
-    }
-  }
+  unsigned m_max;
+  ICP_TRY_RC(stage_quality_items(b, items, count, quality_fits, &fit, &one_by_one, &m_max));
   if (!fit.empty()) {
-    HIP_TRY(reserve_pinned(b->h_qitems, b->cap_h_qitems, fit.size()));
-    HIP_TRY(reserve(b->d_qitems, b->cap_qitems, fit.size()));
     HIP_TRY(reserve_pinned(b->h_qres, b->cap_qres, count));
-    for (size_t k = 0; k < fit.size(); ++k) {
-      const icp_batch_item &it = items[fit[k]];
-      QualityBatchItem &d = b->h_qitems[k];
-      d.src_first = it.src_first;
-      d.dst_first = it.dst_first;
-      d.n = (unsigned)it.n;
-      d.m = (unsigned)it.m;
-      d.slot = (unsigned)fit[k];
-      d.pad = 0;
-      d.T = it.init;
-    }
-    HIP_TRY(hipMemcpyAsync(b->d_qitems, b->h_qitems, fit.size() * sizeof(QualityBatchItem), hipMemcpyHostToDevice,
-                           b->stream));
     // (r * r in f64 on the host, as icp_evaluate_device forms it)
     HIP_TRY(launch_quality_batch(b->dim, m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist,
                                  b->h_qres, b->stream));
@@ -417,28 +424,13 @@ int run_quality(icp_batch *b, const double *d_src, const double *d_dst, const ic
     }
   }
   for (size_t i : one_by_one) {
-    ICP_TRY_RC(serve_quality_one(b, d_src, d_dst, items[i], max_dist, &out[i], &status[i]));
+    ICP_TRY_RC(with_pool_handle(b, d_src, d_dst, items[i], {ICP_OK, ICP_EMPTY_DST, ICP_NAN_INPUT}, &status[i],
+                                [&](icp_handle *h, const double *s) {
+                                  return icp_evaluate_device(h, s, (size_t)items[i].n, &items[i].init, max_dist, &out[i],
+                                                             nullptr);
+                                }));
     ++b->qctr[1];
   }
-  return ICP_OK;
-}
-
-// the host entries' clouds, staged through the batch's buffers: *d_src / *d_dst are what run_quality and
-// run_line_quality read (null for an empty array)
-int stage_clouds(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
-                 const double **d_src, const double **d_dst) {
-  if (src_points > 0) {
-    HIP_TRY(reserve(b->d_src, b->cap_src, src_points * b->dim));
-    HIP_TRY(hipMemcpyAsync(b->d_src, src, src_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  }
-  if (dst_points > 0) {
-    HIP_TRY(reserve(b->d_dst, b->cap_dst, dst_points * b->dim));
-    HIP_TRY(hipMemcpyAsync(b->d_dst, dst, dst_points * b->dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  }
-  // (the items served one by one run on their handles' streams: the staged clouds must have landed first)
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  *d_src = src_points > 0 ? b->d_src : nullptr;
-  *d_dst = dst_points > 0 ? b->d_dst : nullptr;
   return ICP_OK;
 }
 
@@ -480,57 +472,26 @@ bool line_quality_fits(const icp_batch_item &it) {
   return it.n >= 1 && it.n <= kLineQualityMaxN && it.m >= 1 && it.m <= kLineQualityMaxM;
 }
 
-// (the first failing step's status is the item's: ICP_EMPTY_DST and ICP_BAD_ARGUMENT -- targets section 14 refuses --
-// come from the normals, ICP_NAN_INPUT from the evaluation; *out then holds n and zeros)
+// One by one: the first failing step's status is the item's -- ICP_EMPTY_DST and ICP_BAD_ARGUMENT (targets section 14
+// refuses) come from the normals, ICP_NAN_INPUT from the evaluation; *out then holds n and zeros.
 int serve_line_quality_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, int k,
                            double max_dist, icp_line_quality *out, int *status) {
-  line_quality_clear((size_t)it.n, out);
-  icp_handle *h = nullptr;
-  int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
-  if (rc == ICP_OK) {
-    rc = icp_compute_target_line_normals(h, k);
-    if (rc == ICP_OK)
-      rc = icp_evaluate_point_to_line_device(h, it.n > 0 ? d_src + it.src_first * b->dim : nullptr, (size_t)it.n, &it.init,
-                                             max_dist, out, nullptr);
-    icp_destroy(h);
-  }
-  if (rc == ICP_OK || rc == ICP_EMPTY_DST || rc == ICP_NAN_INPUT || rc == ICP_BAD_ARGUMENT) {
-    *status = rc;
-    return ICP_OK;
-  }
-  return rc;
+  quality_clear((size_t)it.n, out);
+  return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_EMPTY_DST, ICP_NAN_INPUT, ICP_BAD_ARGUMENT}, status,
+                          [&](icp_handle *h, const double *s) {
+                            ICP_TRY_RC(icp_compute_target_line_normals(h, k));
+                            return icp_evaluate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_dist, out, nullptr);
+                          });
 }
 
 int run_line_quality(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
                      int k, double max_dist, icp_line_quality *out, int *status) {
   std::vector<size_t> fit, one_by_one;
-  unsigned m_max = 0;
-  for (size_t i = 0; i < count; ++i) {
-    if (line_quality_fits(items[i])) {
-      fit.push_back(i);
-      if (items[i].m > m_max) m_max = (unsigned)items[i].m;
-    } else {
-      one_by_one.push_back(i);
-    }
-  }
+  unsigned m_max;
+  ICP_TRY_RC(stage_quality_items(b, items, count, line_quality_fits, &fit, &one_by_one, &m_max));
   if (!fit.empty()) {
-    HIP_TRY(reserve_pinned(b->h_qitems, b->cap_h_qitems, fit.size()));
-    HIP_TRY(reserve(b->d_qitems, b->cap_qitems, fit.size()));
     HIP_TRY(reserve_pinned(b->h_lqres, b->cap_lqres, count));
-    for (size_t j = 0; j < fit.size(); ++j) {
-      const icp_batch_item &it = items[fit[j]];
-      QualityBatchItem &d = b->h_qitems[j];
-      d.src_first = it.src_first;
-      d.dst_first = it.dst_first;
-      d.n = (unsigned)it.n;
-      d.m = (unsigned)it.m;
-      d.slot = (unsigned)fit[j];
-      d.pad = 0;
-      d.T = it.init;
-      b->h_lqres[fit[j]].pad = 1;  // handed back, unless its workgroup writes the record
-    }
-    HIP_TRY(hipMemcpyAsync(b->d_qitems, b->h_qitems, fit.size() * sizeof(QualityBatchItem), hipMemcpyHostToDevice,
-                           b->stream));
+    for (size_t i : fit) b->h_lqres[i].pad = 1;  // handed back, unless its workgroup writes the record
     bool granted = true;
     // (r * r in f64 on the host, as icp_evaluate_point_to_line_device forms it)
     HIP_TRY(launch_line_quality_batch(m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist, k,

@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "common.hpp"
 #include "gn_loop.hpp"
@@ -49,6 +50,13 @@ inline bool sized_args_ok(const icp_handle *h, const void *src, size_t n, const 
 // points to ask ensure_workspace for: the scratch of a gate or an evaluation (tile counts, level records) lives in the
 // per-point buffers and needs 256 points' worth even for the smallest cloud
 inline size_t workspace_points(size_t n) { return n < 256 ? 256 : n; }
+// n and zeros: what the *out of an evaluation (icp_quality, icp_plane_quality, icp_line_quality) holds unless a result
+// replaces it
+template <typename Q>
+void quality_clear(size_t n, Q *q) {
+  std::memset(q, 0, sizeof(*q));
+  q->n = n;
+}
 // Whatever way the call that holds it ends, nothing of it is in flight on h->stream afterwards, and the search snapshot
 // it may have taken (the cell-sorted copy, keyed on a buffer the caller may now rewrite) is dropped, as
 // icp_estimate_device drops its own.  slot_order is cleared for icp_estimate_gated_device, the one holder that sets it;

@@ -562,8 +562,7 @@ struct FoldPart {
 constexpr int kQualitySums = 6;
 using QualityPart = FoldPart<kQualitySums>;
 static_assert(sizeof(QualityPart) == 64, "eight doubles per record: ceil(n / 256) of them fit in max(n, 256)");
-// host: n and zeros; the fields of section 9 from the root record (ICP_NAN_INPUT where it carries the flag)
-void quality_clear(size_t n, icp_quality *q);
+// host: the fields of section 9 from the root record (ICP_NAN_INPUT where it carries the flag)
 int quality_result(size_t n, const QualityPart &p, icp_quality *q);
 // icp_batch_evaluate (api_batch.hip): items of up to kQualityMaxN source and kQualityMaxM target points run as one
 // workgroup of kQualityBatchThreads each (k_quality_batch), which writes res[slot]
@@ -577,11 +576,13 @@ struct QualityBatchItem {
 hipError_t launch_quality_batch(int dim, unsigned m_max, const double *d_src, const double *d_dst,
                                 const QualityBatchItem *d_items, unsigned count, double r2, QualityPart *res,
                                 hipStream_t stream);
-// EXTENSION: the quality of a pose under the point-to-line residual (quality_line.hip; include/icp_mi355x.h section 16).
-// Its ten sums: inlier d2, inlier p2, p2, rho(p2), and the six entries of the inlier pairs' J^T J, J = (nx, ny, c).
-constexpr int kLineQualitySums = 10;
-using LineQualityPart = FoldPart<kLineQualitySums>;
-void line_quality_clear(size_t n, icp_line_quality *q);
+// EXTENSION: the quality of a pose under a normal-based residual: point-to-plane (quality_plane.hip; include/icp_mi355x.h
+// section 13) and point-to-line (quality_line.hip; section 16).  The ten sums of both (quality_device.hpp): inlier d2,
+// inlier p2, p2, rho(p2), and the six entries of the inlier pairs' J^T J, J = (nx, ny, c).
+constexpr int kNormalQualitySums = 10;
+using NormalQualityPart = FoldPart<kNormalQualitySums>;
+using LineQualityPart = NormalQualityPart;
+static_assert(sizeof(NormalQualityPart) == 96, "twelve doubles per record: ceil(n / 256) of them fit in max(n, 256)");
 int line_quality_result(size_t n, const LineQualityPart &p, icp_line_quality *q);
 // icp_batch_evaluate_point_to_line (api_batch.hip): items of up to kLineQualityMaxN source and kLineQualityMaxM target
 // points run as one workgroup of 1024 threads each (k_line_quality_batch), which computes the item's line normals from k

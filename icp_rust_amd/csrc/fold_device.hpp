@@ -1,8 +1,9 @@
-// The fixed fold tree of include/icp_mi355x.h section 9, shared by the pose quality (quality.hip, six sums) and the
-// point-to-plane pose quality (quality_plane.hip, ten): groups of kFoldGroup values, g[i] += g[i + s] for s = 128, 64,
-// ..., 1 inside a group, the inlier counts added and the NaN flags or-ed beside the sums, one record (common.hpp:
-// FoldPart) per group, level after level down to one.  This tree IS the definition of a result's bits: nothing crosses
-// workgroups inside a launch and no sum uses atomics, so a result is a pure function of the inputs.
+// The fixed fold tree of include/icp_mi355x.h section 9, shared by the three pose qualities: point (quality.hip, six
+// sums), point-to-plane (quality_plane.hip, ten) and point-to-line (quality_line.hip, ten), single calls and batches.
+// Groups of kFoldGroup values, g[i] += g[i + s] for s = 128, 64, ..., 1 inside a group, the inlier counts added and the
+// NaN flags or-ed beside the sums, one record (common.hpp: FoldPart) per group, level after level down to one.  This
+// tree IS the definition of a result's bits: nothing crosses workgroups inside a launch and no sum uses atomics, so a
+// result is a pure function of the inputs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,6 +75,37 @@ __device__ __forceinline__ FoldPart<SUMS> fold_take(const FoldLds<SUMS> &L) {
 #pragma unroll
   for (int k = 0; k < SUMS; ++k) v[k] = L.v[k][0];
   return fold_part(v, L.c[0], L.f[0]);
+}
+
+// The whole tree of one batch item inside its workgroup: thread tid < n holds a point's terms (the others +0.0), n <=
+// the workgroup's size, and every thread calls it (barriers; n is uniform).  The tree over each group of 256 points, then
+// over the group records (grp: room for one per group), as the levels of a single call fold them; thread 0 writes *out.
+// n == 1: *out is the one point's terms (the fold of one value is the value: no +0.0 added, a -0.0 stays).
+template <int SUMS>
+__device__ __forceinline__ void fold_workgroup(FoldLds<SUMS> &L, FoldPart<SUMS> *grp, unsigned tid, unsigned n,
+                                               const double (&v)[SUMS], unsigned in, unsigned nan, FoldPart<SUMS> *out) {
+  if (n == 1) {
+    if (tid == 0) *out = fold_part(v, in, nan);
+    return;
+  }
+  const unsigned groups = (n + kFoldGroup - 1) / kFoldGroup;
+  for (unsigned g = 0; g < groups; ++g) {
+    const unsigned lane = tid - g * kFoldGroup;  // (wraps for the threads below the group: never < kFoldGroup then)
+    if (lane < kFoldGroup) fold_put(L, lane, v, in, nan);
+    fold_group(L, tid);
+    if (tid == 0) grp[g] = fold_take(L);
+    __syncthreads();
+  }
+  if (groups == 1) {
+    if (tid == 0) *out = grp[0];
+    return;
+  }
+  if (tid < kFoldGroup) {
+    if (tid < groups) fold_put(L, tid, grp[tid].v, grp[tid].inliers, grp[tid].nan);
+    else fold_put_zero(L, tid);
+  }
+  fold_group(L, tid);
+  if (tid == 0) *out = fold_take(L);
 }
 
 // a level of the tree: records [256 g, 256 g + 256) of `in` (k of them), +0.0 beyond, folded -> out[g]

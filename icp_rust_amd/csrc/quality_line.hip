@@ -1,89 +1,33 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 16): the quality of a pose under the point-to-LINE
 // residual of section 14 -- fitness, inlier RMSE, line RMSE, error / huber_error of the line residual and the SE(2)
 // information matrix that residual gives -- at a GIVEN pose, for a 2-D handle with current line normals, as a single
-// call and as a batch.  Section 13 (quality_plane.hip) with the third coordinate removed.
+// call and as a batch.  Section 13 (quality_plane.hip) with the third coordinate removed: the terms, the level-1 body,
+// the single calls' driver, the entries' decisions and the result's fields are written once for both, in
+// quality_device.hpp.
 //   k_line_quality_terms  one workgroup per 256 source points: a lane gathers src[i], idx[i], dst[j], nrm[j] once (52 B),
 //                         forms the ten terms of section 16, and the group folds them by the tree of section 9
-//                         (fold_device.hpp) into one 96-byte record
+//                         (fold_device.hpp) into one 96-byte record; its body is normal_quality_level1<2>
 //   k_fold_level<10>      the next level of the same tree: one workgroup per 256 records (as many launches as levels)
 //   k_line_quality_batch  one workgroup per item of icp_batch_evaluate_point_to_line: the item's box, its targets sorted
 //                         into LDS, their line normals (p2line_device.hpp: the sweep k_line_estimate_batch runs), the
-//                         exact nearest neighbour of every moved source point (tiny_nearest), the same terms and the same
-//                         tree as k_quality_batch folds it (api_batch.hip drives it)
+//                         exact nearest neighbour of every moved source point (tiny_nearest), the same terms and the tree
+//                         of a batch item, fold_workgroup, as k_quality_batch folds it (api_batch.hip drives it)
 // Every sum is the fixed tree, so a result is a pure function of the inputs, whichever kernel computed it.
-#include <cmath>
-#include <cstring>
-
-#include "api_internal.hpp"
-#include "fold_device.hpp"
-#include "gn_device.hpp"
 #include "p2line_device.hpp"
+#include "quality_device.hpp"
 #include "tiny_device.hpp"
 
 using namespace icp;
 using namespace icp::api;
 
 namespace icp {
-namespace {
 
-static_assert(sizeof(LineQualityPart) == 96, "twelve doubles per record: ceil(n / 256) of them fit in max(n, 256)");
-
-// A point's terms: the expressions of section 16 (the library is built with -ffp-contract=off: no FMA).  q is the moved
-// source point, b the matched target, (nx, ny) its line normal.  plane_residual (p2plane_device.hpp) adds a trailing
-// + nz dz = + 0.0 to rp; the square does not see it (it only turns a -0.0 into +0.0), so it is left out here.
-__device__ __forceinline__ void line_quality_terms(double qx, double qy, double bx, double by, double nx, double ny,
-                                                   double r2, double v[kLineQualitySums], unsigned &in, unsigned &nan) {
-  const double ex = qx - bx, ey = qy - by;
-  const double d2 = ex * ex + ey * ey;  // the 2-D icp_evaluate's d2
-  const bool inl = d2 <= r2;            // (false for a NaN d2)
-  const double rp = nx * ex + ny * ey;
-  const double p2 = rp * rp;
-  const double c = nx * (-qy) + ny * qx;  // J[2] of k_p2pl_accumulate at identity, a = q; J[0] = nx, J[1] = ny
-  v[0] = inl ? d2 : 0.;
-  v[1] = inl ? p2 : 0.;
-  v[2] = p2;
-  v[3] = huber_rho(p2);
-  v[4] = inl ? nx * nx : 0.;
-  v[5] = inl ? nx * ny : 0.;
-  v[6] = inl ? ny * ny : 0.;
-  v[7] = inl ? nx * c : 0.;
-  v[8] = inl ? ny * c : 0.;
-  v[9] = inl ? c * c : 0.;
-  in = inl ? 1u : 0u;
-  nan = (p2 != p2) ? 1u : 0u;
-}
-
-}  // namespace
-
-// level 1: the terms of source points [256 g, 256 g + 256), folded -> out[g].  n == 1: out[0] is the one point's terms
-// (the fold of one value is the value: no +0.0 added, a -0.0 stays).  src and dst at a stride of 2; the normals at the
-// stride of 3 they are stored with (nz = +0.0 is there and is not read).
 __global__ __launch_bounds__(256) void k_line_quality_terms(const double *__restrict__ src, unsigned n, Pose T,
                                                             const uint32_t *__restrict__ idx,
                                                             const double *__restrict__ dst,
                                                             const double *__restrict__ nrm, unsigned m, double r2,
                                                             LineQualityPart *__restrict__ out) {
-  __shared__ FoldLds<kLineQualitySums> L;
-  const unsigned tid = threadIdx.x;
-  const size_t i = (size_t)blockIdx.x * kFoldGroup + tid;
-  double v[kLineQualitySums] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
-  unsigned in = 0, nan = 0;
-  if (i < n) {
-    const double px = src[i * 2], py = src[i * 2 + 1];
-    const double qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24
-    const double qy = (T.r10 * px + T.r11 * py) + T.ty;
-    uint32_t j = idx[i];
-    if (j >= m) j = 0;  // (the search always answers j < m: this only keeps the reads in bounds)
-    const double *b = dst + (size_t)j * 2, *nj = nrm + (size_t)j * 3;
-    line_quality_terms(qx, qy, b[0], b[1], nj[0], nj[1], r2, v, in, nan);
-  }
-  if (n == 1) {
-    if (tid == 0) out[0] = fold_part(v, in, nan);
-    return;
-  }
-  fold_put(L, tid, v, in, nan);
-  fold_group(L, tid);
-  if (tid == 0) out[blockIdx.x] = fold_take(L);
+  normal_quality_level1<2>(src, n, T, idx, dst, nrm, m, r2, out);
 }
 
 // ---- the LDS plan of a batch launch ----
@@ -98,7 +42,7 @@ namespace {
 constexpr unsigned kLineQualityThreads = 1024;
 constexpr size_t kLineQualityListBytes = kLineKMax * (sizeof(double) + sizeof(uint32_t));
 constexpr size_t kLineQualityFoldBytes =
-    sizeof(FoldLds<kLineQualitySums>) + (kLineQualityMaxN / kFoldGroup) * sizeof(LineQualityPart);
+    sizeof(FoldLds<kNormalQualitySums>) + (kLineQualityMaxN / kFoldGroup) * sizeof(LineQualityPart);
 constexpr size_t kLineQualityCtlBytes = 256;
 struct LineQualityCtl {
   unsigned pos0;  // the sorted position of the target of original index 0
@@ -186,7 +130,7 @@ __global__ __launch_bounds__(kLineQualityThreads) void k_line_quality_batch(cons
   line_normals_of_sorted_targets(tg, cx, cy, scale, kk, L, shared, nrm);
 
   // ---- transform, exact nearest neighbour from a cold start, the ten terms ----
-  double v[kLineQualitySums] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
+  double v[kNormalQualitySums] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
   unsigned in = 0, nan = 0;
   if (tid < n) {
     const double px = src[(size_t)tid * 2], py = src[(size_t)tid * 2 + 1];
@@ -196,34 +140,14 @@ __global__ __launch_bounds__(kLineQualityThreads) void k_line_quality_batch(cons
     tiny_nearest<2>(tg, qx, qy, 0., cx, cy, cz, scale, 0xffffffffu, &nb, &nbo);
     if (nb == 0xffffffffu) nb = C->pos0;  // no finite distance (NaN query): index 0, as a scan from 0 would
     const double2 nq = nrm[nb];
-    line_quality_terms(qx, qy, tx[nb], ty[nb], nq.x, nq.y, r2, v, in, nan);
+    const double q[2] = {qx, qy}, b[2] = {tx[nb], ty[nb]}, nn[2] = {nq.x, nq.y};
+    normal_quality_terms<2>(q, b, nn, r2, v, in, nan);
   }
-  if (n == 1) {  // (uniform across the workgroup)
-    if (tid == 0) res[item.slot] = fold_part(v, in, nan);
-    return;
-  }
-  // ---- the tree over each group of 256 points, then over the (up to four) group records: k_quality_batch's ----
+  // ---- the tree of a batch item, k_quality_batch's ----
   // (the normals' lists are dead since the barrier behind their last round: the fold takes their place)
-  FoldLds<kLineQualitySums> &F = *reinterpret_cast<FoldLds<kLineQualitySums> *>(shared);
-  LineQualityPart *grp = reinterpret_cast<LineQualityPart *>(shared + sizeof(FoldLds<kLineQualitySums>));
-  const unsigned groups = (n + kFoldGroup - 1) / kFoldGroup;
-  for (unsigned g = 0; g < groups; ++g) {
-    const unsigned lane = tid - g * kFoldGroup;  // (wraps for the threads below the group: never < kFoldGroup then)
-    if (lane < kFoldGroup) fold_put(F, lane, v, in, nan);
-    fold_group(F, tid);
-    if (tid == 0) grp[g] = fold_take(F);
-    __syncthreads();
-  }
-  if (groups == 1) {
-    if (tid == 0) res[item.slot] = grp[0];
-    return;
-  }
-  if (tid < kFoldGroup) {
-    if (tid < groups) fold_put(F, tid, grp[tid].v, grp[tid].inliers, grp[tid].nan);
-    else fold_put_zero(F, tid);
-  }
-  fold_group(F, tid);
-  if (tid == 0) res[item.slot] = fold_take(F);
+  FoldLds<kNormalQualitySums> &F = *reinterpret_cast<FoldLds<kNormalQualitySums> *>(shared);
+  LineQualityPart *grp = reinterpret_cast<LineQualityPart *>(shared + sizeof(FoldLds<kNormalQualitySums>));
+  fold_workgroup(F, grp, tid, n, v, in, nan, &res[item.slot]);
 }
 
 hipError_t launch_line_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
@@ -239,76 +163,24 @@ hipError_t launch_line_quality_batch(unsigned m_max, const double *d_src, const 
   return hipGetLastError();
 }
 
-// n and zeros: what *out holds unless a result replaces it
-void line_quality_clear(size_t n, icp_line_quality *q) {
-  std::memset(q, 0, sizeof(*q));
-  q->n = n;
-}
-
 // The fields of section 16 from the root record, on the host (both entries and the batch share it: same bits).
 int line_quality_result(size_t n, const LineQualityPart &p, icp_line_quality *q) {
-  line_quality_clear(n, q);
-  if (n == 0) return ICP_OK;
-  if (p.nan) return ICP_NAN_INPUT;  // (the estimator's rule: a NaN residual)
-  q->inliers = p.inliers;
-  q->fitness = (double)p.inliers / (double)n;
-  q->inlier_sum_d2 = p.v[0];
-  q->inlier_rmse = p.inliers ? std::sqrt(p.v[0] / (double)p.inliers) : 0.;
-  q->line_sum_r2 = p.v[1];
-  q->line_rmse = p.inliers ? std::sqrt(p.v[1] / (double)p.inliers) : 0.;
-  q->error = p.v[2];
-  q->huber_error = p.v[3];
-  const double ixx = p.v[4], ixy = p.v[5], iyy = p.v[6], ixt = p.v[7], iyt = p.v[8], itt = p.v[9];
-  const double info[9] = {ixx, ixy, ixt, ixy, iyy, iyt, ixt, iyt, itt};
-  std::memcpy(q->information, info, sizeof(info));
-  // the eigenvalues of the translation block with + - * sqrt only (host code is built without FMA contraction too)
-  const double h = (ixx + iyy) * 0.5;
-  const double g = (ixx - iyy) * 0.5;
-  const double s = std::sqrt(g * g + ixy * ixy);
-  q->translation_eig[0] = h - s;
-  q->translation_eig[1] = h + s;
-  return ICP_OK;
+  return normal_quality_result(n, p, q, &icp_line_quality::line_sum_r2, &icp_line_quality::line_rmse);
 }
 
 }  // namespace icp
 
 namespace {
 
-// What both entries decide before any work, in the order section 16 gives: the arguments, n == 0, the device, and only
-// then the handle.  *done: the status is final.
-int line_evaluate_enter(icp_handle *h, const void *src, size_t n, const icp_pose *T, double max_dist,
-                        icp_line_quality *out, bool *done) {
-  *done = true;
-  if (out) line_quality_clear(n, out);
-  if (!sized_args_ok(h, src, n, T, max_dist, out)) return ICP_BAD_ARGUMENT;
-  if (n == 0) return ICP_OK;
-  if (!have_device()) return ICP_NO_DEVICE;
-  if (h->dim != 2 || h->normals_m != h->m) return ICP_BAD_ARGUMENT;  // icp_compute_target_line_normals first (again after an append)
-  if (h->m == 0) return ICP_EMPTY_DST;
-  *done = false;
-  return ICP_OK;
-}
-
-// The device part of both entries: the handle's search at T, then the terms and the tree.
+// The device part of both entries: the handle's exact 2-D search at T, then the terms and the tree.
 int line_evaluate(icp_handle *h, const double *d_src, size_t n, const Pose &T, double max_dist, icp_line_quality *out,
                   uint32_t *d_idx) {
-  Quiesce quiesce_on_exit{h};
-  Workspace &w = h->ws;
-  // (the level records live in the residual buffers: ceil(n / 256) records of 12 doubles fit in max(n, 256) doubles)
-  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
-  uint32_t *idx = d_idx ? d_idx : w.d_idx;
-  ICP_TRY_RC(icp_prepare_source_device(h, d_src, n, &T));
-  ICP_TRY_RC(icp_correspond_device(h, d_src, n, &T, nullptr, nullptr, idx));  // exact 2-D NN
   const double r2 = max_dist * max_dist;
-  const unsigned k = (unsigned)((n + kFoldGroup - 1) / kFoldGroup);
-  LineQualityPart *cur = reinterpret_cast<LineQualityPart *>(w.d_rx), *nxt = reinterpret_cast<LineQualityPart *>(w.d_ry);
-  hipLaunchKernelGGL(k_line_quality_terms, dim3(k), dim3(kFoldGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
-                     (const double *)h->d_normals, (unsigned)h->m, r2, cur);
-  HIP_TRY(hipGetLastError());
-  LineQualityPart r, *root;
-  HIP_TRY(fold_levels(cur, nxt, k, h->stream, &root));
-  HIP_TRY(hipMemcpyAsync(&r, root, sizeof(r), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  LineQualityPart r;
+  ICP_TRY_RC(evaluate_on_handle(h, d_src, n, T, d_idx, false, [&](const uint32_t *idx, unsigned k, LineQualityPart *cur) {
+    hipLaunchKernelGGL(k_line_quality_terms, dim3(k), dim3(kFoldGroup), 0, h->stream, d_src, (unsigned)n, T, idx, h->d_dst,
+                       (const double *)h->d_normals, (unsigned)h->m, r2, cur);
+  }, &r));
   return line_quality_result(n, r, out);
 }
 
@@ -317,7 +189,7 @@ int line_evaluate(icp_handle *h, const double *d_src, size_t n, const Pose &T, d
 extern "C" int icp_evaluate_point_to_line_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T,
                                                  double max_dist, icp_line_quality *out, uint32_t *d_idx) {
   bool done;
-  const int rc = line_evaluate_enter(h, d_src, n, T, max_dist, out, &done);
+  const int rc = normal_evaluate_enter(h, d_src, n, T, max_dist, out, 2, &done);
   if (done) return rc;
   HIP_TRY(hipSetDevice(h->device));
   return line_evaluate(h, d_src, n, *T, max_dist, out, d_idx);
@@ -326,15 +198,10 @@ extern "C" int icp_evaluate_point_to_line_device(icp_handle *h, const double *d_
 extern "C" int icp_evaluate_point_to_line(icp_handle *h, const double *src, size_t n, const icp_pose *T, double max_dist,
                                           icp_line_quality *out, uint32_t *idx) {
   bool done;
-  const int erc = line_evaluate_enter(h, src, n, T, max_dist, out, &done);
-  if (done) return erc;
+  const int rc = normal_evaluate_enter(h, src, n, T, max_dist, out, 2, &done);
+  if (done) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, workspace_points(n), true));
-  HIP_TRY(hipMemcpyAsync(h->ws.d_src, src, n * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  const int rc = line_evaluate(h, h->ws.d_src, n, *T, max_dist, out, h->ws.d_idx);
-  if ((rc == ICP_OK || rc == ICP_NAN_INPUT) && idx) {  // (the search ran: its correspondences are there either way)
-    HIP_TRY(hipMemcpyAsync(idx, h->ws.d_idx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return rc;
+  return evaluate_staged(h, src, n, idx, [&](const double *d_src, uint32_t *d_idx) {
+    return line_evaluate(h, d_src, n, *T, max_dist, out, d_idx);
+  });
 }
