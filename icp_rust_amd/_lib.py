@@ -240,6 +240,11 @@ SIGNATURES = {
     "icp_batch_estimate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, _vp, _vp, _vp,
                                                           _vp]),
     "icp_batch_line_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_batch_estimate_point_to_line_gated": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, C.c_double, _vp,
+                                                         _vp, _vp, _vp, _vp]),
+    "icp_batch_estimate_point_to_line_gated_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, C.c_double,
+                                                                _vp, _vp, _vp, _vp, _vp]),
+    "icp_batch_line_gated_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_evaluate_point_to_line": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_evaluate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_batch_evaluate_point_to_line": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp, _vp]),

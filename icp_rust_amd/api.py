@@ -1156,11 +1156,14 @@ class IcpBatch:
         through icp_batch_estimate_device, in place."""
         return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, None)
 
-    def _estimate_packed(self, src, dst, items, max_iter, return_info, allow_failures, line_k):
-        """estimate_packed (line_k None) and estimate_point_to_line_packed (line_k = the normals' neighbours)"""
+    def _estimate_packed(self, src, dst, items, max_iter, return_info, allow_failures, line_k, max_dist=None):
+        """estimate_packed (line_k None) and estimate_point_to_line_packed (line_k = the normals' neighbours; max_dist:
+        the gated entries, which also fill the inlier counts)"""
         count = len(items)
-        name = what = "icp_batch_estimate" if line_k is None else "icp_batch_estimate_point_to_line"
+        name = "icp_batch_estimate" if line_k is None else "icp_batch_estimate_point_to_line"
+        name = what = name + ("" if max_dist is None else "_gated")
         kargs = [] if line_k is None else [int(line_k)]
+        gargs = [] if max_dist is None else [float(max_dist)]
         arr = (_lib.BatchItem * max(count, 1))()
         for i, (f, n, g, m, T) in enumerate(items):
             arr[i].src_first, arr[i].n, arr[i].dst_first, arr[i].m = int(f), int(n), int(g), int(m)
@@ -1168,6 +1171,8 @@ class IcpBatch:
         out = (Pose * max(count, 1))()
         status = np.zeros(max(count, 1), dtype=np.int32)
         inner = np.zeros(max(count * max_iter, 1), dtype=np.uint32)
+        inl = np.zeros(max(count * max_iter, 1), dtype=np.uint32)
+        iargs = [] if max_dist is None else [C.c_void_p(inl.ctypes.data)]
         total = sum(int(it[1]) for it in items)
         want_idx = bool(return_info)
         if _is_device_tensor(src) or _is_device_tensor(dst):
@@ -1182,17 +1187,17 @@ class IcpBatch:
             idx = torch.zeros(max(total, 1), dtype=torch.int32, device=src.device) if want_idx else None
             name += "_device"
             check(getattr(lib(), name)(self._b, C.c_void_p(src.data_ptr()), src.shape[0], C.c_void_p(dst.data_ptr()),
-                                       dst.shape[0], arr, count, *kargs, max_iter, out, C.c_void_p(status.ctypes.data),
-                                       C.c_void_p(idx.data_ptr()) if want_idx else None,
-                                       C.c_void_p(inner.ctypes.data)), name)
+                                       dst.shape[0], arr, count, *kargs, max_iter, *gargs, out,
+                                       C.c_void_p(status.ctypes.data), C.c_void_p(idx.data_ptr()) if want_idx else None,
+                                       C.c_void_p(inner.ctypes.data), *iargs), name)
             idx = idx.cpu().numpy().view(np.uint32) if want_idx else None
         else:
             s, d = _host(src, self.DIM), _host(dst, self.DIM)
             idx = np.zeros(max(total, 1), dtype=np.uint32) if want_idx else None
             check(getattr(lib(), name)(self._b, _ptr(s), s.shape[0], _ptr(d), d.shape[0], arr, count, *kargs, max_iter,
-                                       out, C.c_void_p(status.ctypes.data),
+                                       *gargs, out, C.c_void_p(status.ctypes.data),
                                        C.c_void_p(idx.ctypes.data) if want_idx else None,
-                                       C.c_void_p(inner.ctypes.data)), name)
+                                       C.c_void_p(inner.ctypes.data), *iargs), name)
         status = status[:count]
         Ts = []
         for i in range(count):
@@ -1208,7 +1213,8 @@ class IcpBatch:
         for it in items:
             idxs.append(idx[at:at + int(it[1])])
             at += int(it[1])
-        return Ts, idxs, inner[:count * max_iter].reshape(count, max_iter), status
+        info = (Ts, idxs, inner[:count * max_iter].reshape(count, max_iter), status)
+        return info if max_dist is None else info + (inl[:count * max_iter].reshape(count, max_iter),)
 
     def estimate_hypotheses(self, src, dst, inits, max_iter):
         """One scan against one map from K initial poses (one shared src range and dst range: nothing is copied per
@@ -1228,28 +1234,48 @@ class IcpBatch:
         if self.DIM != 2:
             raise ValueError(f"{what} needs a 2-D batch (IcpBatch(2)): the line residual is section 14's, for 2-D scans")
 
-    def estimate_point_to_line(self, srcs, dsts, inits, max_iter, k=10, return_info=False, allow_failures=False):
+    def estimate_point_to_line(self, srcs, dsts, inits, max_iter, k=10, return_info=False, allow_failures=False,
+                               max_correspondence_distance=None):
         """estimate() with the point-to-line residual: item i is what Icp2d(dsts[i]) returns after
         compute_line_normals(k) from estimate_point_to_line(srcs[i], inits[i], max_iter), bit for bit; items of up to
-        1024 source and 2048 target points run as one workgroup each (normals included), the others one by one."""
+        1024 source and 2048 target points run as one workgroup each (normals included), the others one by one.
+
+        `max_correspondence_distance=r` (icp_batch_estimate_point_to_line_gated*, section 17): item i is what that
+        single call returns with the same r -- the inner loop of each outer iteration sees only the pairs within r;
+        `return_info` then returns (Ts, idxs, inner, status, inliers), inliers count x max_iter.  None: the ungated call."""
         self._need_2d("estimate_point_to_line")
         src, dst, items = self._pack_items(srcs, dsts, inits)
-        return self.estimate_point_to_line_packed(src, dst, items, max_iter, k, return_info, allow_failures)
+        return self.estimate_point_to_line_packed(src, dst, items, max_iter, k, return_info, allow_failures,
+                                                  max_correspondence_distance)
 
-    def estimate_point_to_line_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False):
+    def estimate_point_to_line_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False,
+                                      max_correspondence_distance=None):
         """The same over pre-packed clouds (`items` as for estimate_packed; K hypotheses share one src and one dst range).
-        numpy arrays go through icp_batch_estimate_point_to_line; contiguous float64 CUDA tensors through
-        icp_batch_estimate_point_to_line_device, in place."""
+        numpy arrays go through icp_batch_estimate_point_to_line[_gated]; contiguous float64 CUDA tensors through
+        icp_batch_estimate_point_to_line[_gated]_device, in place."""
         self._need_2d("estimate_point_to_line_packed")
         if not 3 <= int(k) <= 16:
             raise ValueError(f"k must be in [3, 16], got {k!r}")
-        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k))
+        r = None
+        if max_correspondence_distance is not None:
+            r = float(max_correspondence_distance)
+            if not r >= 0.0:  # (also a NaN)
+                raise ValueError(
+                    f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), r)
 
     def line_counters(self):
         """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
         estimate_point_to_line*"""
         out = (C.c_uint64 * 4)()
         check(lib().icp_batch_line_counters(self._b, out), "icp_batch_line_counters")
+        return tuple(int(x) for x in out)
+
+    def line_gated_counters(self):
+        """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
+        estimate_point_to_line*(..., max_correspondence_distance=r)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_line_gated_counters(self._b, out), "icp_batch_line_gated_counters")
         return tuple(int(x) for x in out)
 
     # -- the quality of many poses in one call (icp_batch_evaluate*, include/icp_mi355x.h section 9) --

@@ -5,6 +5,8 @@
 // Section 15, the same call with the point-to-line residual of section 14: k_line_estimate_batch (p2line_batch.hip), one
 // workgroup per item in at most two launches; one by one: icp_create_device + icp_compute_target_line_normals +
 // icp_estimate_point_to_line_device.
+// Section 17, section 15 with a maximum correspondence distance: k_line_estimate_gated_batch, driven the same way; one by
+// one: icp_estimate_point_to_line_gated_device in the last step's place.
 // Sections 9 and 16, the quality of many poses: k_quality_batch (quality.hip) and, with the line residual,
 // k_line_quality_batch (quality_line.hip), one workgroup per item in one launch; one by one: the single calls.
 #include <cstring>
@@ -35,6 +37,9 @@ struct icp_batch {
   size_t cap_inner = 0;
   uint64_t ctr[4] = {0, 0, 0, 0};  // icp_batch_counters
   uint64_t lctr[4] = {0, 0, 0, 0};  // icp_batch_line_counters
+  uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (section 17)
+  size_t cap_inl = 0;
+  uint64_t lgctr[4] = {0, 0, 0, 0};  // icp_batch_line_gated_counters
   // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
   QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
   size_t cap_qitems = 0, cap_h_qitems = 0;
@@ -68,7 +73,7 @@ bool in_range(uint64_t first, uint64_t count, size_t points) { return first <= p
 // every argument, before anything touches the device
 int check_args(const icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
                const icp_batch_item *items, size_t count, size_t max_iter, const void *out, const int *status,
-               const uint32_t *inner_iters) {
+               bool per_iteration_words) {  // (inner_iters or inliers: count x max_iter words must be addressable)
   if (!b) return ICP_BAD_ARGUMENT;
   if (count == 0) return ICP_OK;
   if (!items || !out || !status || count > 0x7fffffffu) return ICP_BAD_ARGUMENT;  // (one workgroup per item)
@@ -76,7 +81,7 @@ int check_args(const icp_batch *b, const double *src, size_t src_points, const d
   if ((src_points > 0 && !src) || (dst_points > 0 && !dst) || src_points > SIZE_MAX / point_bytes ||
       dst_points > SIZE_MAX / point_bytes)
     return ICP_BAD_ARGUMENT;
-  if (inner_iters && max_iter > 0 && count > SIZE_MAX / sizeof(uint32_t) / max_iter) return ICP_BAD_ARGUMENT;
+  if (per_iteration_words && max_iter > 0 && count > SIZE_MAX / sizeof(uint32_t) / max_iter) return ICP_BAD_ARGUMENT;
   for (size_t i = 0; i < count; ++i) {
     const icp_batch_item &it = items[i];
     if (!in_range(it.src_first, it.n, src_points) || !in_range(it.dst_first, it.m, dst_points)) return ICP_BAD_ARGUMENT;
@@ -112,22 +117,37 @@ int with_pool_handle(icp_batch *b, const double *d_src, const double *d_dst, con
   return rc;
 }
 
-// icp_estimate_device on the item's handle; line_k > 0 (section 15): the handle's line normals from line_k neighbours,
-// then icp_estimate_point_to_line_device.
-int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter, int line_k,
-              icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner) {
+// The residual of an estimate call: line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line
+// residual, normals from line_k neighbours); gated on top (section 17): the pairs within max_dist, their counts per
+// outer iteration to `inliers` (count x max_iter, or null).
+struct Residual {
+  int line_k = 0;
+  bool gated = false;
+  double max_dist = 0.;
+  uint32_t *inliers = nullptr;
+};
+
+// icp_estimate_device on the item's handle; line_k > 0: the handle's line normals from line_k neighbours, then
+// icp_estimate_point_to_line_device, or (gated) icp_estimate_point_to_line_gated_device; inl: the item's inlier counts.
+int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter,
+              const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner, uint32_t *inl) {
   return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_NONE, ICP_EMPTY_DST, ICP_NAN_INPUT}, status,
                           [&](icp_handle *h, const double *s) {
-                            if (line_k == 0) return icp_estimate_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
-                            ICP_TRY_RC(icp_compute_target_line_normals(h, line_k));
+                            if (res.line_k == 0)
+                              return icp_estimate_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
+                            ICP_TRY_RC(icp_compute_target_line_normals(h, res.line_k));
+                            if (res.gated)
+                              return icp_estimate_point_to_line_gated_device(h, s, (size_t)it.n, &it.init, max_iter,
+                                                                             res.max_dist, out, d_idx, inner, inl);
                             return icp_estimate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
                           });
 }
 
-// line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line residual, normals from line_k neighbours)
 int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
-        size_t max_iter, int line_k, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
-  uint64_t *ctr = line_k > 0 ? b->lctr : b->ctr;
+        size_t max_iter, const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
+  const int line_k = res.line_k;
+  uint32_t *inliers = res.gated ? res.inliers : nullptr;
+  uint64_t *ctr = res.gated ? b->lgctr : (line_k > 0 ? b->lctr : b->ctr);
   // where each item's indices go, and which items a workgroup may serve, by workgroup size
   std::vector<uint64_t> idx_first(count);
   std::vector<size_t> cls[3], one_by_one;
@@ -149,6 +169,7 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
     HIP_TRY(reserve(b->d_items, b->cap_items, n_tiny));
     HIP_TRY(reserve_pinned(b->h_res, b->cap_res, count));
     if (inner_iters) HIP_TRY(reserve_pinned(b->h_inner, b->cap_inner, count * max_iter));
+    if (inliers) HIP_TRY(reserve_pinned(b->h_inl, b->cap_inl, count * max_iter));
     size_t k = 0;
     unsigned m_max[3] = {0, 0, 0};
     for (int c = 0; c < 3; ++c)
@@ -171,7 +192,12 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
     bool granted = true;
     for (int c = 0; c < 3; ++c) {
       if (cls[c].empty()) continue;
-      if (line_k > 0)
+      if (res.gated)  // (max_dist * max_dist in f64 on the host, as icp_estimate_point_to_line_gated_device forms it)
+        HIP_TRY(launch_line_estimate_gated_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
+                                                 (unsigned)cls[c].size(), (unsigned)max_iter, line_k,
+                                                 res.max_dist * res.max_dist, b->h_res, inner_iters ? b->h_inner : nullptr,
+                                                 d_idx, inliers ? b->h_inl : nullptr, b->stream, &granted));
+      else if (line_k > 0)
         HIP_TRY(launch_line_estimate_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first, (unsigned)cls[c].size(),
                                            (unsigned)max_iter, line_k, b->h_res, inner_iters ? b->h_inner : nullptr, d_idx,
                                            b->stream, &granted));
@@ -198,12 +224,14 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
         status[i] = ICP_OK;
         out[i] = r.pose;
         if (inner_iters) std::memcpy(inner_iters + i * max_iter, b->h_inner + i * max_iter, max_iter * sizeof(uint32_t));
+        if (inliers) std::memcpy(inliers + i * max_iter, b->h_inl + i * max_iter, max_iter * sizeof(uint32_t));
       }
   }
   one_by_one.insert(one_by_one.end(), handed_back.begin(), handed_back.end());
   for (size_t i : one_by_one) {
-    ICP_TRY_RC(serve_one(b, d_src, d_dst, items[i], max_iter, line_k, &out[i], &status[i],
-                         d_idx ? d_idx + idx_first[i] : nullptr, inner_iters ? inner_iters + i * max_iter : nullptr));
+    ICP_TRY_RC(serve_one(b, d_src, d_dst, items[i], max_iter, res, &out[i], &status[i],
+                         d_idx ? d_idx + idx_first[i] : nullptr, inner_iters ? inner_iters + i * max_iter : nullptr,
+                         inliers ? inliers + i * max_iter : nullptr));
     ++ctr[1];
   }
   return ICP_OK;
@@ -253,6 +281,7 @@ extern "C" void icp_batch_destroy(icp_batch *b) {
     if (b->h_items) (void)hipHostFree(b->h_items);
     if (b->h_res) (void)hipHostFree(b->h_res);
     if (b->h_inner) (void)hipHostFree(b->h_inner);
+    if (b->h_inl) (void)hipHostFree(b->h_inl);
     (void)hipFree(b->d_qitems);
     if (b->h_qitems) (void)hipHostFree(b->h_qitems);
     if (b->h_qres) (void)hipHostFree(b->h_qres);
@@ -268,12 +297,13 @@ namespace {
 bool line_args_ok(const icp_batch *b, int k) { return b && b->dim == 2 && k >= 3 && k <= 16; }
 
 int estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst, size_t dst_points,
-                    const icp_batch_item *items, size_t count, size_t max_iter, int line_k, icp_pose *out, int *status,
-                    uint32_t *d_last_idx, uint32_t *inner_iters) {
-  ICP_TRY_RC(check_args(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, out, status, inner_iters));
+                    const icp_batch_item *items, size_t count, size_t max_iter, const Residual &res, icp_pose *out,
+                    int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
+  ICP_TRY_RC(check_args(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, out, status,
+                        inner_iters || res.inliers));
   if (count == 0) return ICP_OK;
   ICP_TRY_RC(ensure_device(b));
-  return run(b, d_src, d_dst, items, count, max_iter, line_k, out, status, d_last_idx, inner_iters);
+  return run(b, d_src, d_dst, items, count, max_iter, res, out, status, d_last_idx, inner_iters);
 }
 
 // the host entries' clouds, staged through the batch's buffers: *d_src / *d_dst are what run, run_quality
@@ -297,9 +327,10 @@ int stage_clouds(icp_batch *b, const double *src, size_t src_points, const doubl
 
 // the entries that take host clouds: staged, the last indices read back
 int estimate_host(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
-                  const icp_batch_item *items, size_t count, size_t max_iter, int line_k, icp_pose *out, int *status,
-                  uint32_t *last_idx, uint32_t *inner_iters) {
-  ICP_TRY_RC(check_args(b, src, src_points, dst, dst_points, items, count, max_iter, out, status, inner_iters));
+                  const icp_batch_item *items, size_t count, size_t max_iter, const Residual &res, icp_pose *out,
+                  int *status, uint32_t *last_idx, uint32_t *inner_iters) {
+  ICP_TRY_RC(check_args(b, src, src_points, dst, dst_points, items, count, max_iter, out, status,
+                        inner_iters || res.inliers));
   if (count == 0) return ICP_OK;
   ICP_TRY_RC(ensure_device(b));
   const double *d_src, *d_dst;
@@ -309,7 +340,7 @@ int estimate_host(icp_batch *b, const double *src, size_t src_points, const doub
   // (as icp_estimate: no outer iteration, no correspondences -- last_idx is left as it was)
   const bool want_idx = last_idx && total_n > 0 && max_iter > 0;
   if (want_idx) HIP_TRY(reserve(b->d_idx, b->cap_idx, total_n));
-  const int rc = run(b, d_src, d_dst, items, count, max_iter, line_k, out, status, want_idx ? b->d_idx : nullptr,
+  const int rc = run(b, d_src, d_dst, items, count, max_iter, res, out, status, want_idx ? b->d_idx : nullptr,
                      inner_iters);
   if (rc != ICP_OK) return rc;
   if (want_idx) {
@@ -324,14 +355,15 @@ int estimate_host(icp_batch *b, const double *src, size_t src_points, const doub
 extern "C" int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
                                          size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
                                          icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, 0, out, status, d_last_idx,
-                         inner_iters);
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, Residual{}, out, status,
+                         d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
                                   const icp_batch_item *items, size_t count, size_t max_iter, icp_pose *out, int *status,
                                   uint32_t *last_idx, uint32_t *inner_iters) {
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, 0, out, status, last_idx, inner_iters);
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{}, out, status, last_idx,
+                       inner_iters);
 }
 
 // ---- section 15: the same two entries with the point-to-line residual (2-D batches, 3 <= k <= 16) ----
@@ -340,8 +372,8 @@ extern "C" int icp_batch_estimate_point_to_line_device(icp_batch *b, const doubl
                                                        size_t count, int k, size_t max_iter, icp_pose *out, int *status,
                                                        uint32_t *d_last_idx, uint32_t *inner_iters) {
   if (!line_args_ok(b, k)) return ICP_BAD_ARGUMENT;
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, k, out, status, d_last_idx,
-                         inner_iters);
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, Residual{k, false, 0., nullptr},
+                         out, status, d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
@@ -349,7 +381,35 @@ extern "C" int icp_batch_estimate_point_to_line(icp_batch *b, const double *src,
                                                 size_t max_iter, icp_pose *out, int *status, uint32_t *last_idx,
                                                 uint32_t *inner_iters) {
   if (!line_args_ok(b, k)) return ICP_BAD_ARGUMENT;
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, k, out, status, last_idx, inner_iters);
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k, false, 0., nullptr}, out,
+                       status, last_idx, inner_iters);
+}
+
+// ---- section 17: section 15's entries with a maximum correspondence distance (max_dist >= 0, or +inf) ----
+extern "C" int icp_batch_estimate_point_to_line_gated_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                             const double *d_dst, size_t dst_points,
+                                                             const icp_batch_item *items, size_t count, int k,
+                                                             size_t max_iter, double max_dist, icp_pose *out, int *status,
+                                                             uint32_t *d_last_idx, uint32_t *inner_iters,
+                                                             uint32_t *inliers) {
+  if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                         Residual{k, true, max_dist, inliers}, out, status, d_last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_estimate_point_to_line_gated(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                                      size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                                      size_t max_iter, double max_dist, icp_pose *out, int *status,
+                                                      uint32_t *last_idx, uint32_t *inner_iters, uint32_t *inliers) {
+  if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k, true, max_dist, inliers},
+                       out, status, last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->lgctr[q];
+  return ICP_OK;
 }
 
 extern "C" int icp_batch_line_counters(icp_batch *b, uint64_t out[4]) {
@@ -373,7 +433,7 @@ int check_quality_args(const icp_batch *b, const double *src, size_t src_points,
                        const icp_batch_item *items, size_t count, double max_dist, const icp_quality *out,
                        const int *status) {
   if (!b || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
-  return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, nullptr);
+  return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, false);
 }
 
 bool quality_fits(const icp_batch_item &it) {
@@ -518,7 +578,7 @@ int check_line_quality_args(const icp_batch *b, const double *src, size_t src_po
                             const icp_batch_item *items, size_t count, int k, double max_dist, const icp_line_quality *out,
                             const int *status) {
   if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
-  return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, nullptr);
+  return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, false);
 }
 
 }  // namespace

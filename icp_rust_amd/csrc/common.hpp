@@ -549,6 +549,12 @@ inline unsigned line_batch_threads(size_t n) { return n <= 512 ? 512u : 1024u; }
 hipError_t launch_line_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
                                       TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
+// EXTENSION: the same with a maximum correspondence distance (k_line_estimate_gated_batch): r2 = max_dist^2, formed in
+// f64 by the caller; inliers: count x max_iter kept counts (pinned host memory, or null), laid out like `inner`.
+hipError_t launch_line_estimate_gated_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                            const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                            double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
+                                            uint32_t *inliers, hipStream_t stream, bool *granted);
 // A record of the fold tree of section 9 (fold_device.hpp): SUMS sums that are doubles, the inlier count and whether some
 // residual was NaN.
 template <int SUMS>

@@ -20,6 +20,10 @@
 //              (tiny_inner_decide); the composed pose and the fixed-point test (tiny_outer_tail)
 // Hand-back reasons: a box that is not finite; a NaN target coordinate; a rotation update outside the restated range of
 // sin / cos.  A NaN residual is the item's ICP_NAN_INPUT.
+// Section 17, k_line_estimate_gated_batch: the same body (line_estimate_item) with the gate of
+// icp_estimate_point_to_line_gated between the search and the inner loop -- the pairs with d2 <= r^2 (p2line.hip:
+// k_lngate_stage's expressions), compacted in thread order, and p2pl_loop_on_pairs on the `kept` of them in the tree of
+// reduce_geometry(kept).
 #include "common.hpp"
 #include "gn_device.hpp"
 #include "p2line_device.hpp"
@@ -77,12 +81,41 @@ static_assert(line_batch_plan(512, kLineBatchMaxM).list_threads == 320 && line_b
                   line_batch_plan(1024, kLineBatchMaxM).lds_bytes <= kTinyLdsGrant,
               "m = 2048");
 
-template <unsigned B>
-__global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restrict__ src_all,
-                                                           const double *__restrict__ dst_all,
-                                                           const TinyBatchItem *__restrict__ items, unsigned max_iter,
-                                                           int kk, unsigned L, unsigned shared_bytes, TinyResult *res_all,
-                                                           uint32_t *inner_all, uint32_t *idx_all) {
+// ---- the gate's words (section 17) ----
+// Behind the estimator's three sort buffers in the shared region, which the normals' lists have left by then: the moved
+// point (x | y, f64) and the sorted position of its match for each kept pair, in pair order, and the 16 wave counts.
+constexpr size_t line_gate_bytes(unsigned threads) {
+  return (size_t)threads * (2 * sizeof(double) + sizeof(uint32_t)) + 16 * sizeof(uint32_t);
+}
+constexpr LinePlan line_gated_batch_plan(unsigned threads, unsigned m_max) {
+  LinePlan plan = line_batch_plan(threads, m_max);  // (the same rounds of the normals: the lists decide them)
+  const size_t need = (size_t)3 * threads * 8 + line_gate_bytes(threads);
+  if (plan.shared_bytes < need) {
+    plan.lds_bytes += need - plan.shared_bytes;
+    plan.shared_bytes = (unsigned)need;
+  }
+  return plan;
+}
+static_assert(line_gated_batch_plan(512, 1).list_threads == 64 &&
+                  line_gated_batch_plan(512, 1).shared_bytes == 3 * 512 * 8 + line_gate_bytes(512) &&
+                  line_gated_batch_plan(1024, 1).shared_bytes == 3 * 1024 * 8 + line_gate_bytes(1024),
+              "m = 1: the sort buffers and the gate's words");
+static_assert(line_gated_batch_plan(1024, 668).list_threads == 640 && line_gated_batch_plan(1024, 668).lds_bytes == 158784,
+              "m = 668: the gate's words lie where the lists were");
+static_assert(line_gated_batch_plan(512, kLineBatchMaxM).list_threads == 320 &&
+                  line_gated_batch_plan(1024, kLineBatchMaxM).list_threads == 320 &&
+                  line_gated_batch_plan(512, kLineBatchMaxM).lds_bytes == 161856 &&
+                  line_gated_batch_plan(1024, kLineBatchMaxM).lds_bytes == 161856 &&
+                  line_fixed_bytes(kLineBatchMaxM) + 3 * 1024 * 8 + line_gate_bytes(1024) <= kTinyLdsGrant,
+              "m = 2048: nothing on top of the ungated plan");
+
+// One item of a batch, by the workgroup's B threads: what both kernels below run.  GATED: the gate between the search and
+// the inner loop; r2, inl_all: the squared bound and the inlier counts (count x max_iter, or null).
+template <unsigned B, bool GATED>
+__device__ __forceinline__ void line_estimate_item(const double *__restrict__ src_all, const double *__restrict__ dst_all,
+                                                   const TinyBatchItem *__restrict__ items, unsigned max_iter, int kk,
+                                                   unsigned L, unsigned shared_bytes, TinyResult *res_all,
+                                                   uint32_t *inner_all, uint32_t *idx_all, double r2, uint32_t *inl_all) {
   static_assert(B == 512 || B == 1024, "one or two blocks of the 512-thread fold tree, a power of two for the sort");
   extern __shared__ unsigned char lds_raw[];
   const TinyBatchItem &item = items[blockIdx.x];  // (read in place: a copy of the pose would live in scratch)
@@ -147,23 +180,21 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
     px = src[(size_t)tid * 2];
     py = src[(size_t)tid * 2 + 1];
   }
-  const int blocks = n > 512u ? 2 : 1;  // reduce_geometry(n) for n <= 1024: 512-thread blocks
+  // the pairs the inner loop sees: all n, thread t its own; gated: the kept ones, thread t the t-th of them
+  unsigned cnt = n;
+  bool hasp = has;
+  int blocks = n > 512u ? 2 : 1;  // reduce_geometry(cnt) for cnt <= 1024: 512-thread blocks
+  // the gate's words, behind the sort buffers (line_gated_batch_plan)
+  double *gqx = reinterpret_cast<double *>(shared + (size_t)3 * B * 8), *gqy = gqx + B;
+  uint32_t *gnb = reinterpret_cast<uint32_t *>(gqy + B), *gcnt = gnb + B;
+  uint32_t *inl_out = GATED && inl_all ? inl_all + (size_t)item.slot * max_iter : nullptr;
   unsigned bi = 0xffffffffu;
   for (unsigned it = 0; it < max_iter; ++it) {
     const Pose T = C->T;
     // ---- transform + exact nearest neighbour, the pair of k_line_gather ----
     PlanePair pr;
     pr.ax = pr.ay = pr.qx = pr.qy = pr.dz = pr.nx = pr.ny = pr.nz = 0.;
-    if (has) {
-      const double qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24
-      const double qy = (T.r10 * px + T.r11 * py) + T.ty;
-      unsigned nb, nbo;  // sorted position / original index of the nearest target
-      tiny_nearest<2>(tg, qx, qy, 0., cx, cy, cz, scale, bi, &nb, &nbo);
-      bi = nb;
-      if (nb == 0xffffffffu) {  // no finite distance (NaN query): index 0, as a scan from 0 would
-        nb = C->pos0;
-        nbo = 0;
-      }
+    auto pair_of = [&](double qx, double qy, unsigned nb) {
       const double2 nq = nrm[nb];
       pr.ax = qx;
       pr.ay = qy;
@@ -171,36 +202,84 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
       pr.qy = ty[nb];
       pr.nx = nq.x;
       pr.ny = nq.y;
+    };
+    double qx = 0., qy = 0.;
+    unsigned nb = 0;  // sorted position of the nearest target
+    bool in = false;  // (gated) the pair passes the gate
+    if (has) {
+      qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24
+      qy = (T.r10 * px + T.r11 * py) + T.ty;
+      unsigned nbo;  // original index of the nearest target
+      tiny_nearest<2>(tg, qx, qy, 0., cx, cy, cz, scale, bi, &nb, &nbo);
+      bi = nb;
+      if (nb == 0xffffffffu) {  // no finite distance (NaN query): index 0, as a scan from 0 would
+        nb = C->pos0;
+        nbo = 0;
+      }
+      if constexpr (GATED) {  // k_lngate_stage's expressions
+        const double ex = qx - tx[nb], ey = qy - ty[nb];
+        const double d2 = ex * ex + ey * ey;
+        in = d2 <= r2;  // (false for a NaN d2)
+      } else {
+        pair_of(qx, qy, nb);
+      }
       if (idx_out && it + 1 == max_iter) idx_out[tid] = nbo;
     }
-    // ---- p2pl_loop_on_pairs (api_ext.hip) on the n pairs ----
+    if constexpr (GATED) {
+      // ---- the gate: the kept pairs in thread order (stable), pair t to thread t ----
+      // rank = kept lanes before this one in its wave + the counts of the waves before it; the kept lanes of a wave
+      // write consecutive words
+      const unsigned long long bal = __ballot(in);
+      unsigned rank = (unsigned)__popcll(bal & ((1ull << (tid & 63)) - 1ull));
+      if ((tid & 63) == 0) gcnt[wave] = (unsigned)__popcll(bal);
+      __syncthreads();
+      unsigned kept = 0;
+#pragma unroll
+      for (int w = 0; w < (int)(B / 64); ++w) {
+        const unsigned c = gcnt[w];
+        rank += w < wave ? c : 0u;
+        kept += c;
+      }
+      if (in) {
+        gqx[rank] = qx;
+        gqy[rank] = qy;
+        gnb[rank] = nb;
+      }
+      cnt = (unsigned)__builtin_amdgcn_readfirstlane((int)kept);  // (the same in every thread)
+      hasp = tid < cnt;
+      blocks = cnt > 512u ? 2 : 1;
+    }
+    // ---- p2pl_loop_on_pairs (api_ext.hip) on the cnt pairs ----
     if (tid == 0) {
       C->Ti = transform_identity();
-      C->done = n < 2u ? 1 : 0;  // fewer than two pairs: the identity, no update
+      C->done = cnt < 2u ? 1 : 0;  // fewer than two pairs: the identity, no update
       C->applied = 0;
       C->prev_error = 1.7976931348623157e308;  // DBL_MAX
     }
     __syncthreads();
+    if constexpr (GATED) {
+      if (hasp) pair_of(gqx[tid], gqy[tid], gnb[tid]);
+    }
     for (int k = 0; k < ICP_INNER_MAX_ITER && !C->done; ++k) {
       const Pose Ti = C->Ti;
       double r = 0.;
-      if (has) {
+      if (hasp) {
         r = plane_residual(pr, Ti);
         if (r != r) C->nan = 1;
       }
       // exact median and MAD of r (launch_stddevs on ((r, 0), (0, 0)) under the identity: dimension 0's statistics of
       // ((1 r + 0 0) + 0) - 0 = r, which plane_residual's trailing + nz dz = + 0.0 has already rid of a -0.0)
-      unsigned long long key[1] = {has ? f2k(r) : ~0ull};
+      unsigned long long key[1] = {hasp ? f2k(r) : ~0ull};
       double med[1], sig[1];
       tiny_bitonic_sort<B, 1>(key, sbuf);
-      tiny_sorted_median_sigma<B, 1>(key, sbuf[2], n, C->mad, med, sig);  // (a third buffer: no barrier behind the sort)
+      tiny_sorted_median_sigma<B, 1>(key, sbuf[2], cnt, C->mad, med, sig);  // (a third buffer: no barrier behind the sort)
       const double sigma = sig[0];
       // k_p2pl_accumulate's terms, one pair per thread, folded as block_reduce_store folds a 512-thread block
       {
         double acc[kLineSums];
 #pragma unroll
         for (int q = 0; q < kLineSums; ++q) acc[q] = 0.;
-        if (has) {
+        if (hasp) {
           const double gw = 1. / sigma;
           const double e = r * r;
           if (sigma != 0.) {  // src/lib.rs:243-245
@@ -241,7 +320,17 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
       if (tid == 0) tiny_inner_decide(C, tot);
       __syncthreads();
     }
-    if (tid == 0) tiny_outer_tail(C, it, max_iter, inner_out);
+    if (tid == 0) {
+      tiny_outer_tail(C, it, max_iter, inner_out);
+      if constexpr (GATED) {
+        // the iterations a fixed point skips repeat this one's search and gate: this one's count is theirs
+        if (inl_out) {
+          inl_out[it] = cnt;
+          if (C->fixed && it + 2 < max_iter)
+            for (unsigned k = it + 1; k + 1 < max_iter; ++k) inl_out[k] = cnt;
+        }
+      }
+    }
     __syncthreads();
     if (C->nan | C->bail) break;
     if (C->fixed && it + 2 < max_iter) it = max_iter - 2;  // (uniform: the flag is the workgroup's)
@@ -252,6 +341,28 @@ __global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restr
     res->sorted = C->evals;
     res->status = C->nan ? 3 : (C->bail ? -1 : 0);
   }
+}
+
+template <unsigned B>
+__global__ __launch_bounds__(B) void k_line_estimate_batch(const double *__restrict__ src_all,
+                                                           const double *__restrict__ dst_all,
+                                                           const TinyBatchItem *__restrict__ items, unsigned max_iter,
+                                                           int kk, unsigned L, unsigned shared_bytes, TinyResult *res_all,
+                                                           uint32_t *inner_all, uint32_t *idx_all) {
+  line_estimate_item<B, false>(src_all, dst_all, items, max_iter, kk, L, shared_bytes, res_all, inner_all, idx_all, 0.,
+                               nullptr);
+}
+
+// section 17: r2 = max_dist^2; inl_all: count x max_iter inlier counts, or null
+template <unsigned B>
+__global__ __launch_bounds__(B) void k_line_estimate_gated_batch(const double *__restrict__ src_all,
+                                                                 const double *__restrict__ dst_all,
+                                                                 const TinyBatchItem *__restrict__ items, unsigned max_iter,
+                                                                 int kk, unsigned L, unsigned shared_bytes, double r2,
+                                                                 TinyResult *res_all, uint32_t *inner_all,
+                                                                 uint32_t *idx_all, uint32_t *inl_all) {
+  line_estimate_item<B, true>(src_all, dst_all, items, max_iter, kk, L, shared_bytes, res_all, inner_all, idx_all, r2,
+                              inl_all);
 }
 
 hipError_t launch_line_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
@@ -270,6 +381,25 @@ hipError_t launch_line_estimate_batch(unsigned threads, unsigned m_max, const do
   else
     hipLaunchKernelGGL((k_line_estimate_batch<1024>), dim3(count), dim3(1024), plan.lds_bytes, stream, d_src, d_dst, d_items,
                        max_iter, k, plan.list_threads, plan.shared_bytes, res, inner, d_idx);
+  return hipGetLastError();
+}
+
+hipError_t launch_line_estimate_gated_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                            const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                            double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
+                                            uint32_t *inliers, hipStream_t stream, bool *granted) {
+  static TinyLdsGrant grant;  // (these kernels' own: refused, nothing launches)
+  *granted = grant.ask({reinterpret_cast<const void *>(&k_line_estimate_gated_batch<512>),
+                        reinterpret_cast<const void *>(&k_line_estimate_gated_batch<1024>)},
+                       kTinyLdsGrant);
+  if (!*granted || count == 0) return hipSuccess;
+  const LinePlan plan = line_gated_batch_plan(threads, m_max);
+  if (threads == 512u)
+    hipLaunchKernelGGL((k_line_estimate_gated_batch<512>), dim3(count), dim3(512), plan.lds_bytes, stream, d_src, d_dst,
+                       d_items, max_iter, k, plan.list_threads, plan.shared_bytes, r2, res, inner, d_idx, inliers);
+  else
+    hipLaunchKernelGGL((k_line_estimate_gated_batch<1024>), dim3(count), dim3(1024), plan.lds_bytes, stream, d_src, d_dst,
+                       d_items, max_iter, k, plan.list_threads, plan.shared_bytes, r2, res, inner, d_idx, inliers);
   return hipGetLastError();
 }
 

@@ -67,7 +67,8 @@ extern "C" {
  * section 13 (icp_plane_quality, icp_evaluate_point_to_plane*); so was section 14 (icp_*_target_line_normals,
  * icp_estimate_point_to_line*); so was section 15 (icp_batch_estimate_point_to_line*; icp_batch_line_counters in
  * icp_mi355x_debug.h); so was section 16 (icp_line_quality, icp_evaluate_point_to_line*,
- * icp_batch_evaluate_point_to_line*; icp_batch_line_quality_counters in icp_mi355x_debug.h) */
+ * icp_batch_evaluate_point_to_line*; icp_batch_line_quality_counters in icp_mi355x_debug.h); so was section 17
+ * (icp_batch_estimate_point_to_line_gated*; icp_batch_line_gated_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -953,6 +954,33 @@ int icp_batch_evaluate_point_to_line(icp_batch *b, const double *src, size_t src
 int icp_batch_evaluate_point_to_line_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
                                             size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                             double max_dist, icp_line_quality *out, int *status);
+
+/* ================================================================================
+ * 17. EXTENSION (not in the reference): section 15's call with a maximum correspondence distance
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Loop-closure candidates and hypotheses far
+ * from the truth overlap only partly: they need section 14's gate.  Item i's out[i], status[i], indices, inner counts
+ * and inlier counts are what icp_create(2, dst + 2 dst_first, m) + icp_compute_target_line_normals(k) +
+ * icp_estimate_point_to_line_gated(src + 2 src_first, n, &init, max_iter, max_dist) return on a fresh handle, bit for
+ * bit: per outer iteration the inner loop sees only the pairs with d2 = ex ex + ey ey <= max_dist * max_dist (no FMA;
+ * max_dist * max_dist in f64; a NaN d2 is never kept, so a NaN source point is gated out), in the caller's order.
+ * Every item within section 15's limits runs as ONE workgroup (one launch per workgroup size, at most two); the other
+ * items, and those a workgroup hands back, go through exactly those three entries one after another.  An item is never
+ * approximated.  DESIGN.md section 9l.
+ * Arguments, ranges, last_idx (the search result of ALL n points in the last iteration), inner_iters, statuses and the
+ * return value are section 15's.  inliers: count * max_iter words, nullable, laid out like inner_iters: the number of
+ * kept pairs of each outer iteration.  In addition ICP_BAD_ARGUMENT for max_dist NaN or negative (+inf is allowed: every
+ * pair with a d2 that is not NaN is kept) -- checked, like every argument, before the device is touched.  count == 0 is a
+ * successful no-op. */
+int icp_batch_estimate_point_to_line_gated(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                           size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                           size_t max_iter, double max_dist, icp_pose *out, int *status,
+                                           uint32_t *last_idx, uint32_t *inner_iters, uint32_t *inliers);
+int icp_batch_estimate_point_to_line_gated_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                  const double *d_dst, size_t dst_points, const icp_batch_item *items,
+                                                  size_t count, int k, size_t max_iter, double max_dist, icp_pose *out,
+                                                  int *status, uint32_t *d_last_idx, uint32_t *inner_iters,
+                                                  uint32_t *inliers);
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,11 @@ int icp_batch_line_counters(icp_batch *b, uint64_t out[4]);
  * icp_evaluate_point_to_line_device (outside the limits, handed back by their workgroup, or no LDS grant), out[2] batch
  * launches, out[3] launches not made because the runtime refused the kernel its LDS. */
 int icp_batch_line_quality_counters(icp_batch *b, uint64_t out[4]);
+/* ... and of icp_batch_estimate_point_to_line_gated[_device] (icp_mi355x.h section 17): out[0] items served inside a
+ * batch launch, out[1] items served one by one through icp_create_device + icp_compute_target_line_normals +
+ * icp_estimate_point_to_line_gated_device (outside the limits, handed back by their workgroup, or no LDS grant), out[2]
+ * batch launches, out[3] launches not made because the runtime refused the kernels their LDS. */
+int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]);
 
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
