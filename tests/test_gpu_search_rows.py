@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import icp_rust_amd as I
+from blind_clouds import _geometry
 from parity_util import apply_pose
 
 pytestmark = pytest.mark.gpu
@@ -28,18 +29,6 @@ pytestmark = pytest.mark.gpu
 N_SRC = 66_003  # > 65 536 (the shared walk), and not a multiple of 64: the last wave has 45 lanes past the end
 T0 = (0.02, -0.015, 0.004)
 HUGE = 1e20     # a finite query beyond the f32 geometry: its box is the whole grid (`wide`)
-
-
-def _geometry(dst):
-    """(origin, cell sizes, cells per axis) of the target grid (nn_grid.hip: build_grid, below its caps)"""
-    lo, hi = dst.min(0), dst.max(0)
-    ext = hi - lo
-    live = ext > 1e-9 * ext.max()
-    hh = (2.0 * np.prod(ext[live]) / len(dst)) ** (1.0 / live.sum())
-    h = np.full(dst.shape[1], hh)
-    h[0] = hh / 4.0
-    n = np.where(live, np.floor(ext / h) + 1, 1).astype(np.int64)
-    return lo, h, n
 
 
 def _rows(q, r, geo, d):
