@@ -251,6 +251,11 @@ SIGNATURES = {
     "icp_batch_evaluate_point_to_line_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp,
                                                           _vp]),
     "icp_batch_line_quality_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_batch_estimate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, _vp, _vp, _vp, _vp]),
+    "icp_batch_estimate_point_to_plane_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, _sz, _vp, _vp, _vp,
+                                                           _vp]),
+    "icp_batch_plane_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_debug_plane_batch_plan": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

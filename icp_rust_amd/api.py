@@ -1156,11 +1156,13 @@ class IcpBatch:
         through icp_batch_estimate_device, in place."""
         return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, None)
 
-    def _estimate_packed(self, src, dst, items, max_iter, return_info, allow_failures, line_k, max_dist=None):
-        """estimate_packed (line_k None) and estimate_point_to_line_packed (line_k = the normals' neighbours; max_dist:
-        the gated entries, which also fill the inlier counts)"""
+    def _estimate_packed(self, src, dst, items, max_iter, return_info, allow_failures, line_k, max_dist=None,
+                         normals_entry="icp_batch_estimate_point_to_line"):
+        """estimate_packed (line_k None), estimate_point_to_line_packed (line_k = the normals' neighbours; max_dist:
+        the gated entries, which also fill the inlier counts) and estimate_point_to_plane_packed (normals_entry: its
+        entry, which takes the same arguments)"""
         count = len(items)
-        name = "icp_batch_estimate" if line_k is None else "icp_batch_estimate_point_to_line"
+        name = "icp_batch_estimate" if line_k is None else normals_entry
         name = what = name + ("" if max_dist is None else "_gated")
         kargs = [] if line_k is None else [int(line_k)]
         gargs = [] if max_dist is None else [float(max_dist)]
@@ -1263,6 +1265,37 @@ class IcpBatch:
                 raise ValueError(
                     f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
         return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), r)
+
+    # -- EXTENSION: the same with the point-to-plane residual for 3-D items (icp_batch_estimate_point_to_plane*,
+    # section 18) --
+    def _need_3d(self, what):
+        if self.DIM != 3:
+            raise ValueError(f"{what} needs a 3-D batch (IcpBatch(3)): the plane residual is for 3-D clouds")
+
+    def estimate_point_to_plane(self, srcs, dsts, inits, max_iter, k=10, return_info=False, allow_failures=False):
+        """estimate() with the point-to-plane residual: item i is what Icp3d(dsts[i]) returns after compute_normals(k)
+        from estimate_point_to_plane(srcs[i], inits[i], max_iter), bit for bit; items of up to 1024 source and 2048
+        target points run as one workgroup each (normals included), the others one by one."""
+        self._need_3d("estimate_point_to_plane")
+        src, dst, items = self._pack_items(srcs, dsts, inits)
+        return self.estimate_point_to_plane_packed(src, dst, items, max_iter, k, return_info, allow_failures)
+
+    def estimate_point_to_plane_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False):
+        """The same over pre-packed clouds (`items` as for estimate_packed; K hypotheses share one src and one dst range).
+        numpy arrays go through icp_batch_estimate_point_to_plane; contiguous float64 CUDA tensors through
+        icp_batch_estimate_point_to_plane_device, in place."""
+        self._need_3d("estimate_point_to_plane_packed")
+        if not 3 <= int(k) <= 16:
+            raise ValueError(f"k must be in [3, 16], got {k!r}")
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), None,
+                                     "icp_batch_estimate_point_to_plane")
+
+    def plane_counters(self):
+        """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
+        estimate_point_to_plane*"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_plane_counters(self._b, out), "icp_batch_plane_counters")
+        return tuple(int(x) for x in out)
 
     def line_counters(self):
         """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of

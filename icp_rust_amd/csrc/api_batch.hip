@@ -9,6 +9,9 @@
 // one: icp_estimate_point_to_line_gated_device in the last step's place.
 // Sections 9 and 16, the quality of many poses: k_quality_batch (quality.hip) and, with the line residual,
 // k_line_quality_batch (quality_line.hip), one workgroup per item in one launch; one by one: the single calls.
+// Section 18, section 8's call with the point-to-plane residual for 3-D batches: k_plane_estimate_batch
+// (p2plane_batch.hip), one workgroup per item in at most two launches; one by one: icp_create_device +
+// icp_compute_target_normals + icp_estimate_point_to_plane_device.
 #include <cstring>
 #include <initializer_list>
 #include <new>
@@ -40,6 +43,7 @@ struct icp_batch {
   uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (section 17)
   size_t cap_inl = 0;
   uint64_t lgctr[4] = {0, 0, 0, 0};  // icp_batch_line_gated_counters
+  uint64_t pctr[4] = {0, 0, 0, 0};   // icp_batch_plane_counters
   // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
   QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
   size_t cap_qitems = 0, cap_h_qitems = 0;
@@ -97,6 +101,10 @@ bool line_fits(const icp_batch_item &it, size_t max_iter) {
   return it.n >= 1 && it.n <= kLineBatchMaxN && it.m >= 1 && it.m <= kLineBatchMaxM && max_iter >= 1 &&
          max_iter <= kLineBatchMaxIter;
 }
+bool plane_fits(const icp_batch_item &it, size_t max_iter) {
+  return it.n >= 1 && it.n <= kPlaneBatchMaxN && it.m >= 1 && it.m <= kPlaneBatchMaxM && max_iter >= 1 &&
+         max_iter <= kPlaneBatchMaxIter;
+}
 
 // An item the way single calls serve it: a handle of the pool on the item's targets, serve(h, the item's sources) on it.
 // The outcomes in `per_item` land in *status; anything else (HIP, memory, device) is the call's failure.
@@ -119,18 +127,29 @@ int with_pool_handle(icp_batch *b, const double *d_src, const double *d_dst, con
 
 // The residual of an estimate call: line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line
 // residual, normals from line_k neighbours); gated on top (section 17): the pairs within max_dist, their counts per
-// outer iteration to `inliers` (count x max_iter, or null).
+// outer iteration to `inliers` (count x max_iter, or null); plane_k > 0 (and line_k == 0): section 18 (the plane residual
+// of a 3-D batch, normals from plane_k neighbours).
 struct Residual {
   int line_k = 0;
   bool gated = false;
   double max_dist = 0.;
   uint32_t *inliers = nullptr;
+  int plane_k = 0;
 };
 
 // icp_estimate_device on the item's handle; line_k > 0: the handle's line normals from line_k neighbours, then
-// icp_estimate_point_to_line_device, or (gated) icp_estimate_point_to_line_gated_device; inl: the item's inlier counts.
+// icp_estimate_point_to_line_device, or (gated) icp_estimate_point_to_line_gated_device; inl: the item's inlier counts;
+// plane_k > 0: the handle's plane normals from plane_k neighbours, then icp_estimate_point_to_plane_device.  The first
+// failing step gives the item's status (ICP_BAD_ARGUMENT: targets the normals refuse, as section 16's one-by-one server).
 int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter,
               const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner, uint32_t *inl) {
+  if (res.plane_k > 0)
+    return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_EMPTY_DST, ICP_NAN_INPUT, ICP_BAD_ARGUMENT}, status,
+                            [&](icp_handle *h, const double *s) {
+                              ICP_TRY_RC(icp_compute_target_normals(h, res.plane_k));
+                              return icp_estimate_point_to_plane_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx,
+                                                                        inner);
+                            });
   return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_NONE, ICP_EMPTY_DST, ICP_NAN_INPUT}, status,
                           [&](icp_handle *h, const double *s) {
                             if (res.line_k == 0)
@@ -145,9 +164,9 @@ int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_
 
 int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
         size_t max_iter, const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
-  const int line_k = res.line_k;
+  const int line_k = res.line_k, plane_k = res.plane_k;
   uint32_t *inliers = res.gated ? res.inliers : nullptr;
-  uint64_t *ctr = res.gated ? b->lgctr : (line_k > 0 ? b->lctr : b->ctr);
+  uint64_t *ctr = plane_k > 0 ? b->pctr : (res.gated ? b->lgctr : (line_k > 0 ? b->lctr : b->ctr));
   // where each item's indices go, and which items a workgroup may serve, by workgroup size
   std::vector<uint64_t> idx_first(count);
   std::vector<size_t> cls[3], one_by_one;
@@ -155,8 +174,11 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
   for (size_t i = 0; i < count; ++i) {
     idx_first[i] = at;
     at += items[i].n;
-    if (line_k > 0 ? line_fits(items[i], max_iter) : tiny_fits(items[i], max_iter)) {
-      const unsigned t = line_k > 0 ? line_batch_threads(items[i].n) : tiny_threads(items[i].n);
+    const bool fits = plane_k > 0 ? plane_fits(items[i], max_iter)
+                                  : (line_k > 0 ? line_fits(items[i], max_iter) : tiny_fits(items[i], max_iter));
+    if (fits) {
+      const unsigned t = plane_k > 0 ? plane_batch_threads(items[i].n)
+                                     : (line_k > 0 ? line_batch_threads(items[i].n) : tiny_threads(items[i].n));
       cls[t == 512u ? 0 : (t == 768u ? 1 : 2)].push_back(i);
     } else {
       one_by_one.push_back(i);
@@ -192,7 +214,11 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
     bool granted = true;
     for (int c = 0; c < 3; ++c) {
       if (cls[c].empty()) continue;
-      if (res.gated)  // (max_dist * max_dist in f64 on the host, as icp_estimate_point_to_line_gated_device forms it)
+      if (plane_k > 0)
+        HIP_TRY(launch_plane_estimate_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
+                                            (unsigned)cls[c].size(), (unsigned)max_iter, plane_k, b->h_res,
+                                            inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
+      else if (res.gated)  // (max_dist * max_dist in f64 on the host, as icp_estimate_point_to_line_gated_device forms it)
         HIP_TRY(launch_line_estimate_gated_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
                                                  (unsigned)cls[c].size(), (unsigned)max_iter, line_k,
                                                  res.max_dist * res.max_dist, b->h_res, inner_iters ? b->h_inner : nullptr,
@@ -404,6 +430,50 @@ extern "C" int icp_batch_estimate_point_to_line_gated(icp_batch *b, const double
   if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
   return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k, true, max_dist, inliers},
                        out, status, last_idx, inner_iters);
+}
+
+// ---- section 18: section 8's two entries with the point-to-plane residual (3-D batches, 3 <= k <= 16) ----
+namespace {
+bool plane_args_ok(const icp_batch *b, int k) { return b && b->dim == 3 && k >= 3 && k <= 16; }
+Residual plane_residual_of(int k) {
+  Residual res;
+  res.plane_k = k;
+  return res;
+}
+}  // namespace
+
+extern "C" int icp_batch_estimate_point_to_plane_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                        const double *d_dst, size_t dst_points, const icp_batch_item *items,
+                                                        size_t count, int k, size_t max_iter, icp_pose *out, int *status,
+                                                        uint32_t *d_last_idx, uint32_t *inner_iters) {
+  if (!plane_args_ok(b, k)) return ICP_BAD_ARGUMENT;
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, plane_residual_of(k), out,
+                         status, d_last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_estimate_point_to_plane(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                                 size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                                 size_t max_iter, icp_pose *out, int *status, uint32_t *last_idx,
+                                                 uint32_t *inner_iters) {
+  if (!plane_args_ok(b, k)) return ICP_BAD_ARGUMENT;
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, plane_residual_of(k), out, status,
+                       last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_plane_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->pctr[q];
+  return ICP_OK;
+}
+
+extern "C" int icp_debug_plane_batch_plan(unsigned threads, unsigned m, uint32_t out[4]) {
+  if (!out || (threads != 512u && threads != 1024u) || m < 1 || m > kPlaneBatchMaxM) return ICP_BAD_ARGUMENT;
+  const PlanePlan plan = plane_batch_plan_of(threads, m);
+  out[0] = plan.list_threads;
+  out[1] = plan.shared_bytes;
+  out[2] = plan.fixed_bytes;
+  out[3] = plan.lds_bytes;
+  return ICP_OK;
 }
 
 extern "C" int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]) {

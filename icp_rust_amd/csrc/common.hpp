@@ -555,6 +555,20 @@ hipError_t launch_line_estimate_gated_batch(unsigned threads, unsigned m_max, co
                                             const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
                                             double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
                                             uint32_t *inliers, hipStream_t stream, bool *granted);
+// EXTENSION: batched point-to-plane registration of 3-D items (p2plane_batch.hip: k_plane_estimate_batch; api_batch.hip
+// drives it).  One workgroup per item computes the item's plane normals (k neighbours) and runs the whole registration;
+// items, results, inner counts, indices, workgroup sizes and *granted as for launch_line_estimate_batch.
+constexpr unsigned kPlaneBatchMaxN = 1024, kPlaneBatchMaxM = 2048, kPlaneBatchMaxIter = 1024;
+inline unsigned plane_batch_threads(size_t n) { return n <= 512 ? 512u : 1024u; }
+hipError_t launch_plane_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                       TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
+// the LDS plan of such a launch: the targets whose k-best lists a round of the normals holds, the
+// bytes of the region the sort keys, the lists and the sort buffers share in turn, the bytes beside it, and their sum
+struct PlanePlan {
+  unsigned list_threads, shared_bytes, fixed_bytes, lds_bytes;
+};
+PlanePlan plane_batch_plan_of(unsigned threads, unsigned m_max);
 // A record of the fold tree of section 9 (fold_device.hpp): SUMS sums that are doubles, the inlier count and whether some
 // residual was NaN.
 template <int SUMS>

@@ -28,16 +28,13 @@
 #include "gn_device.hpp"
 #include "p2line_device.hpp"
 #include "p2plane_device.hpp"
+#include "pair_loop_device.hpp"
 #include "tiny_device.hpp"
 
 namespace icp {
 
-constexpr int kLineSums = kNAcc;  // jtj[9], jtr[3], huber error: what k_p2pl_accumulate folds
-
-struct LineCtl : TinyCtl {
-  double mad[1][2];
-  unsigned pos0;  // the sorted position of the target of original index 0
-};
+constexpr int kLineSums = kPairSums;  // (the sums and the control block of the inner loop: pair_loop_device.hpp)
+using LineCtl = PairCtl;
 
 // ---- the LDS plan of a launch ----
 // per workgroup, for its item's m targets (mp = m rounded up to 64): x | y (f64), the f32 screen records (+ 4 pads), the
@@ -249,77 +246,12 @@ __device__ __forceinline__ void line_estimate_item(const double *__restrict__ sr
       hasp = tid < cnt;
       blocks = cnt > 512u ? 2 : 1;
     }
-    // ---- p2pl_loop_on_pairs (api_ext.hip) on the cnt pairs ----
-    if (tid == 0) {
-      C->Ti = transform_identity();
-      C->done = cnt < 2u ? 1 : 0;  // fewer than two pairs: the identity, no update
-      C->applied = 0;
-      C->prev_error = 1.7976931348623157e308;  // DBL_MAX
-    }
-    __syncthreads();
-    if constexpr (GATED) {
-      if (hasp) pair_of(gqx[tid], gqy[tid], gnb[tid]);
-    }
-    for (int k = 0; k < ICP_INNER_MAX_ITER && !C->done; ++k) {
-      const Pose Ti = C->Ti;
-      double r = 0.;
-      if (hasp) {
-        r = plane_residual(pr, Ti);
-        if (r != r) C->nan = 1;
+    // ---- p2pl_loop_on_pairs (api_ext.hip) on the cnt pairs (pair_loop_device.hpp) ----
+    tiny_pair_loop<B>(pr, hasp, cnt, blocks, C, sbuf, sm, tot, [&]() {
+      if constexpr (GATED) {
+        if (hasp) pair_of(gqx[tid], gqy[tid], gnb[tid]);
       }
-      // exact median and MAD of r (launch_stddevs on ((r, 0), (0, 0)) under the identity: dimension 0's statistics of
-      // ((1 r + 0 0) + 0) - 0 = r, which plane_residual's trailing + nz dz = + 0.0 has already rid of a -0.0)
-      unsigned long long key[1] = {hasp ? f2k(r) : ~0ull};
-      double med[1], sig[1];
-      tiny_bitonic_sort<B, 1>(key, sbuf);
-      tiny_sorted_median_sigma<B, 1>(key, sbuf[2], cnt, C->mad, med, sig);  // (a third buffer: no barrier behind the sort)
-      const double sigma = sig[0];
-      // k_p2pl_accumulate's terms, one pair per thread, folded as block_reduce_store folds a 512-thread block
-      {
-        double acc[kLineSums];
-#pragma unroll
-        for (int q = 0; q < kLineSums; ++q) acc[q] = 0.;
-        if (hasp) {
-          const double gw = 1. / sigma;
-          const double e = r * r;
-          if (sigma != 0.) {  // src/lib.rs:243-245
-            const double a0 = -pr.ay, a1 = pr.ax;  // jacobian(), src/lib.rs:176-184
-            const double b0 = Ti.r00 * a0 + Ti.r01 * a1;
-            const double b1 = Ti.r10 * a0 + Ti.r11 * a1;
-            const double J[3] = {pr.nx * Ti.r00 + pr.ny * Ti.r10, pr.nx * Ti.r01 + pr.ny * Ti.r11, pr.nx * b0 + pr.ny * b1};
-            const double wg = huber_drho(e) * gw;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) acc[9 + q] = acc[9 + q] + (wg * J[q]) * r;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-              for (int b = 0; b < 3; ++b) acc[3 * a + b] = acc[3 * a + b] + (wg * J[a]) * J[b];
-          }
-          acc[12] = acc[12] + huber_rho(e);
-        }
-        wave_tree<kLineSums>(acc);
-        if ((tid & 63) == 0) {
-#pragma unroll
-          for (int q = 0; q < kLineSums; ++q) sm[wave][q] = acc[q];
-        }
-      }
-      __syncthreads();
-      // the blocks' left folds of their eight wave sums, then k_final_reduce over the block sums: thread b of its one
-      // 512-thread block holds 0 + sum_b, every other lane and wave +0.0, so its tree leaves (0 + sum_0) + (0 + sum_1)
-      if (tid < (unsigned)kLineSums) {
-        double p0 = sm[0][tid], p1 = 0.;
-        for (int w = 1; w < 8; ++w) p0 = p0 + sm[w][tid];
-        if (blocks > 1) {
-          p1 = sm[8][tid];
-          for (int w = 9; w < 16; ++w) p1 = p1 + sm[w][tid];
-          p1 = 0. + p1;
-        }
-        tot[tid] = ((0. + p0) + p1) + 0.;
-      }
-      __syncthreads();
-      if (tid == 0) tiny_inner_decide(C, tot);
-      __syncthreads();
-    }
+    });
     if (tid == 0) {
       tiny_outer_tail(C, it, max_iter, inner_out);
       if constexpr (GATED) {

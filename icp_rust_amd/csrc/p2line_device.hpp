@@ -9,7 +9,7 @@
 
 namespace icp {
 
-constexpr int kLineKMax = 16;
+constexpr int kLineKMax = kTinyKBestMax;
 
 // The line normal from the `cnt` neighbours found, in their (d^2, index) order: coord(j, d) is coordinate d of the j-th.
 // Fewer than 3 neighbours, or a zero-length eigenvector: the zero vector.
@@ -68,14 +68,14 @@ __device__ __forceinline__ void line_normal_of_neighbours(int cnt, Coord coord, 
 // ---- the line normals of a workgroup's own targets (the one-workgroup kernels: k_line_estimate_batch,
 // k_line_quality_batch) ----
 // Per target the k best by (d^2, index) from a sweep outwards over the targets SORTED BY x in LDS (tiny_sort_targets;
-// exact: the k-nearest set under that order is unique), L targets per round with their lists in `shared` ((8 + 4) B x
-// kLineKMax x L, free again on return), then line_normal_of_neighbours -> nrm[sorted position].  kk: the entries' k,
+// tiny_device.hpp: tiny_k_best_of_target, which the plane normals of p2plane_batch.hip share), L targets per round with
+// their lists in `shared` ((8 + 4) B x kLineKMax x L, free again on return), then line_normal_of_neighbours ->
+// nrm[sorted position].  kk: the entries' k,
 // clamped here to m.  Every thread of the workgroup calls it; it ends with a barrier.
 __device__ __forceinline__ void line_normals_of_sorted_targets(const TinyTargets &tg, double cx, double cy, double scale,
                                                                int kk, unsigned L, unsigned char *shared, double2 *nrm) {
   const unsigned tid = threadIdx.x, m = tg.m;
   const double *tx = tg.tx, *ty = tg.ty;
-  const float4 *g4 = tg.g4;
   double *ld = reinterpret_cast<double *>(shared);                // [kLineKMax][L]: d^2
   uint32_t *li = reinterpret_cast<uint32_t *>(ld + kLineKMax * L);  // [kLineKMax][L]: (index << 16) | sorted position
   int k = kk < (int)m ? kk : (int)m;
@@ -85,87 +85,7 @@ __device__ __forceinline__ void line_normals_of_sorted_targets(const TinyTargets
     if (tid < L && j < m) {
       double *bd = ld + tid;
       uint32_t *bi = li + tid;
-      const double x = tx[j], y = ty[j];
-      const float4 own = g4[j];
-      const double ec = tiny_screen_margin(x - cx, y - cy, 0., scale);
-      // The k best are kept UNORDERED while the sweep runs, with the worst of them -- its (d^2, index) and its slot --
-      // in registers: a candidate is refused without touching the list, an accepted one replaces the worst and the
-      // new worst is found by k independent reads (a sorted insertion is a chain of dependent LDS accesses as long as
-      // the deepest insertion among the wave's 64 lanes).  They are ordered once, after the sweep.
-      float thr = __builtin_huge_valf();  // the screen's bound: the worst kept distance once k are kept
-      double wd = __builtin_huge_val();
-      uint32_t wi = 0xffffffffu;
-      int wq = 0, cnt = 0;
-      auto offer = [&](unsigned jj, unsigned orig) {
-        const double dx = x - tx[jj], dy = y - ty[jj];
-        const double dd = dx * dx + dy * dy;
-        const uint32_t ti = (orig << 16) | jj;  // (index and position below 2^16: ordered as the indices are)
-        if (cnt == k && !(dd < wd || (dd == wd && ti < wi))) return;
-        const int at = cnt < k ? cnt : wq;
-        bd[at * L] = dd;
-        bi[at * L] = ti;
-        if (cnt < k) ++cnt;
-        if (cnt == k) {
-          wd = bd[0];
-          wi = bi[0];
-          wq = 0;
-          for (int q = 1; q < k; ++q) {
-            const double dq = bd[q * L];
-            const uint32_t iq = bi[q * L];
-            if (dq > wd || (dq == wd && iq > wi)) {
-              wd = dq;
-              wi = iq;
-              wq = q;
-            }
-          }
-          thr = tiny_screen_bound(wd, ec);
-        }
-      };
-      // outwards from the target's own position while a target's x alone does not rule it out: the f32 difference is
-      // within ec of the true one and thr carries that margin, so fx^2 > thr  =>  strictly farther than the k-th best.
-      // Four targets per step, their LDS reads in flight together (as tiny_nearest); unlike a nearest-neighbour
-      // search a list must not be offered a target twice, so a step's slots past either end are masked, not repeated.
-      auto visit = [&](const float4 g, unsigned jj, bool valid) {
-        const float fx = own.x - g.x, fy = own.y - g.y;
-        if (valid && !(__builtin_fmaf(fy, fy, fx * fx) > thr)) offer(jj, __float_as_uint(g.w));
-      };
-      offer(j, __float_as_uint(own.w));
-      for (unsigned jj = j + 1; jj < m; jj += 4) {  // (g4 carries four +inf pads past mp)
-        const float4 g0 = g4[jj], g1 = g4[jj + 1], g2 = g4[jj + 2], g3 = g4[jj + 3];
-        const float f0 = own.x - g0.x;
-        if (f0 * f0 > thr) break;  // sorted by x: everything further right is farther still
-        visit(g0, jj, true);
-        visit(g1, jj + 1, jj + 1 < m);
-        visit(g2, jj + 2, jj + 2 < m);
-        visit(g3, jj + 3, jj + 3 < m);
-      }
-      for (unsigned jj = j; jj > 0;) {
-        const unsigned j0 = jj - 1, j1 = jj > 1 ? jj - 2 : 0, j2 = jj > 2 ? jj - 3 : 0, j3 = jj > 3 ? jj - 4 : 0;
-        const float4 g0 = g4[j0], g1 = g4[j1], g2 = g4[j2], g3 = g4[j3];
-        const float f0 = own.x - g0.x;
-        if (f0 * f0 > thr) break;
-        visit(g0, j0, true);
-        visit(g1, j1, jj > 1);
-        visit(g2, j2, jj > 2);
-        visit(g3, j3, jj > 3);
-        jj = j3;
-      }
-      // the (d^2, index) order: entry q's rank is the number of entries before it (the pairs are distinct); its
-      // sorted position then goes where its d^2 was, at slot `rank` (every rank is known before the first is written)
-      unsigned long long ranks = 0;
-      for (int q = 0; q < cnt; ++q) {
-        const double dq = bd[q * L];
-        const uint32_t iq = bi[q * L];
-        unsigned r = 0;
-        for (int u = 0; u < cnt; ++u) {
-          const double du = bd[u * L];
-          const uint32_t iu = bi[u * L];
-          r += (du < dq || (du == dq && iu < iq)) ? 1u : 0u;
-        }
-        ranks |= (unsigned long long)r << (4 * q);
-      }
-      for (int q = 0; q < cnt; ++q)
-        bd[((ranks >> (4 * q)) & 15u) * L] = __longlong_as_double((long long)(bi[q * L] & 0xffffu));
+      const int cnt = tiny_k_best_of_target<2>(tg, j, cx, cy, 0., scale, k, L, bd, bi);
       double nv[2];
       line_normal_of_neighbours(cnt, [&](int q, int d) {
         const unsigned pos = (unsigned)__double_as_longlong(bd[q * L]);

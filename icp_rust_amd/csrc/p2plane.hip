@@ -26,38 +26,7 @@ __global__ void k_final_reduce(const double *__restrict__ partials, int blocks, 
 
 constexpr int kNormalKMax = 16;
 
-// cyclic Jacobi on a symmetric 3x3 (a: upper triangle used, row-major full), eigenvectors in the
-// columns of v.  Fixed operation order (the CPU restatement runs the same sequence).
-__device__ inline void jacobi3(double a[3][3], double v[3][3]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1. : 0.;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    const double off = (a[0][1] * a[0][1] + a[0][2] * a[0][2]) + a[1][2] * a[1][2];
-    if (off == 0.) break;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        if (a[p][q] == 0.) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2. * a[p][q]);
-        const double t = (theta >= 0. ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-        const double c = 1. / sqrt(t * t + 1.), s = t * c;
-        for (int k = 0; k < 3; ++k) {  // A <- A J (columns p, q)
-          const double akp = a[k][p], akq = a[k][q];
-          a[k][p] = c * akp - s * akq;
-          a[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {  // A <- J^T A (rows p, q)
-          const double apk = a[p][k], aqk = a[q][k];
-          a[p][k] = c * apk - s * aqk;
-          a[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = v[k][p], vkq = v[k][q];
-          v[k][p] = c * vkp - s * vkq;
-          v[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-}
+// (jacobi3 and everything behind the k best neighbours: p2plane_device.hpp, plane_normal_of_neighbours)
 
 // One lane per target: its k nearest targets through the grid (Chebyshev rings of cells around its
 // own cell until the k-th distance is covered by the visited block), then the covariance's smallest
@@ -120,41 +89,8 @@ __global__ __launch_bounds__(64) void k_target_normals(const double *__restrict_
     cover -= 1e-9 * (g.scale + fabs(p[0]) + fabs(p[1]) + fabs(p[2]));
     if (cnt == k && cover > 0. && bd[k - 1] < cover * cover) break;
   }
-  double nrm[3] = {0., 0., 0.};
-  if (cnt >= 3) {
-    double mean[3] = {0., 0., 0.};
-    for (int j = 0; j < cnt; ++j)
-      for (int d = 0; d < 3; ++d) mean[d] = mean[d] + dst[(size_t)bi[j] * 3 + d];
-    for (int d = 0; d < 3; ++d) mean[d] = mean[d] / (double)cnt;
-    double a[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};
-    for (int j = 0; j < cnt; ++j) {
-      double e[3];
-      for (int d = 0; d < 3; ++d) e[d] = dst[(size_t)bi[j] * 3 + d] - mean[d];
-      for (int r = 0; r < 3; ++r)
-        for (int s = 0; s < 3; ++s) a[r][s] = a[r][s] + e[r] * e[s];
-    }
-    double v[3][3];
-    jacobi3(a, v);
-    int col = 0;  // smallest eigenvalue; ties -> lowest column
-    if (a[1][1] < a[col][col]) col = 1;
-    if (a[2][2] < a[col][col]) col = 2;
-    double n0 = v[0][col], n1 = v[1][col], n2 = v[2][col];
-    const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-    if (len > 0.) {
-      n0 = n0 / len;
-      n1 = n1 / len;
-      n2 = n2 / len;
-      const double lead = n2 != 0. ? n2 : (n1 != 0. ? n1 : n0);
-      if (lead < 0.) {
-        n0 = -n0;
-        n1 = -n1;
-        n2 = -n2;
-      }
-      nrm[0] = n0;
-      nrm[1] = n1;
-      nrm[2] = n2;
-    }
-  }
+  double nrm[3];
+  plane_normal_of_neighbours(cnt, [&](int j, int d) { return dst[(size_t)bi[j] * 3 + d]; }, nrm);
   normals[(size_t)i * 3] = nrm[0];
   normals[(size_t)i * 3 + 1] = nrm[1];
   normals[(size_t)i * 3 + 2] = nrm[2];

@@ -1,0 +1,247 @@
+// EXTENSION beyond the reference (include/icp_mi355x.h section 18): batched point-to-PLANE registration, one workgroup per
+// 3-D item.  Item i's result is what icp_create(3, dst_i) + icp_compute_target_normals(k) + icp_estimate_point_to_plane
+// return on a fresh handle, bit for bit (p2plane.hip's header comment and api_ext.hip: p2pl_loop_on_pairs are the
+// definition), or the workgroup hands the item back (TinyResult::status = -1) and api_batch.hip serves it through exactly
+// those entries.  Nothing crosses workgroups: no flag, no atomic, no barrier across them; every loop has a static bound
+// (the rounds of the normals, jacobi3's 12 sweeps, ICP_INNER_MAX_ITER, max_iter).  What a workgroup does, each piece the
+// one copy the other one-workgroup kernels run too:
+//   box        fmin / fmax over its own targets (tiny_batch_box<3>)
+//   targets    sorted by fl32(x - cx) into LDS, x | y | z with the f32 screen records (tiny_sort_targets<3>)
+//   normals    per target the k best by (d^2, index), d^2 = (dx dx + dy dy) + dz dz, from a sweep outwards over the sorted
+//              targets (tiny_k_best_of_target<3>), lists in LDS for as many targets per round as the grant allows, then
+//              plane_normal_of_neighbours, the statement k_target_normals evaluates (p2plane_device.hpp)
+//   outer      transform xy with z carried, exact nearest neighbour (tiny_nearest<3>, warm), the pair of k_p2pl_gather
+//   inner      tiny_pair_loop (pair_loop_device.hpp): plane_residual, exact median and MAD, k_p2pl_accumulate's 13 sums in
+//              the tree of reduce_geometry(n), solve_update and the break tests; then tiny_outer_tail
+// Hand-back reasons: a box that is not finite; a NaN target coordinate; a rotation update outside the restated range of
+// sin / cos.  A NaN residual is the item's ICP_NAN_INPUT.
+#include "common.hpp"
+#include "gn_device.hpp"
+#include "p2plane_device.hpp"
+#include "pair_loop_device.hpp"
+#include "tiny_device.hpp"
+
+namespace icp {
+
+// ---- the LDS plan of a launch ----
+// per workgroup, for its item's m targets (mp = m rounded up to 64): x | y | z (f64), the f32 screen records (+ 4 pads),
+// the normals by sorted position (3 x f64); then ONE shared region, sized by the launch; then the wave sums, the totals
+// and PairCtl.  The shared region holds, one after the other: the target sort's keys (8 B x the next power of two of m),
+// the k-best lists of the normals ((8 + 4) B x 16 per list-holding thread), the estimator's two sort buffers and sorted
+// keys (3 x 8 B x B).  The normals run in rounds of `list_threads` targets: as many as the grant leaves room for, up to
+// one per thread and per target -- 128 beside 2048 targets, sixteen rounds with most of the workgroup idle.
+constexpr size_t kPlaneListBytes = kTinyKBestMax * (sizeof(double) + sizeof(uint32_t));
+constexpr size_t plane_fixed_bytes(unsigned m) {
+  const size_t mp = (m + 63u) & ~63u;
+  return mp * 3 * sizeof(double) + (mp + 4) * sizeof(float4) + mp * 3 * sizeof(double) + sizeof(double) * 16 * kPairSums +
+         sizeof(double) * 16 + 256;
+}
+static_assert(sizeof(PairCtl) <= 256, "PairCtl's share of the LDS");
+static_assert(kPlaneListBytes == 192, "sixteen (d^2, index | position) entries");
+static_assert(kPlaneBatchMaxM <= kTinyKBestMaxTargets, "(original index << 16) | sorted position: both below 2^16");
+static_assert(1024 / 64 * 6 * sizeof(double) <= plane_fixed_bytes(1), "the box's wave minima");
+constexpr PlanePlan plane_batch_plan(unsigned threads, unsigned m_max) {
+  const size_t fixed = plane_fixed_bytes(m_max);
+  size_t keys = 64;
+  while (keys < m_max) keys <<= 1;
+  const size_t fit = (kTinyLdsGrant - fixed) / kPlaneListBytes / 64 * 64;
+  size_t lists = (m_max + 63u) & ~63u;  // (a list per target is all a round can use)
+  lists = lists < threads ? lists : threads;
+  lists = lists < fit ? lists : fit;
+  size_t shared = lists * kPlaneListBytes;
+  shared = shared > keys * 8 ? shared : keys * 8;
+  shared = shared > (size_t)3 * threads * 8 ? shared : (size_t)3 * threads * 8;
+  return PlanePlan{(unsigned)lists, (unsigned)shared, (unsigned)fixed, (unsigned)(fixed + shared)};
+}
+// the plan at its corners: the smallest item, 1024 targets (three rounds of 448), the largest item (sixteen rounds of 128)
+static_assert(plane_batch_plan(512, 1).list_threads == 64 && plane_batch_plan(512, 1).shared_bytes == 3 * 512 * 8 &&
+                  plane_batch_plan(1024, 1).shared_bytes == 3 * 1024 * 8 && plane_batch_plan(512, 1).fixed_bytes == 6208,
+              "m = 1");
+static_assert(plane_batch_plan(1024, 1024).fixed_bytes == 67648 && plane_batch_plan(1024, 1024).list_threads == 448 &&
+                  plane_batch_plan(512, 1024).list_threads == 448 && plane_batch_plan(1024, 1024).shared_bytes == 448 * 192,
+              "m = 1024");
+static_assert(plane_batch_plan(1024, kPlaneBatchMaxM).fixed_bytes == 133184 &&
+                  kTinyLdsGrant - plane_batch_plan(1024, kPlaneBatchMaxM).fixed_bytes == 30400 &&
+                  plane_batch_plan(512, kPlaneBatchMaxM).list_threads == 128 &&
+                  plane_batch_plan(1024, kPlaneBatchMaxM).list_threads == 128 &&
+                  plane_batch_plan(1024, kPlaneBatchMaxM).shared_bytes == 3 * 1024 * 8 &&
+                  plane_batch_plan(1024, kPlaneBatchMaxM).lds_bytes == 157760 &&
+                  plane_batch_plan(1024, kPlaneBatchMaxM).lds_bytes <= kTinyLdsGrant,
+              "m = 2048: the sort buffers fit in what the fixed part leaves");
+// ... and at every m between: at least one round's lists, and never more LDS than the grant
+constexpr bool plane_batch_plan_fits_everywhere() {
+  for (unsigned m = 1; m <= kPlaneBatchMaxM; ++m)
+    for (unsigned threads = 512; threads <= 1024; threads += 512) {
+      const PlanePlan plan = plane_batch_plan(threads, m);
+      if (plan.list_threads < 64 || plan.list_threads > threads || plan.lds_bytes > kTinyLdsGrant) return false;
+    }
+  return true;
+}
+static_assert(plane_batch_plan_fits_everywhere(), "every launch's LDS is within the grant");
+
+PlanePlan plane_batch_plan_of(unsigned threads, unsigned m_max) { return plane_batch_plan(threads, m_max); }
+
+// ---- the plane normals of a workgroup's own targets ----
+// Per target the k best by (d^2, index) (tiny_k_best_of_target<3>), L targets per round with their lists in `shared`
+// (kPlaneListBytes x L, free again on return), then plane_normal_of_neighbours -> nrm[3 x sorted position].  kk: the
+// entries' k, clamped here to m.  Every thread of the workgroup calls it; it ends with a barrier.
+__device__ __forceinline__ void plane_normals_of_sorted_targets(const TinyTargets &tg, double cx, double cy, double cz,
+                                                                double scale, int kk, unsigned L, unsigned char *shared,
+                                                                double *nrm) {
+  const unsigned tid = threadIdx.x, m = tg.m;
+  const double *tx = tg.tx, *ty = tg.ty, *tz = tg.tz;
+  double *ld = reinterpret_cast<double *>(shared);                      // [kTinyKBestMax][L]: d^2
+  uint32_t *li = reinterpret_cast<uint32_t *>(ld + kTinyKBestMax * L);  // [kTinyKBestMax][L]: (index << 16) | position
+  int k = kk < (int)m ? kk : (int)m;
+  k = k < kTinyKBestMax ? k : kTinyKBestMax;  // (the entries refuse k > 16: this only keeps the lists inside their rows)
+  for (unsigned base = 0; base < m; base += L) {  // (at most kPlaneBatchMaxM / 128 = sixteen rounds)
+    const unsigned j = base + tid;
+    if (tid < L && j < m) {
+      double *bd = ld + tid;
+      const int cnt = tiny_k_best_of_target<3>(tg, j, cx, cy, cz, scale, k, L, bd, li + tid);
+      double nv[3];
+      plane_normal_of_neighbours(cnt, [&](int q, int d) {
+        const unsigned pos = (unsigned)__double_as_longlong(bd[q * L]);
+        return d == 0 ? tx[pos] : (d == 1 ? ty[pos] : tz[pos]);
+      }, nv);
+      nrm[3 * j] = nv[0];
+      nrm[3 * j + 1] = nv[1];
+      nrm[3 * j + 2] = nv[2];
+    }
+  }
+  __syncthreads();
+}
+
+template <unsigned B>
+__global__ __launch_bounds__(B) void k_plane_estimate_batch(const double *__restrict__ src_all,
+                                                            const double *__restrict__ dst_all,
+                                                            const TinyBatchItem *__restrict__ items, unsigned max_iter,
+                                                            int kk, unsigned L, unsigned shared_bytes, TinyResult *res_all,
+                                                            uint32_t *inner_all, uint32_t *idx_all) {
+  static_assert(B == 512 || B == 1024, "one or two blocks of the 512-thread fold tree, a power of two for the sort");
+  extern __shared__ unsigned char lds_raw[];
+  const TinyBatchItem &item = items[blockIdx.x];  // (read in place: a copy of the pose would live in scratch)
+  const unsigned n = item.n, m = item.m;          // 1 <= n <= B, 1 <= m <= kPlaneBatchMaxM (api_batch.hip: plane_fits)
+  const double *__restrict__ src = src_all + item.src_first * 3;
+  const double *__restrict__ dst = dst_all + item.dst_first * 3;
+  TinyResult *res = res_all + item.slot;
+  uint32_t *inner_out = inner_all ? inner_all + (size_t)item.slot * max_iter : nullptr;
+  uint32_t *idx_out = idx_all ? idx_all + item.idx_first : nullptr;
+  const unsigned tid = threadIdx.x;
+
+  double cx, cy, cz, scale;
+  if (!tiny_batch_box<3, B>(dst, m, reinterpret_cast<double *>(lds_raw), &cx, &cy, &cz, &scale)) {
+    if (tid == 0) res->status = -1;
+    return;
+  }
+  // ---- LDS carve-up (plane_batch_plan) ----  (targets are kept SORTED BY x: position j below is not the target's index)
+  const unsigned mp = (m + 63u) & ~63u;
+  double *tx = reinterpret_cast<double *>(lds_raw);
+  double *ty = tx + mp;
+  double *tz = ty + mp;
+  unsigned char *p = reinterpret_cast<unsigned char *>(tz + mp);
+  float4 *g4 = reinterpret_cast<float4 *>(p);  // {x, y, z relative to the box centre as f32, original index}
+  p += sizeof(float4) * (mp + 4);
+  double *nrm = reinterpret_cast<double *>(p);  // the plane normal of the target at sorted position j, at [3 j]
+  p += sizeof(double) * 3 * mp;
+  unsigned char *shared = p;  // the target sort's keys, then the normals' lists, then the estimator's sort
+  p += shared_bytes;
+  double(*sm)[kPairSums] = reinterpret_cast<double(*)[kPairSums]>(p);
+  p += sizeof(double) * 16 * kPairSums;
+  double *tot = reinterpret_cast<double *>(p);
+  p += sizeof(double) * 16;
+  PairCtl *C = reinterpret_cast<PairCtl *>(p);
+  const TinyTargets tg = {tx, ty, tz, g4, m};
+
+  if (tid == 0) {
+    C->T = item.init;
+    C->nan = C->bail = 0;
+    C->evals = 0;
+    C->pos0 = 0;
+    C->mad[0][0] = C->mad[0][1] = 0.;
+  }
+  if (tid < 16) {  // (the wave sums of the waves a 512-thread workgroup does not have stay +0.0)
+#pragma unroll
+    for (int q = 0; q < kPairSums; ++q) sm[tid][q] = 0.;
+  }
+  tiny_sort_targets<3, B>(dst, cx, cy, cz, reinterpret_cast<unsigned long long *>(shared), tg,
+                          [&](unsigned j, unsigned k, double x, double y) {
+                            if (k == 0) C->pos0 = j;
+                            const double z = tz[j];  // (this thread has just written it)
+                            if ((x != x) | (y != y) | (z != z)) C->bail = 1;  // a NaN target: the single call decides
+                          });
+  if (C->bail) {  // (uniform)
+    if (tid == 0) res->status = -1;
+    return;
+  }
+  plane_normals_of_sorted_targets(tg, cx, cy, cz, scale, kk, L, shared, nrm);
+  unsigned long long(*sbuf)[1][B] = reinterpret_cast<unsigned long long(*)[1][B]>(shared);  // two sort buffers, then the sorted keys
+  const bool has = tid < n;
+  double px = 0., py = 0., pz = 0.;
+  if (has) {
+    px = src[(size_t)tid * 3];
+    py = src[(size_t)tid * 3 + 1];
+    pz = src[(size_t)tid * 3 + 2];
+  }
+  const int blocks = n > 512u ? 2 : 1;  // reduce_geometry(n) for n <= 1024: 512-thread blocks
+  unsigned bi = 0xffffffffu;
+  for (unsigned it = 0; it < max_iter; ++it) {
+    const Pose T = C->T;
+    // ---- transform + exact nearest neighbour, the pair of k_p2pl_gather ----
+    PlanePair pr;
+    pr.ax = pr.ay = pr.qx = pr.qy = pr.dz = pr.nx = pr.ny = pr.nz = 0.;
+    if (has) {
+      const double qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24; z is carried
+      const double qy = (T.r10 * px + T.r11 * py) + T.ty;
+      unsigned nb, nbo;  // sorted position / original index of the nearest target
+      tiny_nearest<3>(tg, qx, qy, pz, cx, cy, cz, scale, bi, &nb, &nbo);
+      bi = nb;
+      if (nb == 0xffffffffu) {  // no finite distance (NaN query): index 0, as a scan from 0 would
+        nb = C->pos0;
+        nbo = 0;
+      }
+      pr.ax = qx;
+      pr.ay = qy;
+      pr.qx = tx[nb];
+      pr.qy = ty[nb];
+      pr.dz = pz - tz[nb];
+      pr.nx = nrm[3 * nb];
+      pr.ny = nrm[3 * nb + 1];
+      pr.nz = nrm[3 * nb + 2];
+      if (idx_out && it + 1 == max_iter) idx_out[tid] = nbo;
+    }
+    // ---- p2pl_loop_on_pairs (api_ext.hip) on the n pairs ----
+    tiny_pair_loop<B>(pr, has, n, blocks, C, sbuf, sm, tot, []() {});
+    if (tid == 0) tiny_outer_tail(C, it, max_iter, inner_out);
+    __syncthreads();
+    if (C->nan | C->bail) break;
+    if (C->fixed && it + 2 < max_iter) it = max_iter - 2;  // (uniform: the flag is the workgroup's)
+  }
+  if (tid == 0) {
+    res->pose = C->T;
+    res->evals = C->evals;
+    res->sorted = C->evals;
+    res->status = C->nan ? 3 : (C->bail ? -1 : 0);
+  }
+}
+
+hipError_t launch_plane_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                       TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted) {
+  // the grant above 64 KB of dynamic LDS, asked for both kernels once per process; refused: nothing launches
+  static TinyLdsGrant grant;
+  *granted = grant.ask({reinterpret_cast<const void *>(&k_plane_estimate_batch<512>),
+                        reinterpret_cast<const void *>(&k_plane_estimate_batch<1024>)},
+                       kTinyLdsGrant);
+  if (!*granted || count == 0) return hipSuccess;
+  const PlanePlan plan = plane_batch_plan(threads, m_max);
+  if (threads == 512u)
+    hipLaunchKernelGGL((k_plane_estimate_batch<512>), dim3(count), dim3(512), plan.lds_bytes, stream, d_src, d_dst, d_items,
+                       max_iter, k, plan.list_threads, plan.shared_bytes, res, inner, d_idx);
+  else
+    hipLaunchKernelGGL((k_plane_estimate_batch<1024>), dim3(count), dim3(1024), plan.lds_bytes, stream, d_src, d_dst,
+                       d_items, max_iter, k, plan.list_threads, plan.shared_bytes, res, inner, d_idx);
+  return hipGetLastError();
+}
+
+}  // namespace icp

@@ -1,9 +1,9 @@
 // What the one-workgroup estimators share, each piece once: k_tiny_eval, k_tiny_estimate / k_tiny_estimate_batch
-// (gn_fast.hip, tiny_estimate_body.inc), k_line_estimate_batch / k_line_estimate_gated_batch (p2line_batch.hip) and,
-// for the box, the targets and the search, k_line_quality_batch (quality_line.hip).  Every piece defines a result's
-// bits -- the tie rule, the screen's margin, the order of the break tests -- and the batch entries promise what the
-// single calls return, bit for bit: so there is one copy of each.  All functions are called by every thread of the
-// workgroup unless they say otherwise.
+// (gn_fast.hip, tiny_estimate_body.inc), k_line_estimate_batch / k_line_estimate_gated_batch (p2line_batch.hip),
+// k_plane_estimate_batch (p2plane_batch.hip) and, for the box, the targets and the search, k_line_quality_batch
+// (quality_line.hip).  Every piece defines a result's bits -- the tie rule, the screen's margin, the order of the break
+// tests -- and the batch entries promise what the single calls return, bit for bit: so there is one copy of each.  All
+// functions are called by every thread of the workgroup unless they say otherwise.
 #pragma once
 #include <initializer_list>
 
@@ -347,6 +347,113 @@ __device__ __forceinline__ void tiny_nearest(const TinyTargets &t, double qx, do
   }
   *pos = nb;
   *orig = nbo;
+}
+
+// ---- the k nearest targets of a target (the normals of the one-workgroup kernels: p2line_device.hpp:
+// line_normals_of_sorted_targets, p2plane_batch.hip: plane_normals_of_sorted_targets) ----
+// The k best by (d^2, index) of the target at sorted position j, from a sweep outwards over the targets SORTED BY x
+// (exact: the k-nearest set under that order is unique), one target per calling thread.  bd / bi: the thread's list in
+// LDS, kTinyKBestMax entries each, entry q at [q * L].  Returns how many were found (min(k, m)); on return bd[q * L]
+// holds, as an integer's bits, the sorted position of the q-th nearest in (d^2, index) order.  1 <= k <= kTinyKBestMax.
+constexpr int kTinyKBestMax = 16;
+constexpr unsigned kTinyKBestMaxTargets = 1u << 16;  // (original index << 16) | sorted position, in 32 bits
+template <int DIM>
+__device__ __forceinline__ int tiny_k_best_of_target(const TinyTargets &tg, unsigned j, double cx, double cy, double cz,
+                                                     double scale, int k, unsigned L, double *bd, uint32_t *bi) {
+  const unsigned m = tg.m;
+  const double *tx = tg.tx, *ty = tg.ty, *tz = tg.tz;
+  const float4 *g4 = tg.g4;
+  const double x = tx[j], y = ty[j], z = DIM == 3 ? tz[j] : 0.;
+  const float4 own = g4[j];
+  const double ec = tiny_screen_margin(x - cx, y - cy, DIM == 3 ? z - cz : 0., scale);
+  // The k best are kept UNORDERED while the sweep runs, with the worst of them -- its (d^2, index) and its slot --
+  // in registers: a candidate is refused without touching the list, an accepted one replaces the worst and the
+  // new worst is found by k independent reads (a sorted insertion is a chain of dependent LDS accesses as long as
+  // the deepest insertion among the wave's 64 lanes).  They are ordered once, after the sweep.
+  float thr = __builtin_huge_valf();  // the screen's bound: the worst kept distance once k are kept
+  double wd = __builtin_huge_val();
+  uint32_t wi = 0xffffffffu;
+  int wq = 0, cnt = 0;
+  auto offer = [&](unsigned jj, unsigned orig) {
+    const double dx = x - tx[jj], dy = y - ty[jj];
+    double dd = dx * dx + dy * dy;
+    if (DIM == 3) {  // (dx dx + dy dy) + dz dz: k_target_normals' expression
+      const double dz = z - tz[jj];
+      dd = dd + dz * dz;
+    }
+    const uint32_t ti = (orig << 16) | jj;  // (index and position below 2^16: ordered as the indices are)
+    if (cnt == k && !(dd < wd || (dd == wd && ti < wi))) return;
+    const int at = cnt < k ? cnt : wq;
+    bd[at * L] = dd;
+    bi[at * L] = ti;
+    if (cnt < k) ++cnt;
+    if (cnt == k) {
+      wd = bd[0];
+      wi = bi[0];
+      wq = 0;
+      for (int q = 1; q < k; ++q) {
+        const double dq = bd[q * L];
+        const uint32_t iq = bi[q * L];
+        if (dq > wd || (dq == wd && iq > wi)) {
+          wd = dq;
+          wi = iq;
+          wq = q;
+        }
+      }
+      thr = tiny_screen_bound(wd, ec);
+    }
+  };
+  // outwards from the target's own position while a target's x alone does not rule it out: the f32 difference is
+  // within ec of the true one and thr carries that margin, so fx^2 > thr  =>  strictly farther than the k-th best.
+  // Four targets per step, their LDS reads in flight together (as tiny_nearest); unlike a nearest-neighbour
+  // search a list must not be offered a target twice, so a step's slots past either end are masked, not repeated.
+  auto visit = [&](const float4 g, unsigned jj, bool valid) {
+    const float fx = own.x - g.x, fy = own.y - g.y;
+    float s2 = __builtin_fmaf(fy, fy, fx * fx);
+    if (DIM == 3) {
+      const float fz = own.z - g.z;
+      s2 = __builtin_fmaf(fz, fz, s2);
+    }
+    if (valid && !(s2 > thr)) offer(jj, __float_as_uint(g.w));
+  };
+  offer(j, __float_as_uint(own.w));
+  for (unsigned jj = j + 1; jj < m; jj += 4) {  // (g4 carries four +inf pads past mp)
+    const float4 g0 = g4[jj], g1 = g4[jj + 1], g2 = g4[jj + 2], g3 = g4[jj + 3];
+    const float f0 = own.x - g0.x;
+    if (f0 * f0 > thr) break;  // sorted by x: everything further right is farther still
+    visit(g0, jj, true);
+    visit(g1, jj + 1, jj + 1 < m);
+    visit(g2, jj + 2, jj + 2 < m);
+    visit(g3, jj + 3, jj + 3 < m);
+  }
+  for (unsigned jj = j; jj > 0;) {
+    const unsigned j0 = jj - 1, j1 = jj > 1 ? jj - 2 : 0, j2 = jj > 2 ? jj - 3 : 0, j3 = jj > 3 ? jj - 4 : 0;
+    const float4 g0 = g4[j0], g1 = g4[j1], g2 = g4[j2], g3 = g4[j3];
+    const float f0 = own.x - g0.x;
+    if (f0 * f0 > thr) break;
+    visit(g0, j0, true);
+    visit(g1, j1, jj > 1);
+    visit(g2, j2, jj > 2);
+    visit(g3, j3, jj > 3);
+    jj = j3;
+  }
+  // the (d^2, index) order: entry q's rank is the number of entries before it (the pairs are distinct); its
+  // sorted position then goes where its d^2 was, at slot `rank` (every rank is known before the first is written)
+  unsigned long long ranks = 0;
+  for (int q = 0; q < cnt; ++q) {
+    const double dq = bd[q * L];
+    const uint32_t iq = bi[q * L];
+    unsigned r = 0;
+    for (int u = 0; u < cnt; ++u) {
+      const double du = bd[u * L];
+      const uint32_t iu = bi[u * L];
+      r += (du < dq || (du == dq && iu < iq)) ? 1u : 0u;
+    }
+    ranks |= (unsigned long long)r << (4 * q);
+  }
+  for (int q = 0; q < cnt; ++q)
+    bd[((ranks >> (4 * q)) & 15u) * L] = __longlong_as_double((long long)(bi[q * L] & 0xffffu));
+  return cnt;
 }
 
 // ---- thread 0's part of the loops ----

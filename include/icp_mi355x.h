@@ -68,7 +68,8 @@ extern "C" {
  * icp_estimate_point_to_line*); so was section 15 (icp_batch_estimate_point_to_line*; icp_batch_line_counters in
  * icp_mi355x_debug.h); so was section 16 (icp_line_quality, icp_evaluate_point_to_line*,
  * icp_batch_evaluate_point_to_line*; icp_batch_line_quality_counters in icp_mi355x_debug.h); so was section 17
- * (icp_batch_estimate_point_to_line_gated*; icp_batch_line_gated_counters in icp_mi355x_debug.h) */
+ * (icp_batch_estimate_point_to_line_gated*; icp_batch_line_gated_counters in icp_mi355x_debug.h); so was section 18
+ * (icp_batch_estimate_point_to_plane*; icp_batch_plane_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -981,6 +982,30 @@ int icp_batch_estimate_point_to_line_gated_device(icp_batch *b, const double *d_
                                                   size_t count, int k, size_t max_iter, double max_dist, icp_pose *out,
                                                   int *status, uint32_t *d_last_idx, uint32_t *inner_iters,
                                                   uint32_t *inliers);
+
+/* ================================================================================
+ * 18. EXTENSION (not in the reference): many small point-to-plane registrations in one call
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 8's call with the point-to-plane
+ * residual, for 3-D batches: submap patches, object segments, voxel-thinned frames, K pose hypotheses against one small
+ * cloud.  Item i's out[i], status[i], indices and inner counts are what icp_create(3, dst + 3 dst_first, m) +
+ * icp_compute_target_normals(k) + icp_estimate_point_to_plane(src + 3 src_first, n, &init, max_iter) return on a fresh
+ * handle, bit for bit (the ungated call; a first failing step's status is the item's: ICP_EMPTY_DST without targets,
+ * ICP_BAD_ARGUMENT where icp_compute_target_normals refuses them, ICP_NAN_INPUT).  Every item with 1 <= n <= 1024,
+ * 1 <= m <= 2048 and 1 <= max_iter <= 1024 runs as ONE workgroup that computes the item's plane normals and the whole
+ * registration (one launch per workgroup size, at most two); the other items, and those a workgroup hands back, go
+ * through exactly those three entries one after another.  An item is never approximated.  DESIGN.md section 9m lists
+ * the hand-back reasons.
+ * Arguments, ranges, last_idx, inner_iters, per-item statuses and the call's own return value are section 8's; in
+ * addition ICP_BAD_ARGUMENT for a batch that is not 3-D and for k outside [3, 16] -- checked, like every argument,
+ * before the device is touched.  count == 0 is a successful no-op. */
+int icp_batch_estimate_point_to_plane(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                      size_t dst_points, const icp_batch_item *items, size_t count, int k, size_t max_iter,
+                                      icp_pose *out, int *status, uint32_t *last_idx, uint32_t *inner_iters);
+int icp_batch_estimate_point_to_plane_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                             size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                             size_t max_iter, icp_pose *out, int *status, uint32_t *d_last_idx,
+                                             uint32_t *inner_iters);
 
 #ifdef __cplusplus
 }

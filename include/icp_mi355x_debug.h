@@ -116,6 +116,16 @@ int icp_batch_line_quality_counters(icp_batch *b, uint64_t out[4]);
  * icp_estimate_point_to_line_gated_device (outside the limits, handed back by their workgroup, or no LDS grant), out[2]
  * batch launches, out[3] launches not made because the runtime refused the kernels their LDS. */
 int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]);
+/* ... and of icp_batch_estimate_point_to_plane[_device] (icp_mi355x.h section 18): out[0] items served inside a batch
+ * launch, out[1] items served one by one through icp_create_device + icp_compute_target_normals +
+ * icp_estimate_point_to_plane_device (outside the limits, handed back by their workgroup, or no LDS grant), out[2] batch
+ * launches, out[3] launches not made because the runtime refused the kernels their LDS. */
+int icp_batch_plane_counters(icp_batch *b, uint64_t out[4]);
+/* The LDS plan of a launch of section 18's kernel for workgroups of `threads` (512 or 1024)
+ * threads whose items have at most m targets (1 .. 2048): out[0] targets whose neighbour lists one round of the normals
+ * holds, out[1] bytes of the region the sort keys, the lists and the sort buffers use in turn, out[2] bytes beside it,
+ * out[3] dynamic LDS of the launch (out[1] + out[2]).  Host arithmetic: no device use. */
+int icp_debug_plane_batch_plan(unsigned threads, unsigned m, uint32_t out[4]);
 
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
