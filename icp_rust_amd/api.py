@@ -1272,22 +1272,36 @@ class IcpBatch:
         if self.DIM != 3:
             raise ValueError(f"{what} needs a 3-D batch (IcpBatch(3)): the plane residual is for 3-D clouds")
 
-    def estimate_point_to_plane(self, srcs, dsts, inits, max_iter, k=10, return_info=False, allow_failures=False):
+    def estimate_point_to_plane(self, srcs, dsts, inits, max_iter, k=10, return_info=False, allow_failures=False,
+                                max_correspondence_distance=None):
         """estimate() with the point-to-plane residual: item i is what Icp3d(dsts[i]) returns after compute_normals(k)
         from estimate_point_to_plane(srcs[i], inits[i], max_iter), bit for bit; items of up to 1024 source and 2048
-        target points run as one workgroup each (normals included), the others one by one."""
+        target points run as one workgroup each (normals included), the others one by one.
+
+        `max_correspondence_distance=r` (icp_batch_estimate_point_to_plane_gated*, section 19): item i is what that
+        single call returns with the same r -- the inner loop of each outer iteration sees only the pairs within r (3-D
+        distance); `return_info` then returns (Ts, idxs, inner, status, inliers), inliers count x max_iter.  None: the
+        ungated call."""
         self._need_3d("estimate_point_to_plane")
         src, dst, items = self._pack_items(srcs, dsts, inits)
-        return self.estimate_point_to_plane_packed(src, dst, items, max_iter, k, return_info, allow_failures)
+        return self.estimate_point_to_plane_packed(src, dst, items, max_iter, k, return_info, allow_failures,
+                                                   max_correspondence_distance)
 
-    def estimate_point_to_plane_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False):
+    def estimate_point_to_plane_packed(self, src, dst, items, max_iter, k=10, return_info=False, allow_failures=False,
+                                       max_correspondence_distance=None):
         """The same over pre-packed clouds (`items` as for estimate_packed; K hypotheses share one src and one dst range).
-        numpy arrays go through icp_batch_estimate_point_to_plane; contiguous float64 CUDA tensors through
-        icp_batch_estimate_point_to_plane_device, in place."""
+        numpy arrays go through icp_batch_estimate_point_to_plane[_gated]; contiguous float64 CUDA tensors through
+        icp_batch_estimate_point_to_plane[_gated]_device, in place."""
         self._need_3d("estimate_point_to_plane_packed")
         if not 3 <= int(k) <= 16:
             raise ValueError(f"k must be in [3, 16], got {k!r}")
-        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), None,
+        r = None
+        if max_correspondence_distance is not None:
+            r = float(max_correspondence_distance)
+            if not r >= 0.0:  # (also a NaN)
+                raise ValueError(
+                    f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), r,
                                      "icp_batch_estimate_point_to_plane")
 
     def plane_counters(self):
@@ -1295,6 +1309,13 @@ class IcpBatch:
         estimate_point_to_plane*"""
         out = (C.c_uint64 * 4)()
         check(lib().icp_batch_plane_counters(self._b, out), "icp_batch_plane_counters")
+        return tuple(int(x) for x in out)
+
+    def plane_gated_counters(self):
+        """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
+        estimate_point_to_plane*(..., max_correspondence_distance=r)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_plane_gated_counters(self._b, out), "icp_batch_plane_gated_counters")
         return tuple(int(x) for x in out)
 
     def line_counters(self):

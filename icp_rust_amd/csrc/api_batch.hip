@@ -12,6 +12,8 @@
 // Section 18, section 8's call with the point-to-plane residual for 3-D batches: k_plane_estimate_batch
 // (p2plane_batch.hip), one workgroup per item in at most two launches; one by one: icp_create_device +
 // icp_compute_target_normals + icp_estimate_point_to_plane_device.
+// Section 19, section 18 with a maximum correspondence distance: k_plane_estimate_gated_batch, driven the same way; one
+// by one: icp_estimate_point_to_plane_gated_device in the last step's place.
 #include <cstring>
 #include <initializer_list>
 #include <new>
@@ -40,10 +42,11 @@ struct icp_batch {
   size_t cap_inner = 0;
   uint64_t ctr[4] = {0, 0, 0, 0};  // icp_batch_counters
   uint64_t lctr[4] = {0, 0, 0, 0};  // icp_batch_line_counters
-  uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (section 17)
+  uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (sections 17 and 19)
   size_t cap_inl = 0;
   uint64_t lgctr[4] = {0, 0, 0, 0};  // icp_batch_line_gated_counters
   uint64_t pctr[4] = {0, 0, 0, 0};   // icp_batch_plane_counters
+  uint64_t pgctr[4] = {0, 0, 0, 0};  // icp_batch_plane_gated_counters
   // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
   QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
   size_t cap_qitems = 0, cap_h_qitems = 0;
@@ -128,7 +131,7 @@ int with_pool_handle(icp_batch *b, const double *d_src, const double *d_dst, con
 // The residual of an estimate call: line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line
 // residual, normals from line_k neighbours); gated on top (section 17): the pairs within max_dist, their counts per
 // outer iteration to `inliers` (count x max_iter, or null); plane_k > 0 (and line_k == 0): section 18 (the plane residual
-// of a 3-D batch, normals from plane_k neighbours).
+// of a 3-D batch, normals from plane_k neighbours); plane_k > 0 && gated: section 19 (section 18 with the gate).
 struct Residual {
   int line_k = 0;
   bool gated = false;
@@ -139,14 +142,18 @@ struct Residual {
 
 // icp_estimate_device on the item's handle; line_k > 0: the handle's line normals from line_k neighbours, then
 // icp_estimate_point_to_line_device, or (gated) icp_estimate_point_to_line_gated_device; inl: the item's inlier counts;
-// plane_k > 0: the handle's plane normals from plane_k neighbours, then icp_estimate_point_to_plane_device.  The first
-// failing step gives the item's status (ICP_BAD_ARGUMENT: targets the normals refuse, as section 16's one-by-one server).
+// plane_k > 0: the handle's plane normals from plane_k neighbours, then icp_estimate_point_to_plane_device, or (gated)
+// icp_estimate_point_to_plane_gated_device.  The first failing step gives the item's status (ICP_BAD_ARGUMENT: targets
+// the normals refuse, as section 16's one-by-one server).
 int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter,
               const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner, uint32_t *inl) {
   if (res.plane_k > 0)
     return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_EMPTY_DST, ICP_NAN_INPUT, ICP_BAD_ARGUMENT}, status,
                             [&](icp_handle *h, const double *s) {
                               ICP_TRY_RC(icp_compute_target_normals(h, res.plane_k));
+                              if (res.gated)
+                                return icp_estimate_point_to_plane_gated_device(h, s, (size_t)it.n, &it.init, max_iter,
+                                                                                res.max_dist, out, d_idx, inner, inl);
                               return icp_estimate_point_to_plane_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx,
                                                                         inner);
                             });
@@ -166,7 +173,7 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
         size_t max_iter, const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
   const int line_k = res.line_k, plane_k = res.plane_k;
   uint32_t *inliers = res.gated ? res.inliers : nullptr;
-  uint64_t *ctr = plane_k > 0 ? b->pctr : (res.gated ? b->lgctr : (line_k > 0 ? b->lctr : b->ctr));
+  uint64_t *ctr = plane_k > 0 ? (res.gated ? b->pgctr : b->pctr) : (res.gated ? b->lgctr : (line_k > 0 ? b->lctr : b->ctr));
   // where each item's indices go, and which items a workgroup may serve, by workgroup size
   std::vector<uint64_t> idx_first(count);
   std::vector<size_t> cls[3], one_by_one;
@@ -214,7 +221,12 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
     bool granted = true;
     for (int c = 0; c < 3; ++c) {
       if (cls[c].empty()) continue;
-      if (plane_k > 0)
+      if (plane_k > 0 && res.gated)  // (max_dist * max_dist in f64 on the host, as icp_p2pl_gated_inner_loop_device forms it)
+        HIP_TRY(launch_plane_estimate_gated_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
+                                                  (unsigned)cls[c].size(), (unsigned)max_iter, plane_k,
+                                                  res.max_dist * res.max_dist, b->h_res, inner_iters ? b->h_inner : nullptr,
+                                                  d_idx, inliers ? b->h_inl : nullptr, b->stream, &granted));
+      else if (plane_k > 0)
         HIP_TRY(launch_plane_estimate_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
                                             (unsigned)cls[c].size(), (unsigned)max_iter, plane_k, b->h_res,
                                             inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
@@ -458,6 +470,55 @@ extern "C" int icp_batch_estimate_point_to_plane(icp_batch *b, const double *src
   if (!plane_args_ok(b, k)) return ICP_BAD_ARGUMENT;
   return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, plane_residual_of(k), out, status,
                        last_idx, inner_iters);
+}
+
+// ---- section 19: section 18's entries with a maximum correspondence distance (max_dist >= 0, or +inf) ----
+namespace {
+Residual plane_gated_residual_of(int k, double max_dist, uint32_t *inliers) {
+  Residual res;
+  res.plane_k = k;
+  res.gated = true;
+  res.max_dist = max_dist;
+  res.inliers = inliers;
+  return res;
+}
+}  // namespace
+
+extern "C" int icp_batch_estimate_point_to_plane_gated_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                              const double *d_dst, size_t dst_points,
+                                                              const icp_batch_item *items, size_t count, int k,
+                                                              size_t max_iter, double max_dist, icp_pose *out, int *status,
+                                                              uint32_t *d_last_idx, uint32_t *inner_iters,
+                                                              uint32_t *inliers) {
+  if (!plane_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                         plane_gated_residual_of(k, max_dist, inliers), out, status, d_last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_estimate_point_to_plane_gated(icp_batch *b, const double *src, size_t src_points,
+                                                       const double *dst, size_t dst_points, const icp_batch_item *items,
+                                                       size_t count, int k, size_t max_iter, double max_dist, icp_pose *out,
+                                                       int *status, uint32_t *last_idx, uint32_t *inner_iters,
+                                                       uint32_t *inliers) {
+  if (!plane_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter,
+                       plane_gated_residual_of(k, max_dist, inliers), out, status, last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_plane_gated_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->pgctr[q];
+  return ICP_OK;
+}
+
+extern "C" int icp_debug_plane_gated_batch_plan(unsigned threads, unsigned m, uint32_t out[4]) {
+  if (!out || (threads != 512u && threads != 1024u) || m < 1 || m > kPlaneBatchMaxM) return ICP_BAD_ARGUMENT;
+  const PlanePlan plan = plane_gated_batch_plan_of(threads, m);
+  out[0] = plan.list_threads;
+  out[1] = plan.shared_bytes;
+  out[2] = plan.fixed_bytes;
+  out[3] = plan.lds_bytes;
+  return ICP_OK;
 }
 
 extern "C" int icp_batch_plane_counters(icp_batch *b, uint64_t out[4]) {

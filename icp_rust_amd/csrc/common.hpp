@@ -569,6 +569,14 @@ struct PlanePlan {
   unsigned list_threads, shared_bytes, fixed_bytes, lds_bytes;
 };
 PlanePlan plane_batch_plan_of(unsigned threads, unsigned m_max);
+// EXTENSION: the same with a maximum correspondence distance (k_plane_estimate_gated_batch): r2 =
+// max_dist^2, formed in f64 by the caller; inliers: count x max_iter kept counts (pinned host memory, or null), laid out
+// like `inner`.  Its plan: the ungated one with the gate's words behind the sort buffers.
+hipError_t launch_plane_estimate_gated_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                             const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                             double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
+                                             uint32_t *inliers, hipStream_t stream, bool *granted);
+PlanePlan plane_gated_batch_plan_of(unsigned threads, unsigned m_max);
 // A record of the fold tree of section 9 (fold_device.hpp): SUMS sums that are doubles, the inlier count and whether some
 // residual was NaN.
 template <int SUMS>

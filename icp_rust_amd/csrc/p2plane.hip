@@ -65,6 +65,10 @@ __global__ __launch_bounds__(64) void k_target_normals(const double *__restrict_
           const double dx = p[0] - dst[(size_t)ti * 3], dy = p[1] - dst[(size_t)ti * 3 + 1],
                        dz = p[2] - dst[(size_t)ti * 3 + 2];
           const double dd = (dx * dx + dy * dy) + dz * dz;
+          // A NaN distance (a NaN coordinate in either target) is no neighbour: (d^2, index) does not order it, and a
+          // list that took it in would depend on the order of the records inside a cell, which the grid's scatter
+          // leaves to its atomics -- the normals of such a cloud would differ from one handle to the next.
+          if (dd != dd) continue;
           // insertion by (d^2, index) into the k best
           if (cnt == k && !(dd < bd[k - 1] || (dd == bd[k - 1] && ti < bi[k - 1]))) continue;
           int pos = cnt < k ? cnt : k - 1;

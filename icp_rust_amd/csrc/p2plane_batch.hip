@@ -15,6 +15,10 @@
 //              the tree of reduce_geometry(n), solve_update and the break tests; then tiny_outer_tail
 // Hand-back reasons: a box that is not finite; a NaN target coordinate; a rotation update outside the restated range of
 // sin / cos.  A NaN residual is the item's ICP_NAN_INPUT.
+// Section 19, k_plane_estimate_gated_batch: the same body (plane_estimate_item) with the gate of
+// icp_estimate_point_to_plane_gated between the search and the inner loop -- the pairs with d2 <= r^2 (gate_plane.hip:
+// k_plgate_stage's expressions, d2 = (ex ex + ey ey) + dz dz), compacted in thread order, and p2pl_loop_on_pairs on the
+// `kept` of them in the tree of reduce_geometry(kept).
 #include "common.hpp"
 #include "gn_device.hpp"
 #include "p2plane_device.hpp"
@@ -81,6 +85,83 @@ static_assert(plane_batch_plan_fits_everywhere(), "every launch's LDS is within 
 
 PlanePlan plane_batch_plan_of(unsigned threads, unsigned m_max) { return plane_batch_plan(threads, m_max); }
 
+// ---- the gate's words (section 19) ----
+// Behind the estimator's three sort buffers in the shared region, which the normals' lists have left by then: ONE word
+// per kept pair, in pair order -- (source thread << 16) | sorted position of its match, both below 2^16 -- and the 16 wave
+// counts.  The moved point is not kept: thread t reads the source row of pair t again and forms qx, qy with the
+// expression and the pose the gate formed them with.  The record the line kernel keeps (x | y as f64 and the position,
+// with z 28 B a pair: plane_gate_line_style_bytes) does not fit behind the sort buffers beyond 1664 targets.
+constexpr size_t plane_gate_bytes(unsigned threads) {
+  return (size_t)threads * sizeof(uint32_t) + 16 * sizeof(uint32_t);
+}
+constexpr size_t plane_gate_line_style_bytes(unsigned threads) {
+  return (size_t)threads * (3 * sizeof(double) + sizeof(uint32_t)) + 16 * sizeof(uint32_t);
+}
+static_assert(kPlaneBatchMaxN <= 0x10000u && kPlaneBatchMaxM <= 0x10000u,
+              "a source thread and a sorted position in 16 bits each");
+constexpr PlanePlan plane_gated_batch_plan(unsigned threads, unsigned m_max) {
+  PlanePlan plan = plane_batch_plan(threads, m_max);  // (the same rounds of the normals: the lists decide them)
+  const size_t need = (size_t)3 * threads * 8 + plane_gate_bytes(threads);
+  if (plan.shared_bytes < need) {
+    plan.lds_bytes += (unsigned)(need - plan.shared_bytes);
+    plan.shared_bytes = (unsigned)need;
+  }
+  return plan;
+}
+PlanePlan plane_gated_batch_plan_of(unsigned threads, unsigned m_max) { return plane_gated_batch_plan(threads, m_max); }
+// the plan at its corners
+static_assert(plane_gate_bytes(512) == 2112 && plane_gate_bytes(1024) == 4160 &&
+                  plane_gate_line_style_bytes(512) == 14400 && plane_gate_line_style_bytes(1024) == 28736,
+              "the gate's words, and what the line kernel's record would take");
+// (what a 1024-thread workgroup of m targets would need with the line kernel's record behind its sort buffers)
+constexpr size_t plane_line_style_lds(unsigned m) {
+  return plane_fixed_bytes(m) + 3 * 1024 * 8 + plane_gate_line_style_bytes(1024);
+}
+static_assert(plane_gated_batch_plan(512, 1).list_threads == 64 && plane_gated_batch_plan(1024, 1).list_threads == 64 &&
+                  plane_gated_batch_plan(512, 1).shared_bytes == 3 * 512 * 8 + 2112 &&
+                  plane_gated_batch_plan(1024, 1).shared_bytes == 3 * 1024 * 8 + 4160 &&
+                  plane_gated_batch_plan(512, 1).lds_bytes == 6208 + 14400 &&
+                  plane_gated_batch_plan(1024, 1).lds_bytes == 6208 + 28736,
+              "m = 1: the sort buffers and the gate's words");
+static_assert(plane_gated_batch_plan(512, 1024).list_threads == 448 &&
+                  plane_gated_batch_plan(1024, 1024).list_threads == 448 &&
+                  plane_gated_batch_plan(512, 1024).lds_bytes == plane_batch_plan(512, 1024).lds_bytes &&
+                  plane_gated_batch_plan(1024, 1024).lds_bytes == 67648 + 448 * 192,
+              "m = 1024: the gate's words lie where the lists were");
+static_assert(plane_fixed_bytes(1664) == 108608 && plane_line_style_lds(1664) == 161920 &&
+                  plane_line_style_lds(1664) <= kTinyLdsGrant && plane_gated_batch_plan(512, 1664).list_threads == 256 &&
+                  plane_gated_batch_plan(1024, 1664).list_threads == 256 &&
+                  plane_gated_batch_plan(512, 1664).lds_bytes == 108608 + 256 * 192 &&
+                  plane_gated_batch_plan(1024, 1664).lds_bytes == 108608 + 256 * 192,
+              "m = 1664: the last m at which the line kernel's record would still fit; nothing on top of the ungated plan");
+static_assert(plane_fixed_bytes(1665) == 112704 && plane_line_style_lds(1665) > kTinyLdsGrant &&
+                  plane_gated_batch_plan(512, 1665).list_threads == 256 &&
+                  plane_gated_batch_plan(1024, 1665).list_threads == 256 &&
+                  plane_gated_batch_plan(512, 1665).lds_bytes == 112704 + 256 * 192 &&
+                  plane_gated_batch_plan(1024, 1665).lds_bytes == 161856,
+              "m = 1665: the line kernel's record overflows the grant, the one word per pair does not");
+static_assert(plane_gated_batch_plan(512, kPlaneBatchMaxM).list_threads == 128 &&
+                  plane_gated_batch_plan(1024, kPlaneBatchMaxM).list_threads == 128 &&
+                  plane_gated_batch_plan(512, kPlaneBatchMaxM).lds_bytes == 157760 &&
+                  plane_gated_batch_plan(1024, kPlaneBatchMaxM).shared_bytes == 3 * 1024 * 8 + 4160 &&
+                  plane_gated_batch_plan(1024, kPlaneBatchMaxM).shared_bytes <= 30400 &&
+                  plane_gated_batch_plan(1024, kPlaneBatchMaxM).lds_bytes == 133184 + 28736 &&
+                  plane_gated_batch_plan(1024, kPlaneBatchMaxM).lds_bytes <= kTinyLdsGrant,
+              "m = 2048: 28 736 of the 30 400 bytes the fixed part leaves");
+// ... and at every m between: within the grant, and the rounds of the normals those of the ungated plan
+constexpr bool plane_gated_batch_plan_fits_everywhere() {
+  for (unsigned m = 1; m <= kPlaneBatchMaxM; ++m)
+    for (unsigned threads = 512; threads <= 1024; threads += 512) {
+      const PlanePlan plan = plane_gated_batch_plan(threads, m);
+      if (plan.list_threads < 64 || plan.list_threads > threads || plan.lds_bytes > kTinyLdsGrant) return false;
+      if (plan.list_threads != plane_batch_plan(threads, m).list_threads) return false;
+      if (plan.shared_bytes < 3 * threads * 8 + plane_gate_bytes(threads)) return false;
+      if (plan.lds_bytes != plan.fixed_bytes + plan.shared_bytes) return false;
+    }
+  return true;
+}
+static_assert(plane_gated_batch_plan_fits_everywhere(), "every gated launch's LDS is within the grant");
+
 // ---- the plane normals of a workgroup's own targets ----
 // Per target the k best by (d^2, index) (tiny_k_best_of_target<3>), L targets per round with their lists in `shared`
 // (kPlaneListBytes x L, free again on return), then plane_normal_of_neighbours -> nrm[3 x sorted position].  kk: the
@@ -112,12 +193,13 @@ __device__ __forceinline__ void plane_normals_of_sorted_targets(const TinyTarget
   __syncthreads();
 }
 
-template <unsigned B>
-__global__ __launch_bounds__(B) void k_plane_estimate_batch(const double *__restrict__ src_all,
-                                                            const double *__restrict__ dst_all,
-                                                            const TinyBatchItem *__restrict__ items, unsigned max_iter,
-                                                            int kk, unsigned L, unsigned shared_bytes, TinyResult *res_all,
-                                                            uint32_t *inner_all, uint32_t *idx_all) {
+// One item of a batch, by the workgroup's B threads: what both kernels below run.  GATED: the gate between the search and
+// the inner loop; r2, inl_all: the squared bound and the inlier counts (count x max_iter, or null).
+template <unsigned B, bool GATED>
+__device__ __forceinline__ void plane_estimate_item(const double *__restrict__ src_all, const double *__restrict__ dst_all,
+                                                    const TinyBatchItem *__restrict__ items, unsigned max_iter, int kk,
+                                                    unsigned L, unsigned shared_bytes, TinyResult *res_all,
+                                                    uint32_t *inner_all, uint32_t *idx_all, double r2, uint32_t *inl_all) {
   static_assert(B == 512 || B == 1024, "one or two blocks of the 512-thread fold tree, a power of two for the sort");
   extern __shared__ unsigned char lds_raw[];
   const TinyBatchItem &item = items[blockIdx.x];  // (read in place: a copy of the pose would live in scratch)
@@ -183,36 +265,99 @@ __global__ __launch_bounds__(B) void k_plane_estimate_batch(const double *__rest
     py = src[(size_t)tid * 3 + 1];
     pz = src[(size_t)tid * 3 + 2];
   }
-  const int blocks = n > 512u ? 2 : 1;  // reduce_geometry(n) for n <= 1024: 512-thread blocks
+  // the pairs the inner loop sees: all n, thread t its own; gated: the kept ones, thread t the t-th of them
+  unsigned cnt = n;
+  bool hasp = has;
+  int blocks = n > 512u ? 2 : 1;  // reduce_geometry(cnt) for cnt <= 1024: 512-thread blocks
+  // the gate's words, behind the sort buffers (plane_gated_batch_plan)
+  uint32_t *gw = reinterpret_cast<uint32_t *>(shared + (size_t)3 * B * 8), *gcnt = gw + B;
+  uint32_t *inl_out = GATED && inl_all ? inl_all + (size_t)item.slot * max_iter : nullptr;
   unsigned bi = 0xffffffffu;
   for (unsigned it = 0; it < max_iter; ++it) {
     const Pose T = C->T;
     // ---- transform + exact nearest neighbour, the pair of k_p2pl_gather ----
     PlanePair pr;
     pr.ax = pr.ay = pr.qx = pr.qy = pr.dz = pr.nx = pr.ny = pr.nz = 0.;
+    unsigned nb = 0;  // sorted position of the nearest target
+    bool in = false;  // (gated) the pair passes the gate
     if (has) {
       const double qx = (T.r00 * px + T.r01 * py) + T.tx;  // Transform::transform, src/transform.rs:22-24; z is carried
       const double qy = (T.r10 * px + T.r11 * py) + T.ty;
-      unsigned nb, nbo;  // sorted position / original index of the nearest target
+      unsigned nbo;  // original index of the nearest target
       tiny_nearest<3>(tg, qx, qy, pz, cx, cy, cz, scale, bi, &nb, &nbo);
       bi = nb;
       if (nb == 0xffffffffu) {  // no finite distance (NaN query): index 0, as a scan from 0 would
         nb = C->pos0;
         nbo = 0;
       }
-      pr.ax = qx;
-      pr.ay = qy;
-      pr.qx = tx[nb];
-      pr.qy = ty[nb];
-      pr.dz = pz - tz[nb];
-      pr.nx = nrm[3 * nb];
-      pr.ny = nrm[3 * nb + 1];
-      pr.nz = nrm[3 * nb + 2];
+      if constexpr (GATED) {  // k_plgate_stage's expressions
+        const double ex = qx - tx[nb], ey = qy - ty[nb], dz = pz - tz[nb];
+        const double d2 = (ex * ex + ey * ey) + dz * dz;
+        in = d2 <= r2;  // (false for a NaN d2)
+      } else {
+        pr.ax = qx;
+        pr.ay = qy;
+        pr.qx = tx[nb];
+        pr.qy = ty[nb];
+        pr.dz = pz - tz[nb];
+        pr.nx = nrm[3 * nb];
+        pr.ny = nrm[3 * nb + 1];
+        pr.nz = nrm[3 * nb + 2];
+      }
       if (idx_out && it + 1 == max_iter) idx_out[tid] = nbo;
     }
-    // ---- p2pl_loop_on_pairs (api_ext.hip) on the n pairs ----
-    tiny_pair_loop<B>(pr, has, n, blocks, C, sbuf, sm, tot, []() {});
-    if (tid == 0) tiny_outer_tail(C, it, max_iter, inner_out);
+    if constexpr (GATED) {
+      // ---- the gate: the kept pairs in thread order (stable), pair t to thread t ----
+      // rank = kept lanes before this one in its wave + the counts of the waves before it; the kept lanes of a wave
+      // write consecutive words
+      const int wave = tid >> 6;
+      const unsigned long long bal = __ballot(in);
+      unsigned rank = (unsigned)__popcll(bal & ((1ull << (tid & 63)) - 1ull));
+      if ((tid & 63) == 0) gcnt[wave] = (unsigned)__popcll(bal);
+      __syncthreads();
+      unsigned kept = 0;
+#pragma unroll
+      for (int w = 0; w < (int)(B / 64); ++w) {
+        const unsigned c = gcnt[w];
+        rank += w < wave ? c : 0u;
+        kept += c;
+      }
+      if (in) gw[rank] = (tid << 16) | nb;  // (rank < kept <= n <= B; tid < 1024 and nb < m <= 2048: 16 bits each)
+      cnt = (unsigned)__builtin_amdgcn_readfirstlane((int)kept);  // (the same in every thread)
+      hasp = tid < cnt;
+      blocks = cnt > 512u ? 2 : 1;
+    }
+    // ---- p2pl_loop_on_pairs (api_ext.hip) on the cnt pairs (pair_loop_device.hpp) ----
+    tiny_pair_loop<B>(pr, hasp, cnt, blocks, C, sbuf, sm, tot, [&]() {
+      if constexpr (GATED) {
+        // pair t: its source row read again and moved by the pose the gate moved it by (C->T: thread 0 writes it next in
+        // tiny_outer_tail, behind the loop) -- the same expressions, the same bits; the eight values k_plgate_stage writes
+        if (hasp) {
+          const unsigned w = gw[tid], s = w >> 16, g = w & 0xffffu;  // (s < n, g < m: written by the gate above)
+          const double sx = src[(size_t)s * 3], sy = src[(size_t)s * 3 + 1], sz = src[(size_t)s * 3 + 2];
+          const Pose G = C->T;
+          pr.ax = (G.r00 * sx + G.r01 * sy) + G.tx;
+          pr.ay = (G.r10 * sx + G.r11 * sy) + G.ty;
+          pr.qx = tx[g];
+          pr.qy = ty[g];
+          pr.dz = sz - tz[g];
+          pr.nx = nrm[3 * g];
+          pr.ny = nrm[3 * g + 1];
+          pr.nz = nrm[3 * g + 2];
+        }
+      }
+    });
+    if (tid == 0) {
+      tiny_outer_tail(C, it, max_iter, inner_out);
+      if constexpr (GATED) {
+        // the iterations a fixed point skips repeat this one's search and gate: this one's count is theirs
+        if (inl_out) {
+          inl_out[it] = cnt;
+          if (C->fixed && it + 2 < max_iter)
+            for (unsigned k = it + 1; k + 1 < max_iter; ++k) inl_out[k] = cnt;
+        }
+      }
+    }
     __syncthreads();
     if (C->nan | C->bail) break;
     if (C->fixed && it + 2 < max_iter) it = max_iter - 2;  // (uniform: the flag is the workgroup's)
@@ -223,6 +368,28 @@ __global__ __launch_bounds__(B) void k_plane_estimate_batch(const double *__rest
     res->sorted = C->evals;
     res->status = C->nan ? 3 : (C->bail ? -1 : 0);
   }
+}
+
+template <unsigned B>
+__global__ __launch_bounds__(B) void k_plane_estimate_batch(const double *__restrict__ src_all,
+                                                            const double *__restrict__ dst_all,
+                                                            const TinyBatchItem *__restrict__ items, unsigned max_iter,
+                                                            int kk, unsigned L, unsigned shared_bytes, TinyResult *res_all,
+                                                            uint32_t *inner_all, uint32_t *idx_all) {
+  plane_estimate_item<B, false>(src_all, dst_all, items, max_iter, kk, L, shared_bytes, res_all, inner_all, idx_all, 0.,
+                                nullptr);
+}
+
+// section 19: r2 = max_dist^2; inl_all: count x max_iter inlier counts, or null
+template <unsigned B>
+__global__ __launch_bounds__(B) void k_plane_estimate_gated_batch(const double *__restrict__ src_all,
+                                                                  const double *__restrict__ dst_all,
+                                                                  const TinyBatchItem *__restrict__ items, unsigned max_iter,
+                                                                  int kk, unsigned L, unsigned shared_bytes, double r2,
+                                                                  TinyResult *res_all, uint32_t *inner_all,
+                                                                  uint32_t *idx_all, uint32_t *inl_all) {
+  plane_estimate_item<B, true>(src_all, dst_all, items, max_iter, kk, L, shared_bytes, res_all, inner_all, idx_all, r2,
+                               inl_all);
 }
 
 hipError_t launch_plane_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
@@ -241,6 +408,25 @@ hipError_t launch_plane_estimate_batch(unsigned threads, unsigned m_max, const d
   else
     hipLaunchKernelGGL((k_plane_estimate_batch<1024>), dim3(count), dim3(1024), plan.lds_bytes, stream, d_src, d_dst,
                        d_items, max_iter, k, plan.list_threads, plan.shared_bytes, res, inner, d_idx);
+  return hipGetLastError();
+}
+
+hipError_t launch_plane_estimate_gated_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                             const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
+                                             double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
+                                             uint32_t *inliers, hipStream_t stream, bool *granted) {
+  static TinyLdsGrant grant;  // (these kernels' own: refused, nothing launches)
+  *granted = grant.ask({reinterpret_cast<const void *>(&k_plane_estimate_gated_batch<512>),
+                        reinterpret_cast<const void *>(&k_plane_estimate_gated_batch<1024>)},
+                       kTinyLdsGrant);
+  if (!*granted || count == 0) return hipSuccess;
+  const PlanePlan plan = plane_gated_batch_plan(threads, m_max);
+  if (threads == 512u)
+    hipLaunchKernelGGL((k_plane_estimate_gated_batch<512>), dim3(count), dim3(512), plan.lds_bytes, stream, d_src, d_dst,
+                       d_items, max_iter, k, plan.list_threads, plan.shared_bytes, r2, res, inner, d_idx, inliers);
+  else
+    hipLaunchKernelGGL((k_plane_estimate_gated_batch<1024>), dim3(count), dim3(1024), plan.lds_bytes, stream, d_src, d_dst,
+                       d_items, max_iter, k, plan.list_threads, plan.shared_bytes, r2, res, inner, d_idx, inliers);
   return hipGetLastError();
 }
 

@@ -69,7 +69,8 @@ extern "C" {
  * icp_mi355x_debug.h); so was section 16 (icp_line_quality, icp_evaluate_point_to_line*,
  * icp_batch_evaluate_point_to_line*; icp_batch_line_quality_counters in icp_mi355x_debug.h); so was section 17
  * (icp_batch_estimate_point_to_line_gated*; icp_batch_line_gated_counters in icp_mi355x_debug.h); so was section 18
- * (icp_batch_estimate_point_to_plane*; icp_batch_plane_counters in icp_mi355x_debug.h) */
+ * (icp_batch_estimate_point_to_plane*; icp_batch_plane_counters in icp_mi355x_debug.h); so was section 19
+ * (icp_batch_estimate_point_to_plane_gated*; icp_batch_plane_gated_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -1006,6 +1007,33 @@ int icp_batch_estimate_point_to_plane_device(icp_batch *b, const double *d_src, 
                                              size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                              size_t max_iter, icp_pose *out, int *status, uint32_t *d_last_idx,
                                              uint32_t *inner_iters);
+
+/* ================================================================================
+ * 19. EXTENSION (not in the reference): section 18's call with a maximum correspondence distance
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  A submap patch with an object the map does not
+ * hold, a loop-closure candidate, a far hypothesis overlap their targets only partly: they need section 12's gate.  Item
+ * i's out[i], status[i], indices, inner counts and inlier counts are what icp_create(3, dst + 3 dst_first, m) +
+ * icp_compute_target_normals(k) + icp_estimate_point_to_plane_gated(src + 3 src_first, n, &init, max_iter, max_dist)
+ * return on a fresh handle, bit for bit: per outer iteration the inner loop sees only the pairs with
+ * d2 = (ex ex + ey ey) + dz dz <= max_dist * max_dist (no FMA; max_dist * max_dist in f64; a NaN d2 is never kept, so a
+ * NaN source point is gated out), in the caller's order.  Every item within section 18's limits runs as ONE workgroup
+ * (one launch per workgroup size, at most two); the other items, and those a workgroup hands back, go through exactly
+ * those three entries one after another.  An item is never approximated.  DESIGN.md section 9n.
+ * Arguments, ranges, last_idx (the search result of ALL n points in the last iteration), inner_iters, statuses and the
+ * return value are section 18's.  inliers: count * max_iter words, nullable, laid out like inner_iters: the number of
+ * kept pairs of each outer iteration.  In addition ICP_BAD_ARGUMENT for max_dist NaN or negative (+inf is allowed: every
+ * pair with a d2 that is not NaN is kept) -- checked, like every argument, before the device is touched.  count == 0 is a
+ * successful no-op. */
+int icp_batch_estimate_point_to_plane_gated(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                            size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                            size_t max_iter, double max_dist, icp_pose *out, int *status,
+                                            uint32_t *last_idx, uint32_t *inner_iters, uint32_t *inliers);
+int icp_batch_estimate_point_to_plane_gated_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                   const double *d_dst, size_t dst_points, const icp_batch_item *items,
+                                                   size_t count, int k, size_t max_iter, double max_dist, icp_pose *out,
+                                                   int *status, uint32_t *d_last_idx, uint32_t *inner_iters,
+                                                   uint32_t *inliers);
 
 #ifdef __cplusplus
 }

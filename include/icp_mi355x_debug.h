@@ -126,6 +126,15 @@ int icp_batch_plane_counters(icp_batch *b, uint64_t out[4]);
  * holds, out[1] bytes of the region the sort keys, the lists and the sort buffers use in turn, out[2] bytes beside it,
  * out[3] dynamic LDS of the launch (out[1] + out[2]).  Host arithmetic: no device use. */
 int icp_debug_plane_batch_plan(unsigned threads, unsigned m, uint32_t out[4]);
+/* ... and of icp_batch_estimate_point_to_plane_gated[_device] (icp_mi355x.h section 19): out[0] items served inside a
+ * batch launch, out[1] items served one by one through icp_create_device + icp_compute_target_normals +
+ * icp_estimate_point_to_plane_gated_device (outside the limits, handed back by their workgroup, or no LDS grant), out[2]
+ * batch launches, out[3] launches not made because the runtime refused the kernels their LDS. */
+int icp_batch_plane_gated_counters(icp_batch *b, uint64_t out[4]);
+/* The LDS plan of a launch of section 19's kernel, laid out as icp_debug_plane_batch_plan's: the
+ * same rounds of the normals (out[0]), and a shared region (out[1]) that also holds, behind the three sort buffers, one
+ * 4-byte word per thread and sixteen wave counts for the gate.  Host arithmetic: no device use. */
+int icp_debug_plane_gated_batch_plan(unsigned threads, unsigned m, uint32_t out[4]);
 
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
