@@ -262,6 +262,11 @@ SIGNATURES = {
                                                                  C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "icp_batch_plane_gated_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_debug_plane_gated_batch_plan": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_uint32)]),
+    "icp_batch_evaluate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp, _vp]),
+    "icp_batch_evaluate_point_to_plane_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp,
+                                                           _vp]),
+    "icp_batch_plane_quality_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_debug_plane_quality_batch_plan": (C.c_int, [C.c_uint, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

@@ -1351,7 +1351,8 @@ class IcpBatch:
                                      float(max_correspondence_distance), allow_failures, return_status)
 
     def _evaluate_packed(self, struct, wrap, symbol, src, dst, items, kargs, r, allow_failures, return_status):
-        """evaluate_packed and evaluate_point_to_line_packed (kargs: the normals' neighbours) behind their guards:
+        """evaluate_packed, evaluate_point_to_line_packed and evaluate_point_to_plane_packed (kargs: the normals'
+        neighbours) behind their guards:
         `symbol` (host arrays) or `symbol`_device (device tensors) fills one `struct` per item, returned as `wrap`s"""
         count = len(items)
         arr = (_lib.BatchItem * max(count, 1))()
@@ -1420,6 +1421,41 @@ class IcpBatch:
         evaluate_point_to_line*"""
         out = (C.c_uint64 * 4)()
         check(lib().icp_batch_line_quality_counters(self._b, out), "icp_batch_line_quality_counters")
+        return tuple(int(x) for x in out)
+
+    # -- the same under the point-to-plane residual for 3-D items (icp_batch_evaluate_point_to_plane*, section 20) --
+    def evaluate_point_to_plane(self, srcs, dsts, transforms, k=10, max_correspondence_distance=float("inf"),
+                                allow_failures=False, return_status=False):
+        """The PlaneQuality of transforms[i] for srcs[i] against dsts[i] (a list, one Transform for all, or None:
+        identity): item i equals what Icp3d(dsts[i]) returns after compute_normals(k) from
+        evaluate_point_to_plane(srcs[i], transforms[i], max_correspondence_distance), bit for bit; items of up to 1024
+        source and 2048 target points run as one workgroup each of a single launch (normals included), the others one
+        by one.  A failed item raises IcpError naming it, unless allow_failures=True (its PlaneQuality is then None);
+        return_status=True also returns the statuses."""
+        self._need_3d("evaluate_point_to_plane")
+        src, dst, items = self._pack_items(srcs, dsts, transforms)
+        return self.evaluate_point_to_plane_packed(src, dst, items, k, max_correspondence_distance, allow_failures,
+                                                   return_status)
+
+    def evaluate_point_to_plane_packed(self, src, dst, items, k=10, max_correspondence_distance=float("inf"),
+                                       allow_failures=False, return_status=False):
+        """The same over pre-packed clouds (`items` as for evaluate_packed; K hypotheses share one src and one dst
+        range).  numpy arrays go through icp_batch_evaluate_point_to_plane; contiguous float64 CUDA tensors through
+        icp_batch_evaluate_point_to_plane_device, in place."""
+        self._need_3d("evaluate_point_to_plane_packed")
+        if not 3 <= int(k) <= 16:
+            raise ValueError(f"k must be in [3, 16], got {k!r}")
+        r = float(max_correspondence_distance)
+        if not r >= 0.0:  # (also a NaN)
+            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
+        return self._evaluate_packed(_lib.PlaneQualityStruct, PlaneQuality, "icp_batch_evaluate_point_to_plane", src, dst,
+                                     items, [int(k)], r, allow_failures, return_status)
+
+    def plane_quality_counters(self):
+        """(items scored in a batch launch, items scored one by one, launches, launches not made for want of LDS) of
+        evaluate_point_to_plane*"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_plane_quality_counters(self._b, out), "icp_batch_plane_quality_counters")
         return tuple(int(x) for x in out)
 
     def evaluate_counters(self):

@@ -9,6 +9,8 @@
 // one: icp_estimate_point_to_line_gated_device in the last step's place.
 // Sections 9 and 16, the quality of many poses: k_quality_batch (quality.hip) and, with the line residual,
 // k_line_quality_batch (quality_line.hip), one workgroup per item in one launch; one by one: the single calls.
+// Section 20, section 16's call with the point-to-plane residual for 3-D batches: k_plane_quality_batch
+// (quality_plane_batch.hip), through the driver section 16 runs on.
 // Section 18, section 8's call with the point-to-plane residual for 3-D batches: k_plane_estimate_batch
 // (p2plane_batch.hip), one workgroup per item in at most two launches; one by one: icp_create_device +
 // icp_compute_target_normals + icp_estimate_point_to_plane_device.
@@ -53,10 +55,11 @@ struct icp_batch {
   QualityPart *h_qres = nullptr;
   size_t cap_qres = 0;
   uint64_t qctr[3] = {0, 0, 0};  // icp_batch_evaluate_counters
-  // icp_batch_evaluate_point_to_line (section 16): the item list above, and its own records (pinned)
-  LineQualityPart *h_lqres = nullptr;
-  size_t cap_lqres = 0;
+  // icp_batch_evaluate_point_to_line / _plane (sections 16 and 20): the item list above, and their own records (pinned)
+  NormalQualityPart *h_nqres = nullptr;
+  size_t cap_nqres = 0;
   uint64_t lqctr[4] = {0, 0, 0, 0};  // icp_batch_line_quality_counters
+  uint64_t pqctr[4] = {0, 0, 0, 0};  // icp_batch_plane_quality_counters
 };
 
 namespace {
@@ -323,7 +326,7 @@ extern "C" void icp_batch_destroy(icp_batch *b) {
     (void)hipFree(b->d_qitems);
     if (b->h_qitems) (void)hipHostFree(b->h_qitems);
     if (b->h_qres) (void)hipHostFree(b->h_qres);
-    if (b->h_lqres) (void)hipHostFree(b->h_lqres);
+    if (b->h_nqres) (void)hipHostFree(b->h_nqres);
     (void)hipStreamDestroy(b->stream);
   }
   delete b;
@@ -345,7 +348,7 @@ int estimate_device(icp_batch *b, const double *d_src, size_t src_points, const 
 }
 
 // the host entries' clouds, staged through the batch's buffers: *d_src / *d_dst are what run, run_quality
-// and run_line_quality read (null for an empty array)
+// and run_normal_quality read (null for an empty array)
 int stage_clouds(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
                  const double **d_src, const double **d_dst) {
   if (src_points > 0) {
@@ -653,63 +656,120 @@ extern "C" int icp_batch_evaluate_counters(icp_batch *b, uint64_t out[3]) {
   return ICP_OK;
 }
 
-// ---- icp_batch_evaluate_point_to_line (include/icp_mi355x.h section 16): the same with the point-to-line residual ----
-// The items that fit one workgroup run as k_line_quality_batch (quality_line.hip), one workgroup each, in one launch;
-// the rest, and those a workgroup hands back, go one by one through a handle of the pool: icp_create_device +
-// icp_compute_target_line_normals + icp_evaluate_point_to_line_device, exactly as single calls serve them.
+// ---- icp_batch_evaluate_point_to_line (include/icp_mi355x.h section 16) and icp_batch_evaluate_point_to_plane
+// (section 20): the same with the point-to-line residual of a 2-D batch, the point-to-plane residual of a 3-D batch ----
+// The items that fit one workgroup run as k_line_quality_batch (quality_line.hip) / k_plane_quality_batch
+// (quality_plane_batch.hip), one workgroup each, in one launch; the rest, and those a workgroup hands back, go one by
+// one through a handle of the pool: icp_create_device + the residual's normals + its single evaluation, exactly as
+// single calls serve them.  ONE driver and one pair of entries; what the two residuals differ in is a Kind below.
 namespace {
 
-bool line_quality_fits(const icp_batch_item &it) {
-  return it.n >= 1 && it.n <= kLineQualityMaxN && it.m >= 1 && it.m <= kLineQualityMaxM;
-}
+struct LineQualityKind {
+  using Q = icp_line_quality;
+  static constexpr int kDim = 2;
+  static bool fits(const icp_batch_item &it) {
+    return it.n >= 1 && it.n <= kLineQualityMaxN && it.m >= 1 && it.m <= kLineQualityMaxM;
+  }
+  static constexpr auto launch = launch_line_quality_batch;
+  static int result(size_t n, const NormalQualityPart &p, Q *q) { return line_quality_result(n, p, q); }
+  static int normals(icp_handle *h, int k) { return icp_compute_target_line_normals(h, k); }
+  static int evaluate(icp_handle *h, const double *s, size_t n, const icp_pose *T, double max_dist, Q *out) {
+    return icp_evaluate_point_to_line_device(h, s, n, T, max_dist, out, nullptr);
+  }
+  static uint64_t *counters(icp_batch *b) { return b->lqctr; }
+};
 
-// One by one: the first failing step's status is the item's -- ICP_EMPTY_DST and ICP_BAD_ARGUMENT (targets section 14
-// refuses) come from the normals, ICP_NAN_INPUT from the evaluation; *out then holds n and zeros.
-int serve_line_quality_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, int k,
-                           double max_dist, icp_line_quality *out, int *status) {
+struct PlaneQualityKind {
+  using Q = icp_plane_quality;
+  static constexpr int kDim = 3;
+  static bool fits(const icp_batch_item &it) {  // (plane_fits' limits: what section 18 serves in a launch, this does)
+    return it.n >= 1 && it.n <= kPlaneQualityMaxN && it.m >= 1 && it.m <= kPlaneQualityMaxM;
+  }
+  static constexpr auto launch = launch_plane_quality_batch;
+  static int result(size_t n, const NormalQualityPart &p, Q *q) { return plane_quality_result(n, p, q); }
+  static int normals(icp_handle *h, int k) { return icp_compute_target_normals(h, k); }
+  static int evaluate(icp_handle *h, const double *s, size_t n, const icp_pose *T, double max_dist, Q *out) {
+    return icp_evaluate_point_to_plane_device(h, s, n, T, max_dist, out, nullptr);
+  }
+  static uint64_t *counters(icp_batch *b) { return b->pqctr; }
+};
+
+// One by one: the first failing step's status is the item's -- ICP_EMPTY_DST and ICP_BAD_ARGUMENT (targets the normals
+// refuse) come from the normals, ICP_NAN_INPUT from the evaluation; *out then holds n and zeros.
+template <typename Kind>
+int serve_normal_quality_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, int k,
+                             double max_dist, typename Kind::Q *out, int *status) {
   quality_clear((size_t)it.n, out);
   return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_EMPTY_DST, ICP_NAN_INPUT, ICP_BAD_ARGUMENT}, status,
                           [&](icp_handle *h, const double *s) {
-                            ICP_TRY_RC(icp_compute_target_line_normals(h, k));
-                            return icp_evaluate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_dist, out, nullptr);
+                            ICP_TRY_RC(Kind::normals(h, k));
+                            return Kind::evaluate(h, s, (size_t)it.n, &it.init, max_dist, out);
                           });
 }
 
-int run_line_quality(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
-                     int k, double max_dist, icp_line_quality *out, int *status) {
+template <typename Kind>
+int run_normal_quality(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
+                       int k, double max_dist, typename Kind::Q *out, int *status) {
   std::vector<size_t> fit, one_by_one;
   unsigned m_max;
-  ICP_TRY_RC(stage_quality_items(b, items, count, line_quality_fits, &fit, &one_by_one, &m_max));
+  uint64_t *ctr = Kind::counters(b);
+  ICP_TRY_RC(stage_quality_items(b, items, count, Kind::fits, &fit, &one_by_one, &m_max));
   if (!fit.empty()) {
-    HIP_TRY(reserve_pinned(b->h_lqres, b->cap_lqres, count));
-    for (size_t i : fit) b->h_lqres[i].pad = 1;  // handed back, unless its workgroup writes the record
+    HIP_TRY(reserve_pinned(b->h_nqres, b->cap_nqres, count));
+    for (size_t i : fit) b->h_nqres[i].pad = 1;  // handed back, unless its workgroup writes the record
     bool granted = true;
-    // (r * r in f64 on the host, as icp_evaluate_point_to_line_device forms it)
-    HIP_TRY(launch_line_quality_batch(m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist, k,
-                                      b->h_lqres, b->stream, &granted));
-    ++b->lqctr[granted ? 2 : 3];
+    // (r * r in f64 on the host, as the single evaluations form it)
+    HIP_TRY(Kind::launch(m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist, k, b->h_nqres,
+                         b->stream, &granted));
+    ++ctr[granted ? 2 : 3];
     HIP_TRY(hipStreamSynchronize(b->stream));
     for (size_t i : fit) {
-      if (!granted || b->h_lqres[i].pad != 0) {
+      if (!granted || b->h_nqres[i].pad != 0) {
         one_by_one.push_back(i);
         continue;
       }
-      status[i] = line_quality_result((size_t)items[i].n, b->h_lqres[i], &out[i]);
-      ++b->lqctr[0];
+      status[i] = Kind::result((size_t)items[i].n, b->h_nqres[i], &out[i]);
+      ++ctr[0];
     }
   }
   for (size_t i : one_by_one) {
-    ICP_TRY_RC(serve_line_quality_one(b, d_src, d_dst, items[i], k, max_dist, &out[i], &status[i]));
-    ++b->lqctr[1];
+    ICP_TRY_RC(serve_normal_quality_one<Kind>(b, d_src, d_dst, items[i], k, max_dist, &out[i], &status[i]));
+    ++ctr[1];
   }
   return ICP_OK;
 }
 
-int check_line_quality_args(const icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
-                            const icp_batch_item *items, size_t count, int k, double max_dist, const icp_line_quality *out,
-                            const int *status) {
-  if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+// every argument, before anything touches the device
+template <typename Kind>
+int check_normal_quality_args(const icp_batch *b, const double *src, size_t src_points, const double *dst,
+                              size_t dst_points, const icp_batch_item *items, size_t count, int k, double max_dist,
+                              const typename Kind::Q *out, const int *status) {
+  // (a NaN bound fails the comparison)
+  if (!b || b->dim != Kind::kDim || k < 3 || k > 16 || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;
   return check_args(b, src, src_points, dst, dst_points, items, count, 0, out, status, false);
+}
+
+template <typename Kind>
+int normal_quality_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst, size_t dst_points,
+                          const icp_batch_item *items, size_t count, int k, double max_dist, typename Kind::Q *out,
+                          int *status) {
+  ICP_TRY_RC(check_normal_quality_args<Kind>(b, d_src, src_points, d_dst, dst_points, items, count, k, max_dist, out,
+                                             status));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  return run_normal_quality<Kind>(b, d_src, d_dst, items, count, k, max_dist, out, status);
+}
+
+template <typename Kind>
+int normal_quality_host(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                        const icp_batch_item *items, size_t count, int k, double max_dist, typename Kind::Q *out,
+                        int *status) {
+  ICP_TRY_RC(check_normal_quality_args<Kind>(b, src, src_points, dst, dst_points, items, count, k, max_dist, out, status));
+  if (count == 0) return ICP_OK;
+  ICP_TRY_RC(ensure_device(b));
+  const double *d_src, *d_dst;
+  ICP_TRY_RC(stage_clouds(b, src, src_points, dst, dst_points, &d_src, &d_dst));
+  return run_normal_quality<Kind>(b, d_src, d_dst, items, count, k, max_dist, out, status);
 }
 
 }  // namespace
@@ -718,25 +778,49 @@ extern "C" int icp_batch_evaluate_point_to_line_device(icp_batch *b, const doubl
                                                        const double *d_dst, size_t dst_points, const icp_batch_item *items,
                                                        size_t count, int k, double max_dist, icp_line_quality *out,
                                                        int *status) {
-  ICP_TRY_RC(check_line_quality_args(b, d_src, src_points, d_dst, dst_points, items, count, k, max_dist, out, status));
-  if (count == 0) return ICP_OK;
-  ICP_TRY_RC(ensure_device(b));
-  return run_line_quality(b, d_src, d_dst, items, count, k, max_dist, out, status);
+  return normal_quality_device<LineQualityKind>(b, d_src, src_points, d_dst, dst_points, items, count, k, max_dist, out,
+                                                status);
 }
 
 extern "C" int icp_batch_evaluate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
                                                 size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                                 double max_dist, icp_line_quality *out, int *status) {
-  ICP_TRY_RC(check_line_quality_args(b, src, src_points, dst, dst_points, items, count, k, max_dist, out, status));
-  if (count == 0) return ICP_OK;
-  ICP_TRY_RC(ensure_device(b));
-  const double *d_src, *d_dst;
-  ICP_TRY_RC(stage_clouds(b, src, src_points, dst, dst_points, &d_src, &d_dst));
-  return run_line_quality(b, d_src, d_dst, items, count, k, max_dist, out, status);
+  return normal_quality_host<LineQualityKind>(b, src, src_points, dst, dst_points, items, count, k, max_dist, out, status);
 }
 
 extern "C" int icp_batch_line_quality_counters(icp_batch *b, uint64_t out[4]) {
   if (!b || !out) return ICP_BAD_ARGUMENT;
   for (int q = 0; q < 4; ++q) out[q] = b->lqctr[q];
+  return ICP_OK;
+}
+
+// ---- section 20: the two entries with the point-to-plane residual (3-D batches, 3 <= k <= 16) ----
+extern "C" int icp_batch_evaluate_point_to_plane_device(icp_batch *b, const double *d_src, size_t src_points,
+                                                        const double *d_dst, size_t dst_points, const icp_batch_item *items,
+                                                        size_t count, int k, double max_dist, icp_plane_quality *out,
+                                                        int *status) {
+  return normal_quality_device<PlaneQualityKind>(b, d_src, src_points, d_dst, dst_points, items, count, k, max_dist, out,
+                                                 status);
+}
+
+extern "C" int icp_batch_evaluate_point_to_plane(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                                 size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                                 double max_dist, icp_plane_quality *out, int *status) {
+  return normal_quality_host<PlaneQualityKind>(b, src, src_points, dst, dst_points, items, count, k, max_dist, out, status);
+}
+
+extern "C" int icp_batch_plane_quality_counters(icp_batch *b, uint64_t out[4]) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) out[q] = b->pqctr[q];
+  return ICP_OK;
+}
+
+extern "C" int icp_debug_plane_quality_batch_plan(unsigned m, uint32_t out[4]) {
+  if (!out || m < 1 || m > kPlaneQualityMaxM) return ICP_BAD_ARGUMENT;
+  const PlanePlan plan = plane_quality_plan_of(m);
+  out[0] = plan.list_threads;
+  out[1] = plan.shared_bytes;
+  out[2] = plan.fixed_bytes;
+  out[3] = plan.lds_bytes;
   return ICP_OK;
 }

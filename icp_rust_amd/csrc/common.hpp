@@ -620,6 +620,18 @@ constexpr unsigned kLineQualityMaxN = 1024, kLineQualityMaxM = 2048;
 hipError_t launch_line_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
                                      const QualityBatchItem *d_items, unsigned count, double r2, int k,
                                      LineQualityPart *res, hipStream_t stream, bool *granted);
+// EXTENSION: the same under the point-to-plane residual for 3-D batches (quality_plane_batch.hip: k_plane_quality_batch;
+// include/icp_mi355x.h section 20; api_batch.hip drives it): one workgroup of 1024 threads per item computes the item's
+// plane normals from k neighbours and writes res[slot] with pad = 0; hand-backs and *granted as for
+// launch_line_quality_batch.  The limits are launch_plane_estimate_batch's.
+constexpr unsigned kPlaneQualityMaxN = 1024, kPlaneQualityMaxM = 2048;
+int plane_quality_result(size_t n, const NormalQualityPart &p, icp_plane_quality *q);
+hipError_t launch_plane_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
+                                      const QualityBatchItem *d_items, unsigned count, double r2, int k,
+                                      NormalQualityPart *res, hipStream_t stream, bool *granted);
+// its LDS plan: the rounds of the normals, the region the sort keys, the lists and the fold share
+// in turn, the bytes beside it, and their sum
+PlanePlan plane_quality_plan_of(unsigned m_max);
 // three launches around a predicted window (gn_win.hip); h_res->overflow == 2 when it missed
 bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind = 2, bool any_n = false,
                    double f_override = 0.);

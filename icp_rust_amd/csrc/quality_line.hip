@@ -86,7 +86,7 @@ static_assert(line_quality_plan(kLineQualityMaxM).list_threads == 320 &&
 
 }  // namespace
 
-// One item per workgroup, a thread per source point (1 <= n <= 1024, 1 <= m <= 2048: api_batch.hip, line_quality_fits).
+// One item per workgroup, a thread per source point (1 <= n <= 1024, 1 <= m <= 2048: api_batch.hip, LineQualityKind).
 // Hand-backs (the item's record is left as the host preset it, pad != 0): a box that is not finite, a NaN target.
 __global__ __launch_bounds__(kLineQualityThreads) void k_line_quality_batch(const double *__restrict__ src_all,
                                                                             const double *__restrict__ dst_all,

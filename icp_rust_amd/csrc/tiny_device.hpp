@@ -1,9 +1,10 @@
 // What the one-workgroup estimators share, each piece once: k_tiny_eval, k_tiny_estimate / k_tiny_estimate_batch
 // (gn_fast.hip, tiny_estimate_body.inc), k_line_estimate_batch / k_line_estimate_gated_batch (p2line_batch.hip),
 // k_plane_estimate_batch (p2plane_batch.hip) and, for the box, the targets and the search, k_line_quality_batch
-// (quality_line.hip).  Every piece defines a result's bits -- the tie rule, the screen's margin, the order of the break
-// tests -- and the batch entries promise what the single calls return, bit for bit: so there is one copy of each.  All
-// functions are called by every thread of the workgroup unless they say otherwise.
+// (quality_line.hip) and k_plane_quality_batch (quality_plane_batch.hip).  Every piece defines a result's bits -- the
+// tie rule, the screen's margin, the order of the break tests -- and the batch entries promise what the single calls
+// return, bit for bit: so there is one copy of each.  All functions are called by every thread of the workgroup unless
+// they say otherwise.
 #pragma once
 #include <initializer_list>
 

@@ -70,7 +70,8 @@ extern "C" {
  * icp_batch_evaluate_point_to_line*; icp_batch_line_quality_counters in icp_mi355x_debug.h); so was section 17
  * (icp_batch_estimate_point_to_line_gated*; icp_batch_line_gated_counters in icp_mi355x_debug.h); so was section 18
  * (icp_batch_estimate_point_to_plane*; icp_batch_plane_counters in icp_mi355x_debug.h); so was section 19
- * (icp_batch_estimate_point_to_plane_gated*; icp_batch_plane_gated_counters in icp_mi355x_debug.h) */
+ * (icp_batch_estimate_point_to_plane_gated*; icp_batch_plane_gated_counters in icp_mi355x_debug.h); so was section 20
+ * (icp_batch_evaluate_point_to_plane*; icp_batch_plane_quality_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -1034,6 +1035,30 @@ int icp_batch_estimate_point_to_plane_gated_device(icp_batch *b, const double *d
                                                    size_t count, int k, size_t max_iter, double max_dist, icp_pose *out,
                                                    int *status, uint32_t *d_last_idx, uint32_t *inner_iters,
                                                    uint32_t *inliers);
+
+/* ================================================================================
+ * 20. EXTENSION (not in the reference): the point-to-plane quality of many poses in one call
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 16's batch call with section 13's
+ * residual, for 3-D batches: K submap patches, loop-closure candidates or hypotheses registered by section 18 are ranked
+ * by plane_rmse and handed to a pose graph with the information the plane residual gives (section 9's batch score has
+ * c I for its translation block whatever the scene looks like).  Item i's out[i] and status[i] are what
+ * icp_create(3, dst + 3 dst_first, m) + icp_compute_target_normals(k) +
+ * icp_evaluate_point_to_plane(src + 3 src_first, n, &items[i].init, max_dist) give on a fresh handle, bit for bit; the
+ * first failing step's status is the item's (ICP_EMPTY_DST without targets, ICP_BAD_ARGUMENT where
+ * icp_compute_target_normals refuses the targets, ICP_NAN_INPUT), and out[i] then holds n and zeros.  Every item with
+ * 1 <= n <= 1024 and 1 <= m <= 2048 (section 18's limits) runs as ONE workgroup that computes the item's plane normals
+ * and the score, all of them in one launch; the other items, and those a workgroup hands back,
+ * go through exactly those three entries one after another.  An item is never approximated.  Arguments and ranges are
+ * section 8's and section 9's: ICP_BAD_ARGUMENT for b, items, out or status NULL with count > 0, a range outside the
+ * packed arrays, max_dist NaN or negative, a batch that is not 3-D and k outside [3, 16] -- all before the device is
+ * touched; count == 0 is a successful no-op. */
+int icp_batch_evaluate_point_to_plane(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                      size_t dst_points, const icp_batch_item *items, size_t count, int k, double max_dist,
+                                      icp_plane_quality *out, int *status);
+int icp_batch_evaluate_point_to_plane_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                             size_t dst_points, const icp_batch_item *items, size_t count, int k,
+                                             double max_dist, icp_plane_quality *out, int *status);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,17 @@ int icp_batch_plane_gated_counters(icp_batch *b, uint64_t out[4]);
  * same rounds of the normals (out[0]), and a shared region (out[1]) that also holds, behind the three sort buffers, one
  * 4-byte word per thread and sixteen wave counts for the gate.  Host arithmetic: no device use. */
 int icp_debug_plane_gated_batch_plan(unsigned threads, unsigned m, uint32_t out[4]);
+/* ... and of icp_batch_evaluate_point_to_plane[_device] (icp_mi355x.h section 20): out[0] items scored inside a batch
+ * launch, out[1] items scored one by one through icp_create_device + icp_compute_target_normals +
+ * icp_evaluate_point_to_plane_device (outside the limits, handed back by their workgroup, or no LDS grant), out[2] batch
+ * launches, out[3] launches not made because the runtime refused the kernel its LDS. */
+int icp_batch_plane_quality_counters(icp_batch *b, uint64_t out[4]);
+/* The LDS plan of a launch of section 20's kernel, 1024 threads per workgroup, for items of at
+ * most m targets (1 .. 2048), laid out as icp_debug_plane_batch_plan's: out[0] targets whose neighbour lists one round of
+ * the normals holds, out[1] bytes of the region the sort keys, the lists and the fold use in turn, out[2] bytes beside it
+ * (x | y | z, the screen records, the normals, 256 B of control words), out[3] dynamic LDS of the launch (out[1] +
+ * out[2]).  Host arithmetic: no device use. */
+int icp_debug_plane_quality_batch_plan(unsigned m, uint32_t out[4]);
 
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
