@@ -17,12 +17,12 @@
 // Section 19, section 18 with a maximum correspondence distance: k_plane_estimate_gated_batch, driven the same way; one
 // by one: icp_estimate_point_to_plane_gated_device in the last step's place.
 #include <cstring>
-#include <initializer_list>
 #include <new>
 #include <vector>
 
 #include "../../include/icp_mi355x_debug.h"
 #include "api_internal.hpp"
+#include "normal_batch_device.hpp"  // (the LDS plans the debug entries report)
 
 using namespace icp;
 using namespace icp::api;
@@ -42,24 +42,20 @@ struct icp_batch {
   size_t cap_res = 0;
   uint32_t *h_inner = nullptr;  // pinned: count x max_iter inner counts
   size_t cap_inner = 0;
-  uint64_t ctr[4] = {0, 0, 0, 0};  // icp_batch_counters
-  uint64_t lctr[4] = {0, 0, 0, 0};  // icp_batch_line_counters
   uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (sections 17 and 19)
   size_t cap_inl = 0;
-  uint64_t lgctr[4] = {0, 0, 0, 0};  // icp_batch_line_gated_counters
-  uint64_t pctr[4] = {0, 0, 0, 0};   // icp_batch_plane_counters
-  uint64_t pgctr[4] = {0, 0, 0, 0};  // icp_batch_plane_gated_counters
+  // what each family of entries has done, by CounterSet: {items a workgroup served, items served one by one, launches,
+  // launches the runtime refused their LDS} (icp_batch_evaluate_counters: the first three)
+  enum CounterSet { kPoint, kLine, kLineGated, kPlane, kPlaneGated, kQuality, kLineQuality, kPlaneQuality, kCounterSets };
+  uint64_t ctr[kCounterSets][4] = {};
   // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
   QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
   size_t cap_qitems = 0, cap_h_qitems = 0;
   QualityPart *h_qres = nullptr;
   size_t cap_qres = 0;
-  uint64_t qctr[3] = {0, 0, 0};  // icp_batch_evaluate_counters
   // icp_batch_evaluate_point_to_line / _plane (sections 16 and 20): the item list above, and their own records (pinned)
   NormalQualityPart *h_nqres = nullptr;
   size_t cap_nqres = 0;
-  uint64_t lqctr[4] = {0, 0, 0, 0};  // icp_batch_line_quality_counters
-  uint64_t pqctr[4] = {0, 0, 0, 0};  // icp_batch_plane_quality_counters
 };
 
 namespace {
@@ -100,23 +96,11 @@ int check_args(const icp_batch *b, const double *src, size_t src_points, const d
   return ICP_OK;
 }
 
-bool tiny_fits(const icp_batch_item &it, size_t max_iter) {
-  return it.n >= 1 && it.n <= kTinyMaxN && it.m >= 1 && it.m <= kTinyMaxM && max_iter >= 1 && max_iter <= kTinyMaxIter;
-}
-bool line_fits(const icp_batch_item &it, size_t max_iter) {
-  return it.n >= 1 && it.n <= kLineBatchMaxN && it.m >= 1 && it.m <= kLineBatchMaxM && max_iter >= 1 &&
-         max_iter <= kLineBatchMaxIter;
-}
-bool plane_fits(const icp_batch_item &it, size_t max_iter) {
-  return it.n >= 1 && it.n <= kPlaneBatchMaxN && it.m >= 1 && it.m <= kPlaneBatchMaxM && max_iter >= 1 &&
-         max_iter <= kPlaneBatchMaxIter;
-}
-
 // An item the way single calls serve it: a handle of the pool on the item's targets, serve(h, the item's sources) on it.
 // The outcomes in `per_item` land in *status; anything else (HIP, memory, device) is the call's failure.
-template <typename Serve>
+template <size_t N, typename Serve>
 int with_pool_handle(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it,
-                     std::initializer_list<int> per_item, int *status, Serve serve) {
+                     const int (&per_item)[N], int *status, Serve serve) {
   icp_handle *h = nullptr;
   int rc = icp_create_device(&h, b->dim, it.m > 0 ? d_dst + it.dst_first * b->dim : nullptr, (size_t)it.m, b->device);
   if (rc == ICP_OK) {
@@ -131,52 +115,84 @@ int with_pool_handle(icp_batch *b, const double *d_src, const double *d_dst, con
   return rc;
 }
 
-// The residual of an estimate call: line_k == 0: section 8 (the point residual); line_k > 0: section 15 (the line
-// residual, normals from line_k neighbours); gated on top (section 17): the pairs within max_dist, their counts per
-// outer iteration to `inliers` (count x max_iter, or null); plane_k > 0 (and line_k == 0): section 18 (the plane residual
-// of a 3-D batch, normals from plane_k neighbours); plane_k > 0 && gated: section 19 (section 18 with the gate).
+// What the caller of an estimate entry supplies besides the clouds and the items: k, the neighbours of the normals (the
+// point residual has none); for the gated entries max_dist and where the pairs kept per outer iteration go (count x
+// max_iter, or null).
 struct Residual {
-  int line_k = 0;
-  bool gated = false;
+  int k = 0;
   double max_dist = 0.;
   uint32_t *inliers = nullptr;
-  int plane_k = 0;
 };
 
-// icp_estimate_device on the item's handle; line_k > 0: the handle's line normals from line_k neighbours, then
-// icp_estimate_point_to_line_device, or (gated) icp_estimate_point_to_line_gated_device; inl: the item's inlier counts;
-// plane_k > 0: the handle's plane normals from plane_k neighbours, then icp_estimate_point_to_plane_device, or (gated)
-// icp_estimate_point_to_plane_gated_device.  The first failing step gives the item's status (ICP_BAD_ARGUMENT: targets
-// the normals refuse, as section 16's one-by-one server).
-int serve_one(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item &it, size_t max_iter,
-              const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner, uint32_t *inl) {
-  if (res.plane_k > 0)
-    return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_EMPTY_DST, ICP_NAN_INPUT, ICP_BAD_ARGUMENT}, status,
-                            [&](icp_handle *h, const double *s) {
-                              ICP_TRY_RC(icp_compute_target_normals(h, res.plane_k));
-                              if (res.gated)
-                                return icp_estimate_point_to_plane_gated_device(h, s, (size_t)it.n, &it.init, max_iter,
-                                                                                res.max_dist, out, d_idx, inner, inl);
-                              return icp_estimate_point_to_plane_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx,
-                                                                        inner);
-                            });
-  return with_pool_handle(b, d_src, d_dst, it, {ICP_OK, ICP_NONE, ICP_EMPTY_DST, ICP_NAN_INPUT}, status,
-                          [&](icp_handle *h, const double *s) {
-                            if (res.line_k == 0)
-                              return icp_estimate_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
-                            ICP_TRY_RC(icp_compute_target_line_normals(h, res.line_k));
-                            if (res.gated)
-                              return icp_estimate_point_to_line_gated_device(h, s, (size_t)it.n, &it.init, max_iter,
-                                                                             res.max_dist, out, d_idx, inner, inl);
-                            return icp_estimate_point_to_line_device(h, s, (size_t)it.n, &it.init, max_iter, out, d_idx, inner);
-                          });
+// ---- the five estimates behind run(): what they differ in is a Kind ----
+//   kMaxN, kMaxM, kMaxIter  the items a workgroup serves
+//   threads(n)              its size
+//   launch(...)             one launch over the items of one size (inl: the pinned inlier counts, or null)
+//   kCounters               the entry's counters
+//   kPerItem, normals, estimate   one by one: the statuses that are the item's own, and the single calls on its handle --
+//                           the first failing step gives the item's status (ICP_BAD_ARGUMENT: targets the plane normals
+//                           refuse, as section 20's one-by-one server)
+struct PointKind {  // section 8: k_tiny_estimate_batch (gn_fast.hip); icp_estimate_device
+  static constexpr unsigned kMaxN = kTinyMaxN, kMaxM = kTinyMaxM, kMaxIter = kTinyMaxIter;
+  static constexpr icp_batch::CounterSet kCounters = icp_batch::kPoint;
+  static constexpr int kPerItem[4] = {ICP_OK, ICP_NONE, ICP_EMPTY_DST, ICP_NAN_INPUT};
+  static unsigned threads(size_t n) { return tiny_threads(n); }
+  static hipError_t launch(icp_batch *b, const Residual &, unsigned threads, unsigned m_max, const double *d_src,
+                           const double *d_dst, const TinyBatchItem *d_items, unsigned count, unsigned max_iter,
+                           uint32_t *inner, uint32_t *d_idx, uint32_t *, bool *granted) {
+    return launch_tiny_estimate_batch(b->dim, threads, m_max, d_src, d_dst, d_items, count, max_iter, b->h_res, inner, d_idx,
+                                      b->stream, granted);
+  }
+  static int normals(icp_handle *, int) { return ICP_OK; }
+  static int estimate(icp_handle *h, const double *s, size_t n, const icp_pose *init, size_t max_iter, const Residual &,
+                      icp_pose *out, uint32_t *d_idx, uint32_t *inner, uint32_t *) {
+    return icp_estimate_device(h, s, n, init, max_iter, out, d_idx, inner);
+  }
+};
+
+// sections 15 and 17 (DIM 2: the line residual, p2line_batch.hip), 18 and 19 (DIM 3: the plane residual,
+// p2plane_batch.hip); GATED: sections 17 and 19
+template <int DIM, bool GATED>
+struct NormalKind {
+  static constexpr unsigned kMaxN = DIM == 2 ? kLineBatchMaxN : kPlaneBatchMaxN;
+  static constexpr unsigned kMaxM = DIM == 2 ? kLineBatchMaxM : kPlaneBatchMaxM;
+  static constexpr unsigned kMaxIter = DIM == 2 ? kLineBatchMaxIter : kPlaneBatchMaxIter;
+  static constexpr icp_batch::CounterSet kCounters =
+      DIM == 2 ? (GATED ? icp_batch::kLineGated : icp_batch::kLine) : (GATED ? icp_batch::kPlaneGated : icp_batch::kPlane);
+  static constexpr int kPerItem[4] = {ICP_OK, DIM == 2 ? ICP_NONE : ICP_BAD_ARGUMENT, ICP_EMPTY_DST, ICP_NAN_INPUT};
+  static unsigned threads(size_t n) { return normal_batch_threads(n); }
+  static hipError_t launch(icp_batch *b, const Residual &res, unsigned threads, unsigned m_max, const double *d_src,
+                           const double *d_dst, const TinyBatchItem *d_items, unsigned count, unsigned max_iter,
+                           uint32_t *inner, uint32_t *d_idx, uint32_t *inl, bool *granted) {
+    // (max_dist * max_dist in f64 on the host, as the single gated entries form it)
+    return launch_normal_estimate_batch<DIM, GATED>(threads, m_max, d_src, d_dst, d_items, count, max_iter, res.k,
+                                                    res.max_dist * res.max_dist, b->h_res, inner, d_idx, inl, b->stream,
+                                                    granted);
+  }
+  static int normals(icp_handle *h, int k) {
+    return DIM == 2 ? icp_compute_target_line_normals(h, k) : icp_compute_target_normals(h, k);
+  }
+  static int estimate(icp_handle *h, const double *s, size_t n, const icp_pose *init, size_t max_iter, const Residual &res,
+                      icp_pose *out, uint32_t *d_idx, uint32_t *inner, uint32_t *inl) {
+    if constexpr (GATED)
+      return (DIM == 2 ? icp_estimate_point_to_line_gated_device
+                       : icp_estimate_point_to_plane_gated_device)(h, s, n, init, max_iter, res.max_dist, out, d_idx, inner, inl);
+    else
+      return (DIM == 2 ? icp_estimate_point_to_line_device
+                       : icp_estimate_point_to_plane_device)(h, s, n, init, max_iter, out, d_idx, inner);
+  }
+};
+
+template <typename Kind>
+bool fits(const icp_batch_item &it, size_t max_iter) {
+  return it.n >= 1 && it.n <= Kind::kMaxN && it.m >= 1 && it.m <= Kind::kMaxM && max_iter >= 1 && max_iter <= Kind::kMaxIter;
 }
 
+template <typename Kind>
 int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_item *items, size_t count,
         size_t max_iter, const Residual &res, icp_pose *out, int *status, uint32_t *d_idx, uint32_t *inner_iters) {
-  const int line_k = res.line_k, plane_k = res.plane_k;
-  uint32_t *inliers = res.gated ? res.inliers : nullptr;
-  uint64_t *ctr = plane_k > 0 ? (res.gated ? b->pgctr : b->pctr) : (res.gated ? b->lgctr : (line_k > 0 ? b->lctr : b->ctr));
+  uint32_t *inliers = res.inliers;
+  uint64_t *ctr = b->ctr[Kind::kCounters];
   // where each item's indices go, and which items a workgroup may serve, by workgroup size
   std::vector<uint64_t> idx_first(count);
   std::vector<size_t> cls[3], one_by_one;
@@ -184,11 +200,8 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
   for (size_t i = 0; i < count; ++i) {
     idx_first[i] = at;
     at += items[i].n;
-    const bool fits = plane_k > 0 ? plane_fits(items[i], max_iter)
-                                  : (line_k > 0 ? line_fits(items[i], max_iter) : tiny_fits(items[i], max_iter));
-    if (fits) {
-      const unsigned t = plane_k > 0 ? plane_batch_threads(items[i].n)
-                                     : (line_k > 0 ? line_batch_threads(items[i].n) : tiny_threads(items[i].n));
+    if (fits<Kind>(items[i], max_iter)) {
+      const unsigned t = Kind::threads(items[i].n);
       cls[t == 512u ? 0 : (t == 768u ? 1 : 2)].push_back(i);
     } else {
       one_by_one.push_back(i);
@@ -224,28 +237,9 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
     bool granted = true;
     for (int c = 0; c < 3; ++c) {
       if (cls[c].empty()) continue;
-      if (plane_k > 0 && res.gated)  // (max_dist * max_dist in f64 on the host, as icp_p2pl_gated_inner_loop_device forms it)
-        HIP_TRY(launch_plane_estimate_gated_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
-                                                  (unsigned)cls[c].size(), (unsigned)max_iter, plane_k,
-                                                  res.max_dist * res.max_dist, b->h_res, inner_iters ? b->h_inner : nullptr,
-                                                  d_idx, inliers ? b->h_inl : nullptr, b->stream, &granted));
-      else if (plane_k > 0)
-        HIP_TRY(launch_plane_estimate_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
-                                            (unsigned)cls[c].size(), (unsigned)max_iter, plane_k, b->h_res,
-                                            inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
-      else if (res.gated)  // (max_dist * max_dist in f64 on the host, as icp_estimate_point_to_line_gated_device forms it)
-        HIP_TRY(launch_line_estimate_gated_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
-                                                 (unsigned)cls[c].size(), (unsigned)max_iter, line_k,
-                                                 res.max_dist * res.max_dist, b->h_res, inner_iters ? b->h_inner : nullptr,
-                                                 d_idx, inliers ? b->h_inl : nullptr, b->stream, &granted));
-      else if (line_k > 0)
-        HIP_TRY(launch_line_estimate_batch(kThreads[c], m_max[c], d_src, d_dst, b->d_items + first, (unsigned)cls[c].size(),
-                                           (unsigned)max_iter, line_k, b->h_res, inner_iters ? b->h_inner : nullptr, d_idx,
-                                           b->stream, &granted));
-      else
-        HIP_TRY(launch_tiny_estimate_batch(b->dim, kThreads[c], m_max[c], d_src, d_dst, b->d_items + first,
-                                           (unsigned)cls[c].size(), (unsigned)max_iter, b->h_res,
-                                           inner_iters ? b->h_inner : nullptr, d_idx, b->stream, &granted));
+      HIP_TRY(Kind::launch(b, res, kThreads[c], m_max[c], d_src, d_dst, b->d_items + first, (unsigned)cls[c].size(),
+                           (unsigned)max_iter, inner_iters ? b->h_inner : nullptr, d_idx, inliers ? b->h_inl : nullptr,
+                           &granted));
       ++ctr[granted ? 2 : 3];
       first += cls[c].size();
     }
@@ -270,9 +264,12 @@ int run(icp_batch *b, const double *d_src, const double *d_dst, const icp_batch_
   }
   one_by_one.insert(one_by_one.end(), handed_back.begin(), handed_back.end());
   for (size_t i : one_by_one) {
-    ICP_TRY_RC(serve_one(b, d_src, d_dst, items[i], max_iter, res, &out[i], &status[i],
-                         d_idx ? d_idx + idx_first[i] : nullptr, inner_iters ? inner_iters + i * max_iter : nullptr,
-                         inliers ? inliers + i * max_iter : nullptr));
+    ICP_TRY_RC(with_pool_handle(b, d_src, d_dst, items[i], Kind::kPerItem, &status[i], [&](icp_handle *h, const double *s) {
+      ICP_TRY_RC(Kind::normals(h, res.k));
+      return Kind::estimate(h, s, (size_t)items[i].n, &items[i].init, max_iter, res, &out[i],
+                            d_idx ? d_idx + idx_first[i] : nullptr, inner_iters ? inner_iters + i * max_iter : nullptr,
+                            inliers ? inliers + i * max_iter : nullptr);
+    }));
     ++ctr[1];
   }
   return ICP_OK;
@@ -334,9 +331,32 @@ extern "C" void icp_batch_destroy(icp_batch *b) {
 
 namespace {
 
-// section 15's two checks on top of check_args: a 2-D batch, 3 <= k <= 16
-bool line_args_ok(const icp_batch *b, int k) { return b && b->dim == 2 && k >= 3 && k <= 16; }
+// what the entries with normals check on top of check_args: a batch of the residual's dimension, 3 <= k <= 16
+bool normal_args_ok(const icp_batch *b, int dim, int k) { return b && b->dim == dim && k >= 3 && k <= 16; }
 
+// one set of counters -> out[0 .. n)
+int counters_out(const icp_batch *b, icp_batch::CounterSet set, uint64_t *out, int n = 4) {
+  if (!b || !out) return ICP_BAD_ARGUMENT;
+  for (int q = 0; q < n; ++q) out[q] = b->ctr[set][q];
+  return ICP_OK;
+}
+
+// an LDS plan -> out[0 .. 4), where the debug entry's arguments are in range
+template <typename Plan>
+int plan_out(bool in_range, uint32_t *out, Plan plan) {
+  if (!out || !in_range) return ICP_BAD_ARGUMENT;
+  const NormalPlan p = plan();
+  out[0] = p.list_threads;
+  out[1] = p.shared_bytes;
+  out[2] = p.fixed_bytes;
+  out[3] = p.lds_bytes;
+  return ICP_OK;
+}
+bool estimate_plan_args_ok(unsigned threads, unsigned m) {
+  return (threads == 512u || threads == 1024u) && m >= 1 && m <= kPlaneBatchMaxM;
+}
+
+template <typename Kind>
 int estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst, size_t dst_points,
                     const icp_batch_item *items, size_t count, size_t max_iter, const Residual &res, icp_pose *out,
                     int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
@@ -344,7 +364,7 @@ int estimate_device(icp_batch *b, const double *d_src, size_t src_points, const 
                         inner_iters || res.inliers));
   if (count == 0) return ICP_OK;
   ICP_TRY_RC(ensure_device(b));
-  return run(b, d_src, d_dst, items, count, max_iter, res, out, status, d_last_idx, inner_iters);
+  return run<Kind>(b, d_src, d_dst, items, count, max_iter, res, out, status, d_last_idx, inner_iters);
 }
 
 // the host entries' clouds, staged through the batch's buffers: *d_src / *d_dst are what run, run_quality
@@ -367,6 +387,7 @@ int stage_clouds(icp_batch *b, const double *src, size_t src_points, const doubl
 }
 
 // the entries that take host clouds: staged, the last indices read back
+template <typename Kind>
 int estimate_host(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
                   const icp_batch_item *items, size_t count, size_t max_iter, const Residual &res, icp_pose *out,
                   int *status, uint32_t *last_idx, uint32_t *inner_iters) {
@@ -381,8 +402,8 @@ int estimate_host(icp_batch *b, const double *src, size_t src_points, const doub
   // (as icp_estimate: no outer iteration, no correspondences -- last_idx is left as it was)
   const bool want_idx = last_idx && total_n > 0 && max_iter > 0;
   if (want_idx) HIP_TRY(reserve(b->d_idx, b->cap_idx, total_n));
-  const int rc = run(b, d_src, d_dst, items, count, max_iter, res, out, status, want_idx ? b->d_idx : nullptr,
-                     inner_iters);
+  const int rc = run<Kind>(b, d_src, d_dst, items, count, max_iter, res, out, status, want_idx ? b->d_idx : nullptr,
+                           inner_iters);
   if (rc != ICP_OK) return rc;
   if (want_idx) {
     HIP_TRY(hipMemcpyAsync(last_idx, b->d_idx, total_n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
@@ -396,15 +417,15 @@ int estimate_host(icp_batch *b, const double *src, size_t src_points, const doub
 extern "C" int icp_batch_estimate_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
                                          size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
                                          icp_pose *out, int *status, uint32_t *d_last_idx, uint32_t *inner_iters) {
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, Residual{}, out, status,
-                         d_last_idx, inner_iters);
+  return estimate_device<PointKind>(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, Residual{}, out,
+                                    status, d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
                                   const icp_batch_item *items, size_t count, size_t max_iter, icp_pose *out, int *status,
                                   uint32_t *last_idx, uint32_t *inner_iters) {
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{}, out, status, last_idx,
-                       inner_iters);
+  return estimate_host<PointKind>(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{}, out, status,
+                                  last_idx, inner_iters);
 }
 
 // ---- section 15: the same two entries with the point-to-line residual (2-D batches, 3 <= k <= 16) ----
@@ -412,18 +433,18 @@ extern "C" int icp_batch_estimate_point_to_line_device(icp_batch *b, const doubl
                                                        const double *d_dst, size_t dst_points, const icp_batch_item *items,
                                                        size_t count, int k, size_t max_iter, icp_pose *out, int *status,
                                                        uint32_t *d_last_idx, uint32_t *inner_iters) {
-  if (!line_args_ok(b, k)) return ICP_BAD_ARGUMENT;
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, Residual{k, false, 0., nullptr},
-                         out, status, d_last_idx, inner_iters);
+  if (!normal_args_ok(b, 2, k)) return ICP_BAD_ARGUMENT;
+  return estimate_device<NormalKind<2, false>>(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                                               Residual{k}, out, status, d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate_point_to_line(icp_batch *b, const double *src, size_t src_points, const double *dst,
                                                 size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                                 size_t max_iter, icp_pose *out, int *status, uint32_t *last_idx,
                                                 uint32_t *inner_iters) {
-  if (!line_args_ok(b, k)) return ICP_BAD_ARGUMENT;
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k, false, 0., nullptr}, out,
-                       status, last_idx, inner_iters);
+  if (!normal_args_ok(b, 2, k)) return ICP_BAD_ARGUMENT;
+  return estimate_host<NormalKind<2, false>>(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k}, out,
+                                             status, last_idx, inner_iters);
 }
 
 // ---- section 17: section 15's entries with a maximum correspondence distance (max_dist >= 0, or +inf) ----
@@ -433,69 +454,49 @@ extern "C" int icp_batch_estimate_point_to_line_gated_device(icp_batch *b, const
                                                              size_t max_iter, double max_dist, icp_pose *out, int *status,
                                                              uint32_t *d_last_idx, uint32_t *inner_iters,
                                                              uint32_t *inliers) {
-  if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
-                         Residual{k, true, max_dist, inliers}, out, status, d_last_idx, inner_iters);
+  if (!normal_args_ok(b, 2, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_device<NormalKind<2, true>>(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                                              Residual{k, max_dist, inliers}, out, status, d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate_point_to_line_gated(icp_batch *b, const double *src, size_t src_points, const double *dst,
                                                       size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                                       size_t max_iter, double max_dist, icp_pose *out, int *status,
                                                       uint32_t *last_idx, uint32_t *inner_iters, uint32_t *inliers) {
-  if (!line_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k, true, max_dist, inliers},
-                       out, status, last_idx, inner_iters);
+  if (!normal_args_ok(b, 2, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_host<NormalKind<2, true>>(b, src, src_points, dst, dst_points, items, count, max_iter,
+                                            Residual{k, max_dist, inliers}, out, status, last_idx, inner_iters);
 }
 
 // ---- section 18: section 8's two entries with the point-to-plane residual (3-D batches, 3 <= k <= 16) ----
-namespace {
-bool plane_args_ok(const icp_batch *b, int k) { return b && b->dim == 3 && k >= 3 && k <= 16; }
-Residual plane_residual_of(int k) {
-  Residual res;
-  res.plane_k = k;
-  return res;
-}
-}  // namespace
-
 extern "C" int icp_batch_estimate_point_to_plane_device(icp_batch *b, const double *d_src, size_t src_points,
                                                         const double *d_dst, size_t dst_points, const icp_batch_item *items,
                                                         size_t count, int k, size_t max_iter, icp_pose *out, int *status,
                                                         uint32_t *d_last_idx, uint32_t *inner_iters) {
-  if (!plane_args_ok(b, k)) return ICP_BAD_ARGUMENT;
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter, plane_residual_of(k), out,
-                         status, d_last_idx, inner_iters);
+  if (!normal_args_ok(b, 3, k)) return ICP_BAD_ARGUMENT;
+  return estimate_device<NormalKind<3, false>>(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                                               Residual{k}, out, status, d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate_point_to_plane(icp_batch *b, const double *src, size_t src_points, const double *dst,
                                                  size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                                  size_t max_iter, icp_pose *out, int *status, uint32_t *last_idx,
                                                  uint32_t *inner_iters) {
-  if (!plane_args_ok(b, k)) return ICP_BAD_ARGUMENT;
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter, plane_residual_of(k), out, status,
-                       last_idx, inner_iters);
+  if (!normal_args_ok(b, 3, k)) return ICP_BAD_ARGUMENT;
+  return estimate_host<NormalKind<3, false>>(b, src, src_points, dst, dst_points, items, count, max_iter, Residual{k}, out,
+                                             status, last_idx, inner_iters);
 }
 
 // ---- section 19: section 18's entries with a maximum correspondence distance (max_dist >= 0, or +inf) ----
-namespace {
-Residual plane_gated_residual_of(int k, double max_dist, uint32_t *inliers) {
-  Residual res;
-  res.plane_k = k;
-  res.gated = true;
-  res.max_dist = max_dist;
-  res.inliers = inliers;
-  return res;
-}
-}  // namespace
-
 extern "C" int icp_batch_estimate_point_to_plane_gated_device(icp_batch *b, const double *d_src, size_t src_points,
                                                               const double *d_dst, size_t dst_points,
                                                               const icp_batch_item *items, size_t count, int k,
                                                               size_t max_iter, double max_dist, icp_pose *out, int *status,
                                                               uint32_t *d_last_idx, uint32_t *inner_iters,
                                                               uint32_t *inliers) {
-  if (!plane_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
-  return estimate_device(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
-                         plane_gated_residual_of(k, max_dist, inliers), out, status, d_last_idx, inner_iters);
+  if (!normal_args_ok(b, 3, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_device<NormalKind<3, true>>(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                                              Residual{k, max_dist, inliers}, out, status, d_last_idx, inner_iters);
 }
 
 extern "C" int icp_batch_estimate_point_to_plane_gated(icp_batch *b, const double *src, size_t src_points,
@@ -503,59 +504,28 @@ extern "C" int icp_batch_estimate_point_to_plane_gated(icp_batch *b, const doubl
                                                        size_t count, int k, size_t max_iter, double max_dist, icp_pose *out,
                                                        int *status, uint32_t *last_idx, uint32_t *inner_iters,
                                                        uint32_t *inliers) {
-  if (!plane_args_ok(b, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
-  return estimate_host(b, src, src_points, dst, dst_points, items, count, max_iter,
-                       plane_gated_residual_of(k, max_dist, inliers), out, status, last_idx, inner_iters);
+  if (!normal_args_ok(b, 3, k) || !(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_host<NormalKind<3, true>>(b, src, src_points, dst, dst_points, items, count, max_iter,
+                                            Residual{k, max_dist, inliers}, out, status, last_idx, inner_iters);
 }
 
+// ---- the estimates' counters and the LDS plans of the plane kernels' launches (include/icp_mi355x_debug.h) ----
+extern "C" int icp_batch_counters(icp_batch *b, uint64_t out[4]) { return counters_out(b, icp_batch::kPoint, out); }
+extern "C" int icp_batch_line_counters(icp_batch *b, uint64_t out[4]) { return counters_out(b, icp_batch::kLine, out); }
+extern "C" int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]) {
+  return counters_out(b, icp_batch::kLineGated, out);
+}
+extern "C" int icp_batch_plane_counters(icp_batch *b, uint64_t out[4]) { return counters_out(b, icp_batch::kPlane, out); }
 extern "C" int icp_batch_plane_gated_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->pgctr[q];
-  return ICP_OK;
-}
-
-extern "C" int icp_debug_plane_gated_batch_plan(unsigned threads, unsigned m, uint32_t out[4]) {
-  if (!out || (threads != 512u && threads != 1024u) || m < 1 || m > kPlaneBatchMaxM) return ICP_BAD_ARGUMENT;
-  const PlanePlan plan = plane_gated_batch_plan_of(threads, m);
-  out[0] = plan.list_threads;
-  out[1] = plan.shared_bytes;
-  out[2] = plan.fixed_bytes;
-  out[3] = plan.lds_bytes;
-  return ICP_OK;
-}
-
-extern "C" int icp_batch_plane_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->pctr[q];
-  return ICP_OK;
+  return counters_out(b, icp_batch::kPlaneGated, out);
 }
 
 extern "C" int icp_debug_plane_batch_plan(unsigned threads, unsigned m, uint32_t out[4]) {
-  if (!out || (threads != 512u && threads != 1024u) || m < 1 || m > kPlaneBatchMaxM) return ICP_BAD_ARGUMENT;
-  const PlanePlan plan = plane_batch_plan_of(threads, m);
-  out[0] = plan.list_threads;
-  out[1] = plan.shared_bytes;
-  out[2] = plan.fixed_bytes;
-  out[3] = plan.lds_bytes;
-  return ICP_OK;
+  return plan_out(estimate_plan_args_ok(threads, m), out, [&] { return normal_estimate_plan<3, false>(threads, m); });
 }
 
-extern "C" int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->lgctr[q];
-  return ICP_OK;
-}
-
-extern "C" int icp_batch_line_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->lctr[q];
-  return ICP_OK;
-}
-
-extern "C" int icp_batch_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->ctr[q];
-  return ICP_OK;
+extern "C" int icp_debug_plane_gated_batch_plan(unsigned threads, unsigned m, uint32_t out[4]) {
+  return plan_out(estimate_plan_args_ok(threads, m), out, [&] { return normal_estimate_plan<3, true>(threads, m); });
 }
 
 // ---- icp_batch_evaluate (include/icp_mi355x.h section 9): the quality of many poses in one launch ----
@@ -610,11 +580,11 @@ int run_quality(icp_batch *b, const double *d_src, const double *d_dst, const ic
     // (r * r in f64 on the host, as icp_evaluate_device forms it)
     HIP_TRY(launch_quality_batch(b->dim, m_max, d_src, d_dst, b->d_qitems, (unsigned)fit.size(), max_dist * max_dist,
                                  b->h_qres, b->stream));
-    ++b->qctr[2];
+    ++b->ctr[icp_batch::kQuality][2];
     HIP_TRY(hipStreamSynchronize(b->stream));
     for (size_t i : fit) {
       status[i] = quality_result((size_t)items[i].n, b->h_qres[i], &out[i]);
-      ++b->qctr[0];
+      ++b->ctr[icp_batch::kQuality][0];
     }
   }
   for (size_t i : one_by_one) {
@@ -623,7 +593,7 @@ int run_quality(icp_batch *b, const double *d_src, const double *d_dst, const ic
                                   return icp_evaluate_device(h, s, (size_t)items[i].n, &items[i].init, max_dist, &out[i],
                                                              nullptr);
                                 }));
-    ++b->qctr[1];
+    ++b->ctr[icp_batch::kQuality][1];
   }
   return ICP_OK;
 }
@@ -651,9 +621,7 @@ extern "C" int icp_batch_evaluate(icp_batch *b, const double *src, size_t src_po
 }
 
 extern "C" int icp_batch_evaluate_counters(icp_batch *b, uint64_t out[3]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 3; ++q) out[q] = b->qctr[q];
-  return ICP_OK;
+  return counters_out(b, icp_batch::kQuality, out, 3);
 }
 
 // ---- icp_batch_evaluate_point_to_line (include/icp_mi355x.h section 16) and icp_batch_evaluate_point_to_plane
@@ -670,28 +638,28 @@ struct LineQualityKind {
   static bool fits(const icp_batch_item &it) {
     return it.n >= 1 && it.n <= kLineQualityMaxN && it.m >= 1 && it.m <= kLineQualityMaxM;
   }
-  static constexpr auto launch = launch_line_quality_batch;
+  static constexpr auto launch = launch_normal_quality_batch<2>;
   static int result(size_t n, const NormalQualityPart &p, Q *q) { return line_quality_result(n, p, q); }
   static int normals(icp_handle *h, int k) { return icp_compute_target_line_normals(h, k); }
   static int evaluate(icp_handle *h, const double *s, size_t n, const icp_pose *T, double max_dist, Q *out) {
     return icp_evaluate_point_to_line_device(h, s, n, T, max_dist, out, nullptr);
   }
-  static uint64_t *counters(icp_batch *b) { return b->lqctr; }
+  static uint64_t *counters(icp_batch *b) { return b->ctr[icp_batch::kLineQuality]; }
 };
 
 struct PlaneQualityKind {
   using Q = icp_plane_quality;
   static constexpr int kDim = 3;
-  static bool fits(const icp_batch_item &it) {  // (plane_fits' limits: what section 18 serves in a launch, this does)
+  static bool fits(const icp_batch_item &it) {  // (section 18's limits: what that serves in a launch, this does)
     return it.n >= 1 && it.n <= kPlaneQualityMaxN && it.m >= 1 && it.m <= kPlaneQualityMaxM;
   }
-  static constexpr auto launch = launch_plane_quality_batch;
+  static constexpr auto launch = launch_normal_quality_batch<3>;
   static int result(size_t n, const NormalQualityPart &p, Q *q) { return plane_quality_result(n, p, q); }
   static int normals(icp_handle *h, int k) { return icp_compute_target_normals(h, k); }
   static int evaluate(icp_handle *h, const double *s, size_t n, const icp_pose *T, double max_dist, Q *out) {
     return icp_evaluate_point_to_plane_device(h, s, n, T, max_dist, out, nullptr);
   }
-  static uint64_t *counters(icp_batch *b) { return b->pqctr; }
+  static uint64_t *counters(icp_batch *b) { return b->ctr[icp_batch::kPlaneQuality]; }
 };
 
 // One by one: the first failing step's status is the item's -- ICP_EMPTY_DST and ICP_BAD_ARGUMENT (targets the normals
@@ -789,9 +757,7 @@ extern "C" int icp_batch_evaluate_point_to_line(icp_batch *b, const double *src,
 }
 
 extern "C" int icp_batch_line_quality_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->lqctr[q];
-  return ICP_OK;
+  return counters_out(b, icp_batch::kLineQuality, out);
 }
 
 // ---- section 20: the two entries with the point-to-plane residual (3-D batches, 3 <= k <= 16) ----
@@ -810,17 +776,9 @@ extern "C" int icp_batch_evaluate_point_to_plane(icp_batch *b, const double *src
 }
 
 extern "C" int icp_batch_plane_quality_counters(icp_batch *b, uint64_t out[4]) {
-  if (!b || !out) return ICP_BAD_ARGUMENT;
-  for (int q = 0; q < 4; ++q) out[q] = b->pqctr[q];
-  return ICP_OK;
+  return counters_out(b, icp_batch::kPlaneQuality, out);
 }
 
 extern "C" int icp_debug_plane_quality_batch_plan(unsigned m, uint32_t out[4]) {
-  if (!out || m < 1 || m > kPlaneQualityMaxM) return ICP_BAD_ARGUMENT;
-  const PlanePlan plan = plane_quality_plan_of(m);
-  out[0] = plan.list_threads;
-  out[1] = plan.shared_bytes;
-  out[2] = plan.fixed_bytes;
-  out[3] = plan.lds_bytes;
-  return ICP_OK;
+  return plan_out(m >= 1 && m <= kPlaneQualityMaxM, out, [&] { return normal_quality_plan<3>(m); });
 }

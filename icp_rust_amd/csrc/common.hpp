@@ -541,42 +541,28 @@ size_t tiny_lds_bytes_of(int dim, unsigned m);
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
-// EXTENSION: batched point-to-line registration (p2line_batch.hip: k_line_estimate_batch; api_batch.hip drives it).  One
-// workgroup per item computes the item's line normals (k neighbours) and runs the whole registration; items, results,
-// inner counts and indices as for launch_tiny_estimate_batch.  Workgroups of 512 (n <= 512) or 1024 threads.
+// EXTENSION: batched registration with a normal-based residual, one workgroup per item (api_batch.hip drives it): the
+// point-to-line residual of 2-D items (DIM 2; p2line_batch.hip: k_line_estimate_batch) and the point-to-plane residual of
+// 3-D items (DIM 3; p2plane_batch.hip: k_plane_estimate_batch).  A workgroup computes its item's normals (k neighbours)
+// and runs the whole registration; items, results, inner counts, indices and *granted as for
+// launch_tiny_estimate_batch.  Workgroups of 512 (n <= 512) or 1024 threads.  GATED: the same with a maximum
+// correspondence distance (k_line_estimate_gated_batch, k_plane_estimate_gated_batch): r2 = max_dist^2, formed in f64 by
+// the caller; inliers: count x max_iter kept counts (pinned host memory, or null), laid out like `inner`.  Ungated
+// launches ignore both.  Each of the four (DIM, GATED) is defined beside its kernels, with its own grant.
 constexpr unsigned kLineBatchMaxN = 1024, kLineBatchMaxM = 2048, kLineBatchMaxIter = 1024;
-inline unsigned line_batch_threads(size_t n) { return n <= 512 ? 512u : 1024u; }
-hipError_t launch_line_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
-                                      const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
-                                      TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
-// EXTENSION: the same with a maximum correspondence distance (k_line_estimate_gated_batch): r2 = max_dist^2, formed in
-// f64 by the caller; inliers: count x max_iter kept counts (pinned host memory, or null), laid out like `inner`.
-hipError_t launch_line_estimate_gated_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
-                                            const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
-                                            double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
-                                            uint32_t *inliers, hipStream_t stream, bool *granted);
-// EXTENSION: batched point-to-plane registration of 3-D items (p2plane_batch.hip: k_plane_estimate_batch; api_batch.hip
-// drives it).  One workgroup per item computes the item's plane normals (k neighbours) and runs the whole registration;
-// items, results, inner counts, indices, workgroup sizes and *granted as for launch_line_estimate_batch.
 constexpr unsigned kPlaneBatchMaxN = 1024, kPlaneBatchMaxM = 2048, kPlaneBatchMaxIter = 1024;
-inline unsigned plane_batch_threads(size_t n) { return n <= 512 ? 512u : 1024u; }
-hipError_t launch_plane_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
-                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
-                                       TinyResult *res, uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
-// the LDS plan of such a launch: the targets whose k-best lists a round of the normals holds, the
-// bytes of the region the sort keys, the lists and the sort buffers share in turn, the bytes beside it, and their sum
-struct PlanePlan {
+inline unsigned normal_batch_threads(size_t n) { return n <= 512 ? 512u : 1024u; }
+template <int DIM, bool GATED>
+hipError_t launch_normal_estimate_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
+                                        const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k, double r2,
+                                        TinyResult *res, uint32_t *inner, uint32_t *d_idx, uint32_t *inliers,
+                                        hipStream_t stream, bool *granted);
+// the LDS plan of such a launch, and of a quality's below (normal_batch_device.hpp: normal_batch_plan): the targets whose
+// k-best lists a round of the normals holds, the bytes of the region the sort keys, the lists and what runs behind them
+// share in turn, the bytes beside it, and their sum
+struct NormalPlan {
   unsigned list_threads, shared_bytes, fixed_bytes, lds_bytes;
 };
-PlanePlan plane_batch_plan_of(unsigned threads, unsigned m_max);
-// EXTENSION: the same with a maximum correspondence distance (k_plane_estimate_gated_batch): r2 =
-// max_dist^2, formed in f64 by the caller; inliers: count x max_iter kept counts (pinned host memory, or null), laid out
-// like `inner`.  Its plan: the ungated one with the gate's words behind the sort buffers.
-hipError_t launch_plane_estimate_gated_batch(unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
-                                             const TinyBatchItem *d_items, unsigned count, unsigned max_iter, int k,
-                                             double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
-                                             uint32_t *inliers, hipStream_t stream, bool *granted);
-PlanePlan plane_gated_batch_plan_of(unsigned threads, unsigned m_max);
 // A record of the fold tree of section 9 (fold_device.hpp): SUMS sums that are doubles, the inlier count and whether some
 // residual was NaN.
 template <int SUMS>
@@ -612,26 +598,18 @@ using NormalQualityPart = FoldPart<kNormalQualitySums>;
 using LineQualityPart = NormalQualityPart;
 static_assert(sizeof(NormalQualityPart) == 96, "twelve doubles per record: ceil(n / 256) of them fit in max(n, 256)");
 int line_quality_result(size_t n, const LineQualityPart &p, icp_line_quality *q);
-// icp_batch_evaluate_point_to_line (api_batch.hip): items of up to kLineQualityMaxN source and kLineQualityMaxM target
-// points run as one workgroup of 1024 threads each (k_line_quality_batch), which computes the item's line normals from k
-// neighbours and writes res[slot] with pad = 0; a workgroup that hands its item back leaves res[slot] alone (the host
-// presets pad != 0).  *granted as for launch_tiny_estimate_batch.
-constexpr unsigned kLineQualityMaxN = 1024, kLineQualityMaxM = 2048;
-hipError_t launch_line_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
-                                     const QualityBatchItem *d_items, unsigned count, double r2, int k,
-                                     LineQualityPart *res, hipStream_t stream, bool *granted);
-// EXTENSION: the same under the point-to-plane residual for 3-D batches (quality_plane_batch.hip: k_plane_quality_batch;
-// include/icp_mi355x.h section 20; api_batch.hip drives it): one workgroup of 1024 threads per item computes the item's
-// plane normals from k neighbours and writes res[slot] with pad = 0; hand-backs and *granted as for
-// launch_line_quality_batch.  The limits are launch_plane_estimate_batch's.
-constexpr unsigned kPlaneQualityMaxN = 1024, kPlaneQualityMaxM = 2048;
 int plane_quality_result(size_t n, const NormalQualityPart &p, icp_plane_quality *q);
-hipError_t launch_plane_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
-                                      const QualityBatchItem *d_items, unsigned count, double r2, int k,
-                                      NormalQualityPart *res, hipStream_t stream, bool *granted);
-// its LDS plan: the rounds of the normals, the region the sort keys, the lists and the fold share
-// in turn, the bytes beside it, and their sum
-PlanePlan plane_quality_plan_of(unsigned m_max);
+// icp_batch_evaluate_point_to_line / _plane (api_batch.hip; include/icp_mi355x.h sections 16 and 20): items of up to 1024
+// source and 2048 target points run as one workgroup of 1024 threads each (DIM 2: quality_line.hip: k_line_quality_batch;
+// DIM 3: quality_plane_batch.hip: k_plane_quality_batch), which computes the item's normals from k neighbours and writes
+// res[slot] with pad = 0; a workgroup that hands its item back leaves res[slot] alone (the host presets pad != 0).
+// *granted as for launch_tiny_estimate_batch.  Each DIM is defined beside its kernel, with its own grant.
+constexpr unsigned kLineQualityMaxN = 1024, kLineQualityMaxM = 2048;
+constexpr unsigned kPlaneQualityMaxN = 1024, kPlaneQualityMaxM = 2048;
+template <int DIM>
+hipError_t launch_normal_quality_batch(unsigned m_max, const double *d_src, const double *d_dst,
+                                       const QualityBatchItem *d_items, unsigned count, double r2, int k,
+                                       NormalQualityPart *res, hipStream_t stream, bool *granted);
 // three launches around a predicted window (gn_win.hip); h_res->overflow == 2 when it missed
 bool window_usable(const icp_handle *h, size_t n, WinParams *P, int kind = 2, bool any_n = false,
                    double f_override = 0.);

@@ -1,8 +1,8 @@
 // What the kernels that compute line normals share (p2line.hip: k_line_normals, through the target grid;
 // p2line_batch.hip: k_line_estimate_batch and quality_line.hip: k_line_quality_batch, a sweep over the workgroup's own
-// targets): everything behind the k best neighbours -- ONE statement of include/icp_mi355x.h section 14's mean,
-// covariance, Jacobi rotation, column choice, normalisation and sign, so that they cannot drift apart -- and, for the
-// two one-workgroup kernels, the sweep itself.
+// targets, normal_batch_device.hpp: normals_of_sorted_targets<2>): everything behind the k best neighbours -- ONE
+// statement of include/icp_mi355x.h section 14's mean, covariance, Jacobi rotation, column choice, normalisation and
+// sign, so that they cannot drift apart.
 #pragma once
 #include "common.hpp"
 #include "tiny_device.hpp"
@@ -63,38 +63,6 @@ __device__ __forceinline__ void line_normal_of_neighbours(int cnt, Coord coord, 
     nrm[0] = n0;
     nrm[1] = n1;
   }
-}
-
-// ---- the line normals of a workgroup's own targets (the one-workgroup kernels: k_line_estimate_batch,
-// k_line_quality_batch) ----
-// Per target the k best by (d^2, index) from a sweep outwards over the targets SORTED BY x in LDS (tiny_sort_targets;
-// tiny_device.hpp: tiny_k_best_of_target, which the plane normals of p2plane_batch.hip share), L targets per round with
-// their lists in `shared` ((8 + 4) B x kLineKMax x L, free again on return), then line_normal_of_neighbours ->
-// nrm[sorted position].  kk: the entries' k,
-// clamped here to m.  Every thread of the workgroup calls it; it ends with a barrier.
-__device__ __forceinline__ void line_normals_of_sorted_targets(const TinyTargets &tg, double cx, double cy, double scale,
-                                                               int kk, unsigned L, unsigned char *shared, double2 *nrm) {
-  const unsigned tid = threadIdx.x, m = tg.m;
-  const double *tx = tg.tx, *ty = tg.ty;
-  double *ld = reinterpret_cast<double *>(shared);                // [kLineKMax][L]: d^2
-  uint32_t *li = reinterpret_cast<uint32_t *>(ld + kLineKMax * L);  // [kLineKMax][L]: (index << 16) | sorted position
-  int k = kk < (int)m ? kk : (int)m;
-  k = k < kLineKMax ? k : kLineKMax;  // (the entries refuse k > 16: this only keeps the lists inside their rows)
-  for (unsigned base = 0; base < m; base += L) {
-    const unsigned j = base + tid;
-    if (tid < L && j < m) {
-      double *bd = ld + tid;
-      uint32_t *bi = li + tid;
-      const int cnt = tiny_k_best_of_target<2>(tg, j, cx, cy, 0., scale, k, L, bd, bi);
-      double nv[2];
-      line_normal_of_neighbours(cnt, [&](int q, int d) {
-        const unsigned pos = (unsigned)__double_as_longlong(bd[q * L]);
-        return d == 0 ? tx[pos] : ty[pos];
-      }, nv);
-      nrm[j] = make_double2(nv[0], nv[1]);
-    }
-  }
-  __syncthreads();
 }
 
 }  // namespace icp

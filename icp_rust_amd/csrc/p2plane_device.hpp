@@ -1,8 +1,8 @@
 // What the point-to-plane kernels share (p2plane.hip: gather, residual, accumulate; gate_plane.hip: the gate that writes
 // the same pairs for the inliers only): the per-pair constants of an inner loop and the residual over them.
-// Also: everything behind the k best neighbours of a target, and, for the one-workgroup kernels (p2plane_batch.hip:
-// k_plane_estimate_batch, quality_plane_batch.hip: k_plane_quality_batch), the rounds that find them among the
-// workgroup's own targets.
+// Also: everything behind the k best neighbours of a target (the rounds that find them among a workgroup's own targets,
+// for the one-workgroup kernels of p2plane_batch.hip and quality_plane_batch.hip, are normal_batch_device.hpp:
+// normals_of_sorted_targets<3>).
 #pragma once
 #include "common.hpp"
 #include "tiny_device.hpp"
@@ -101,38 +101,6 @@ __device__ __forceinline__ void plane_normal_of_neighbours(int cnt, Coord coord,
       nrm[2] = n2;
     }
   }
-}
-
-// ---- the plane normals of a workgroup's own targets (the one-workgroup kernels: k_plane_estimate_batch,
-// k_plane_quality_batch) ----
-// Per target the k best by (d^2, index) (tiny_k_best_of_target<3>), L targets per round with their lists in `shared`
-// ((8 + 4) B x kTinyKBestMax x L, free again on return), then plane_normal_of_neighbours -> nrm[3 x sorted position].
-// kk: the entries' k, clamped here to m.  Every thread of the workgroup calls it; it ends with a barrier.
-__device__ __forceinline__ void plane_normals_of_sorted_targets(const TinyTargets &tg, double cx, double cy, double cz,
-                                                                double scale, int kk, unsigned L, unsigned char *shared,
-                                                                double *nrm) {
-  const unsigned tid = threadIdx.x, m = tg.m;
-  const double *tx = tg.tx, *ty = tg.ty, *tz = tg.tz;
-  double *ld = reinterpret_cast<double *>(shared);                      // [kTinyKBestMax][L]: d^2
-  uint32_t *li = reinterpret_cast<uint32_t *>(ld + kTinyKBestMax * L);  // [kTinyKBestMax][L]: (index << 16) | position
-  int k = kk < (int)m ? kk : (int)m;
-  k = k < kTinyKBestMax ? k : kTinyKBestMax;  // (the entries refuse k > 16: this only keeps the lists inside their rows)
-  for (unsigned base = 0; base < m; base += L) {  // (at most kPlaneBatchMaxM / 128 = sixteen rounds)
-    const unsigned j = base + tid;
-    if (tid < L && j < m) {
-      double *bd = ld + tid;
-      const int cnt = tiny_k_best_of_target<3>(tg, j, cx, cy, cz, scale, k, L, bd, li + tid);
-      double nv[3];
-      plane_normal_of_neighbours(cnt, [&](int q, int d) {
-        const unsigned pos = (unsigned)__double_as_longlong(bd[q * L]);
-        return d == 0 ? tx[pos] : (d == 1 ? ty[pos] : tz[pos]);
-      }, nv);
-      nrm[3 * j] = nv[0];
-      nrm[3 * j + 1] = nv[1];
-      nrm[3 * j + 2] = nv[2];
-    }
-  }
-  __syncthreads();
 }
 
 }  // namespace icp

@@ -350,8 +350,8 @@ __device__ __forceinline__ void tiny_nearest(const TinyTargets &t, double qx, do
   *orig = nbo;
 }
 
-// ---- the k nearest targets of a target (the normals of the one-workgroup kernels: p2line_device.hpp:
-// line_normals_of_sorted_targets, p2plane_batch.hip: plane_normals_of_sorted_targets) ----
+// ---- the k nearest targets of a target (the normals of the one-workgroup kernels: normal_batch_device.hpp:
+// normals_of_sorted_targets<DIM>) ----
 // The k best by (d^2, index) of the target at sorted position j, from a sweep outwards over the targets SORTED BY x
 // (exact: the k-nearest set under that order is unique), one target per calling thread.  bd / bi: the thread's list in
 // LDS, kTinyKBestMax entries each, entry q at [q * L].  Returns how many were found (min(k, m)); on return bd[q * L]

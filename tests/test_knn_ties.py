@@ -2,7 +2,7 @@
 continuous random clouds of the other suites never go: exact ties at the k-th place, candidates outside the visited
 block at the distance of the current k-th, coincident targets, clouds far from the origin, clipped k.  Three device
 searches choose those neighbours -- k_target_normals (3-D grid), k_line_normals (2-D grid) and the one-workgroup sweep
-line_normals_of_sorted_targets behind the batch kernels -- and none returns its lists: the observable is the normal,
+normals_of_sorted_targets<DIM> behind the batch kernels -- and none returns its lists: the observable is the normal,
 so the clouds (tests/tie_clouds.py: lattices, every d^2 exact) make the normal depend on which tied candidates got in.
 
 The CPU tests prove that on the inputs themselves: most rows tie at the k-th place, the covariances are well

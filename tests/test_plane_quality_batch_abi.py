@@ -5,7 +5,7 @@ outside the packed arrays -- rejected before the device is touched, count == 0 a
 refusals and return shapes (with a library that is not the real one); the LDS plan at its corners and its invariants at
 every m (DESIGN.md section 9o derives the figures); the kernel's cross-compile for gfx950 within the budget of the
 1024-thread kernels, and the four instantiations of p2plane_batch.hip within theirs now that the normals' rounds live in
-p2plane_device.hpp; and what the call is for, on the CPU: 64 hypotheses of a thinned corridor and of a closed room
+one header for the line and the plane kernels (normal_batch_device.hpp); and what the call is for, on the CPU: 64 hypotheses of a thinned corridor and of a closed room
 (imported by tests/test_gpu_plane_quality_batch.py), scored by the numpy restatement with the oracle's normals."""
 import ctypes as C
 import os
@@ -298,9 +298,18 @@ def test_plane_estimate_batch_kernels_keep_their_budgets_with_the_normals_in_the
             u = use[names[0]]
             print(names[0], u)
             assert u["vgpr"] <= vgpr and u["scratch"] <= scratch and u["lds"] == 0, (names[0], u)
-    text = open(os.path.join(CSRC, "p2plane_batch.hip")).read()
-    assert "void plane_normals_of_sorted_targets" not in text  # one statement, in the header, two callers
-    assert "void plane_normals_of_sorted_targets" in open(os.path.join(CSRC, "p2plane_device.hpp")).read()
+    # one statement of the normals' rounds, in a header, in none of the .hip files: the line and the plane kernels, the
+    # estimates and the qualities, all call csrc/normal_batch_device.hpp: normals_of_sorted_targets<DIM>
+    name = "void normals_of_sorted_targets"
+    for src in sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")):
+        text = open(os.path.join(CSRC, src)).read()
+        assert name not in text and "_normals_of_sorted_targets" not in text, src
+    where = [h for h in sorted(os.listdir(CSRC)) if h.endswith((".hpp", ".inc"))
+             and "normals_of_sorted_targets(const" in open(os.path.join(CSRC, h)).read()]
+    assert where == ["normal_batch_device.hpp"], where
+    assert open(os.path.join(CSRC, "normal_batch_device.hpp")).read().count(name + "(const") == 1
+    for src in ("p2line_batch.hip", "p2plane_batch.hip", "quality_line.hip", "quality_plane_batch.hip"):
+        assert '#include "normal_batch_device.hpp"' in open(os.path.join(CSRC, src)).read(), src
 
 
 # ------------------------------------------------------------------ what it is for (shared with the GPU file)

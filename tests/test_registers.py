@@ -103,7 +103,15 @@ ONE_WORKGROUP_BEFORE_SHARING = {
         "k_tiny_estimate_batchILi3ELj512E": (148, 0), "k_tiny_estimate_batchILi3ELj768E": (148, 0),
         "k_tiny_estimate_batchILi3ELj1024E": (128, 104),
     },
-    "p2line_batch.hip": {"k_line_estimate_batchILj512E": (135, 0), "k_line_estimate_batchILj1024E": (128, 48)},
+    "p2line_batch.hip": {"k_line_estimate_batchILj512E": (135, 0), "k_line_estimate_batchILj1024E": (128, 48),
+                         # ... and as the build before csrc/normal_batch_device.hpp reported the kernels whose bodies it holds
+                         "k_line_estimate_gated_batchILj512E": (125, 0), "k_line_estimate_gated_batchILj1024E": (128, 44)},
+    "p2plane_batch.hip": {
+        "k_plane_estimate_batchILj512E": (126, 0), "k_plane_estimate_batchILj1024E": (127, 0),
+        "k_plane_estimate_gated_batchILj512E": (133, 0), "k_plane_estimate_gated_batchILj1024E": (128, 36),
+    },
+    "quality_line.hip": {"k_line_quality_batchE": (128, 0)},
+    "quality_plane_batch.hip": {"k_plane_quality_batchE": (90, 0)},
 }
 
 
