@@ -785,59 +785,39 @@ class _Icp:
         `max_correspondence_distance=r` (include/icp_mi355x.h section 12): the inner loop of each outer iteration sees
         only the pairs whose nearest target lies within r of the moved source point (d2 <= r * r, evaluate's inlier
         rule), in the caller's order; `return_info` then returns (T, idx, inner, inliers).  None: the ungated call."""
-        if max_correspondence_distance is not None:
-            return self._estimate_point_to_plane_gated(src, initial_transform, max_iter, return_info,
-                                                       max_correspondence_distance)
-        o = Transform()
-        inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
-        if _is_device_tensor(src):
-            import torch
+        return self._estimate_normal("icp_estimate_point_to_plane", src, initial_transform, max_iter, return_info,
+                                     max_correspondence_distance)
 
-            self._dev(src, "src")
-            n = src.shape[0]
-            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_info else None
-            check(lib().icp_estimate_point_to_plane_device(self._h, C.c_void_p(src.data_ptr()), n,
-                                                           C.byref(initial_transform.pose), max_iter, C.byref(o.pose),
-                                                           C.c_void_p(idx.data_ptr()) if return_info else None,
-                                                           C.c_void_p(inner.ctypes.data)),
-                  "icp_estimate_point_to_plane_device")
-            return (o, idx[:n].cpu().numpy().view(np.uint32), inner[:max_iter]) if return_info else o
-        s = _host(src, self.DIM)
-        n = s.shape[0]
-        idx = np.zeros(max(n, 1), dtype=np.uint32)
-        check(lib().icp_estimate_point_to_plane(self._h, _ptr(s), n, C.byref(initial_transform.pose), max_iter,
-                                                C.byref(o.pose), C.c_void_p(idx.ctypes.data),
-                                                C.c_void_p(inner.ctypes.data)), "icp_estimate_point_to_plane")
-        return (o, idx[:n], inner[:max_iter]) if return_info else o
-
-    def _estimate_point_to_plane_gated(self, src, initial_transform, max_iter, return_info, bound):
-        r = float(bound)
-        if not r >= 0.0:  # (also a NaN)
+    def _estimate_normal(self, stem, src, initial_transform, max_iter, return_info, bound):
+        """the four entries `stem`[_gated][_device] of a registration under a normal residual (plane or line)"""
+        gated = bound is not None
+        r = float(bound) if gated else 0.0
+        if gated and not r >= 0.0:  # (also a NaN)
             raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {bound!r}")
         o = Transform()
         inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
         inl = np.zeros(max(max_iter, 1), dtype=np.uint32)
-        if _is_device_tensor(src):
+        on_device = _is_device_tensor(src)
+        if on_device:
             import torch
 
             self._dev(src, "src")
             n = src.shape[0]
             idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_info else None
-            check(lib().icp_estimate_point_to_plane_gated_device(
-                self._h, C.c_void_p(src.data_ptr()), n, C.byref(initial_transform.pose), max_iter, r, C.byref(o.pose),
-                C.c_void_p(idx.data_ptr()) if return_info else None, C.c_void_p(inner.ctypes.data),
-                C.c_void_p(inl.ctypes.data)), "icp_estimate_point_to_plane_gated_device")
-            if not return_info:
-                return o
-            return o, idx[:n].cpu().numpy().view(np.uint32), inner[:max_iter], inl[:max_iter]
-        s = _host(src, self.DIM)
-        n = s.shape[0]
-        idx = np.zeros(max(n, 1), dtype=np.uint32)
-        check(lib().icp_estimate_point_to_plane_gated(self._h, _ptr(s), n, C.byref(initial_transform.pose), max_iter, r,
-                                                      C.byref(o.pose), C.c_void_p(idx.ctypes.data),
-                                                      C.c_void_p(inner.ctypes.data), C.c_void_p(inl.ctypes.data)),
-              "icp_estimate_point_to_plane_gated")
-        return (o, idx[:n], inner[:max_iter], inl[:max_iter]) if return_info else o
+            sp, ip = C.c_void_p(src.data_ptr()), (C.c_void_p(idx.data_ptr()) if return_info else None)
+        else:
+            s = _host(src, self.DIM)
+            n = s.shape[0]
+            idx = np.zeros(max(n, 1), dtype=np.uint32)
+            sp, ip = _ptr(s), C.c_void_p(idx.ctypes.data)
+        name = stem + ("_gated" if gated else "") + ("_device" if on_device else "")
+        args = [self._h, sp, n, C.byref(initial_transform.pose), max_iter] + ([r] if gated else [])
+        args += [C.byref(o.pose), ip, C.c_void_p(inner.ctypes.data)] + ([C.c_void_p(inl.ctypes.data)] if gated else [])
+        check(getattr(lib(), name)(*args), name)
+        if not return_info:
+            return o
+        idx = idx[:n].cpu().numpy().view(np.uint32) if on_device else idx[:n]
+        return (o, idx, inner[:max_iter], inl[:max_iter]) if gated else (o, idx, inner[:max_iter])
 
     # -- EXTENSION (not in the reference): the quality of a pose under the plane residual, section 13 --
     def evaluate_point_to_plane(self, src, transform, max_correspondence_distance=float("inf"), return_indices=False):
@@ -911,34 +891,8 @@ class _Icp:
         target lies within r of the moved source point (d2 <= r * r), in the caller's order; `return_info` then returns
         (T, idx, inner, inliers).  None: the ungated call."""
         self._need_2d("estimate_point_to_line")
-        gated = max_correspondence_distance is not None
-        r = float(max_correspondence_distance) if gated else 0.0
-        if gated and not r >= 0.0:  # (also a NaN)
-            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
-        o = Transform()
-        inner = np.zeros(max(max_iter, 1), dtype=np.uint32)
-        inl = np.zeros(max(max_iter, 1), dtype=np.uint32)
-        on_device = _is_device_tensor(src)
-        if on_device:
-            import torch
-
-            self._dev(src, "src")
-            n = src.shape[0]
-            idx = torch.empty(max(n, 1), dtype=torch.int32, device=src.device) if return_info else None
-            sp, ip = C.c_void_p(src.data_ptr()), (C.c_void_p(idx.data_ptr()) if return_info else None)
-        else:
-            s = _host(src, self.DIM)
-            n = s.shape[0]
-            idx = np.zeros(max(n, 1), dtype=np.uint32)
-            sp, ip = _ptr(s), C.c_void_p(idx.ctypes.data)
-        name = "icp_estimate_point_to_line" + ("_gated" if gated else "") + ("_device" if on_device else "")
-        args = [self._h, sp, n, C.byref(initial_transform.pose), max_iter] + ([r] if gated else [])
-        args += [C.byref(o.pose), ip, C.c_void_p(inner.ctypes.data)] + ([C.c_void_p(inl.ctypes.data)] if gated else [])
-        check(getattr(lib(), name)(*args), name)
-        if not return_info:
-            return o
-        idx = idx[:n].cpu().numpy().view(np.uint32) if on_device else idx[:n]
-        return (o, idx, inner[:max_iter], inl[:max_iter]) if gated else (o, idx, inner[:max_iter])
+        return self._estimate_normal("icp_estimate_point_to_line", src, initial_transform, max_iter, return_info,
+                                     max_correspondence_distance)
 
     # -- EXTENSION (not in the reference): the quality of a pose under the line residual, section 16 --
     def evaluate_point_to_line(self, src, transform, max_correspondence_distance=float("inf"), return_indices=False):

@@ -1,6 +1,6 @@
-// C ABI, EXTENSIONS beyond the reference (include/icp_mi355x.h sections 6 and 7): a target cloud that grows
-// (scan-to-map, BASELINE.json configs[4]) and point-to-plane residuals.  Split out of api.hip in round 5; the hot path
-// of the reference (Icp{2,3}d::new / estimate and the stage calls) lives in api.hip.
+// C ABI, EXTENSION beyond the reference (include/icp_mi355x.h section 6): a target cloud that grows (scan-to-map,
+// BASELINE.json configs[4]).  Split out of api.hip in round 5; the hot path of the reference (Icp{2,3}d::new / estimate
+// and the stage calls) lives in api.hip, the point-to-plane residuals of section 7 in api_normal.hip.
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -164,227 +164,3 @@ extern "C" int icp_read_targets(icp_handle *h, size_t first, size_t k, double *o
   HIP_TRY(hipStreamSynchronize(h->stream));
   return ICP_OK;
 }
-
-// ------------------------------------------- EXTENSION: point-to-plane residuals -----
-// Not in the reference (no normals anywhere in src/); definition and CPU restatement: p2plane.hip,
-// the CPU checker under tests (tests/test_p2plane.py).  Everything around the residual is the reference's: exact 3-D
-// nearest neighbour, SE(2) pose on xy, Huber / MAD Gauss-Newton, the inner loop's break tests.
-namespace icp {
-namespace api {
-
-// What icp_compute_target_normals and icp_compute_target_line_normals (api_line.hip) share once each has decided on the
-// handle's dimension: `launch` is the normals kernel of that dimension.  The normals are m x 3 either way.
-int compute_normals_with(icp_handle *h, int k, NormalsLaunch launch) {
-  if (h->m == 0) return ICP_EMPTY_DST;
-  if (!h->grid.built) return ICP_BAD_ARGUMENT;  // non-finite targets: no grid to search neighbourhoods with
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(reserve(h->d_normals, h->cap_normals, h->m * 3));
-  HIP_TRY(launch(h, k, h->d_normals, 0));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->normals_m = h->m;
-  h->normals_k = k;
-  return ICP_OK;
-}
-
-// ... and the two update entries: the targets behind normals_m get theirs, the older ones keep what they have
-int update_normals_with(icp_handle *h, int k, NormalsLaunch launch) {
-  if (h->m == 0) return ICP_EMPTY_DST;
-  if (!h->grid.built || h->normals_m > h->m) return ICP_BAD_ARGUMENT;
-  if (h->normals_m > 0 && h->normals_k != k) return ICP_BAD_ARGUMENT;  // one neighbourhood size per cloud
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->m * 3 > h->cap_normals || !h->d_normals) {  // grow, keeping the normals that exist
-    double *old = h->d_normals;
-    const size_t keep = h->normals_m * 3;
-    h->d_normals = nullptr;
-    h->cap_normals = 0;
-    hipError_t e = reserve(h->d_normals, h->cap_normals, h->m * 3);
-    if (e == hipSuccess && old && keep)
-      e = hipMemcpyAsync(h->d_normals, old, keep * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(old);
-    if (e != hipSuccess) {
-      h->normals_m = 0;
-      return map_hip(e);
-    }
-  }
-  HIP_TRY(launch(h, k, h->d_normals, h->normals_m));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->normals_m = h->m;
-  h->normals_k = k;
-  return ICP_OK;
-}
-
-}  // namespace api
-}  // namespace icp
-
-extern "C" int icp_compute_target_normals(icp_handle *h, int k) {
-  if (!h || h->dim != 3 || k < 3 || k > 16) return ICP_BAD_ARGUMENT;
-  return compute_normals_with(h, k, launch_target_normals);
-}
-
-// The targets appended since the normals were last computed get theirs (from their k nearest targets in the cloud
-// as it is NOW); the older targets keep the normals they have -- "normals at insertion time", the definition a map that
-// grows frame by frame uses (a full icp_compute_target_normals re-derives all of them from the current cloud).
-extern "C" int icp_update_target_normals(icp_handle *h, int k) {
-  if (!h || h->dim != 3 || k < 3 || k > 16) return ICP_BAD_ARGUMENT;
-  return update_normals_with(h, k, launch_target_normals);
-}
-
-extern "C" int icp_read_target_normals(icp_handle *h, size_t first, size_t count, double *out) {
-  if (!h || h->normals_m != h->m || h->m == 0 || first > h->m || count > h->m - first || (count > 0 && !out))
-    return ICP_BAD_ARGUMENT;
-  if (count == 0) return ICP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipMemcpyAsync(out, h->d_normals + first * 3, count * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return ICP_OK;
-}
-
-namespace icp {
-namespace api {
-
-// the per-pair scratch of a point-to-plane inner loop
-int ensure_plane_buffers(icp_handle *h, size_t n) {
-  if (n > h->cap_plane) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_plane_pairs);
-    (void)hipFree(h->d_plane_fa);
-    (void)hipFree(h->d_plane_fb);
-    h->d_plane_pairs = nullptr;
-    h->d_plane_fa = h->d_plane_fb = nullptr;
-    h->cap_plane = 0;
-    HIP_TRY(hipMalloc(&h->d_plane_pairs, n * p2pl_pair_bytes()));
-    HIP_TRY(hipMalloc(&h->d_plane_fa, n * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->d_plane_fb, n * 2 * sizeof(double)));
-    h->cap_plane = n;
-  }
-  return ICP_OK;
-}
-
-// ... and the staging buffer of its gate (gate_plane.hip: n pairs; only a gated call asks for it)
-int ensure_plane_stage(icp_handle *h, size_t n) {
-  if (n > h->cap_plane_stage) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_plane_stage);
-    h->d_plane_stage = nullptr;
-    h->cap_plane_stage = 0;
-    HIP_TRY(hipMalloc(&h->d_plane_stage, n * p2pl_pair_bytes()));
-    h->cap_plane_stage = n;
-  }
-  return ICP_OK;
-}
-
-// The inner loop (src/lib.rs:59-84 around the plane residual) on the k pairs in h->d_plane_pairs, whoever wrote them
-// (the gather of all correspondences, or the gate's survivors): the pose update dT and the updates applied.  Fewer than
-// two pairs: check_input_size -- the identity, no update.
-int p2pl_loop_on_pairs(icp_handle *h, size_t k, Pose *dT, uint32_t *applied_out) {
-  Workspace &w = h->ws;
-  Pose Ti = transform_identity();
-  uint32_t applied = 0;
-  if (k >= 2) {
-    double prev_error = DBL_MAX;
-    for (int it = 0; it < ICP_INNER_MAX_ITER; ++it) {
-      HIP_TRY(launch_p2pl_eval(h, h->d_plane_pairs, k, Ti, h->d_plane_fa, h->d_plane_fb));
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      const GnResult &r = *w.h_res;
-      if (r.nan_flag) return ICP_NAN_INPUT;
-      double delta[3];
-      if (!solve_update(r.acc, r.acc + 9, delta)) break;
-      if ((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < ICP_DELTA_NORM_THRESHOLD) break;
-      if (r.acc[12] > prev_error) break;
-      prev_error = r.acc[12];
-      Ti = transform_mul(transform_new(delta), Ti);
-      ++applied;
-    }
-  }
-  *dT = Ti;
-  if (applied_out) *applied_out = applied;
-  return ICP_OK;
-}
-
-}  // namespace api
-}  // namespace icp
-
-// One outer iteration's inner loop for given correspondences d_idx of the WHOLE source cloud under pose T: make the
-// pairs (one gather), loop on them.  (icp_multi_estimate_point_to_plane runs this on every rank after the ranks have
-// exchanged the indices of their slices.)
-int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
-                               icp_pose *dT, uint32_t *applied_out) {
-  if (!h || h->dim != 3 || !T || !dT || (n > 0 && (!d_src || !d_idx)) || h->normals_m != h->m || h->m == 0) return ICP_BAD_ARGUMENT;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n, false));
-  ICP_TRY_RC(ensure_plane_buffers(h, n));
-  HIP_TRY(launch_p2pl_gather(h, d_src, n, *T, d_idx, h->d_normals, h->d_plane_pairs));
-  return p2pl_loop_on_pairs(h, n, dT, applied_out);
-}
-
-// ... with a maximum correspondence distance (include/icp_mi355x.h section 12): the gate makes the pairs of the inliers
-// only (gate_plane.hip: two launches and the wait that brings their number), the loop runs on those.
-int icp_p2pl_gated_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
-                                     double max_dist, icp_pose *dT, uint32_t *applied_out, size_t *kept) {
-  if (!h || h->dim != 3 || !T || !dT || !kept || (n > 0 && (!d_src || !d_idx)) || !(max_dist >= 0.) ||
-      h->normals_m != h->m || h->m == 0)
-    return ICP_BAD_ARGUMENT;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, workspace_points(n), false));
-  ICP_TRY_RC(ensure_plane_buffers(h, n));
-  ICP_TRY_RC(ensure_plane_stage(h, n));
-  HIP_TRY(launch_gate_plane(h, d_src, n, *T, d_idx, max_dist * max_dist, h->d_plane_pairs, nullptr));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  *kept = gate_count(h);
-  return p2pl_loop_on_pairs(h, *kept, dT, applied_out);
-}
-
-extern "C" int icp_estimate_point_to_plane_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *init,
-                                                  size_t max_iter, icp_pose *out, uint32_t *d_last_idx,
-                                                  uint32_t *inner_iters) {
-  if (!h || h->dim != 3 || !init || !out || (n > 0 && !d_src) || n >= 0xffffffffull) return ICP_BAD_ARGUMENT;
-  if (h->m == 0) {  // index.unwrap() on an empty tree, src/lib.rs:165 -- only when a search would run
-    if (n > 0 && max_iter > 0) return ICP_EMPTY_DST;
-    *out = *init;
-    return ICP_OK;
-  }
-  if (h->normals_m != h->m) return ICP_BAD_ARGUMENT;  // icp_compute_target_normals first (again after an append)
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n, false));
-  ICP_TRY_RC(ensure_plane_buffers(h, n));
-  Workspace &w = h->ws;
-  Pose T = *init;
-  if (max_iter > 0) {
-    const int prc = icp_prepare_source_device(h, d_src, n, init);
-    if (prc != ICP_OK) return prc;
-  }
-  Quiesce quiesce_on_exit{h};
-  for (size_t it = 0; it < max_iter; ++it) {
-    uint32_t *idx = (it + 1 == max_iter && d_last_idx) ? d_last_idx : w.d_idx;
-    int rc = icp_correspond_device(h, d_src, n, &T, nullptr, nullptr, idx);  // exact 3-D NN, src/lib.rs:161-167
-    if (rc != ICP_OK) return rc;
-    Pose Ti;
-    uint32_t applied = 0;
-    rc = icp_p2pl_inner_loop_device(h, d_src, n, &T, idx, &Ti, &applied);
-    if (rc != ICP_OK) return rc;
-    if (inner_iters) inner_iters[it] = applied;
-    T = transform_mul(Ti, T);
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  *out = T;
-  return ICP_OK;
-}
-
-extern "C" int icp_estimate_point_to_plane(icp_handle *h, const double *src, size_t n, const icp_pose *init,
-                                           size_t max_iter, icp_pose *out, uint32_t *last_idx, uint32_t *inner_iters) {
-  if (!h || h->dim != 3 || !init || !out || (n > 0 && !src) || n >= 0xffffffffull) return ICP_BAD_ARGUMENT;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(ensure_workspace(h, n, true));
-  if (n > 0)
-    HIP_TRY(hipMemcpyAsync(h->ws.d_src, src, n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  uint32_t *d_li = nullptr;
-  if (last_idx && n > 0) HIP_TRY(hipMalloc(&d_li, n * sizeof(uint32_t)));
-  int rc = icp_estimate_point_to_plane_device(h, h->ws.d_src, n, init, max_iter, out, d_li, inner_iters);
-  if (rc == ICP_OK && d_li && max_iter > 0) {
-    if (hipMemcpy(last_idx, d_li, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = ICP_HIP_ERROR;
-  }
-  (void)hipFree(d_li);
-  return rc;
-}
-

@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share (api.hip: handles, stage calls, the loops of Icp::estimate; api_shard.hip:
-// the sharded registration; api_ext.hip: the extensions beyond the reference).  Internal: nothing here is exported
-// (csrc/exports.map).
+// the sharded registration; api_ext.hip, api_normal.hip and the others: the extensions beyond the reference).  Internal:
+// nothing here is exported (csrc/exports.map).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -102,28 +102,21 @@ int estimate_transform_on_pairs(icp_handle *h, const double *d_a, const double *
 hipError_t launch_gate(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
                        double *d_a, double *d_b, uint32_t *d_kept);
 size_t gate_count(const icp_handle *h);
-// ... of a point-to-plane registration (gate_plane.hip): the same compaction, fused with what k_p2pl_gather does -- the
-// survivors' PlanePairs (8 doubles each) in d_pairs, their source positions in d_kept (nullable); the count as above.
-// Needs ensure_workspace(max(n, 256)), ensure_plane_stage(n) and current normals.
-hipError_t launch_gate_plane(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
-                             void *d_pairs, uint32_t *d_kept);
-// ... of a point-to-line registration on a 2-D handle (p2line.hip): the same, the clouds read at a stride of 2
-hipError_t launch_gate_line(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
-                            void *d_pairs, uint32_t *d_kept);
-// compute / update the targets' normals with the normals kernel of the handle's dimension (api_ext.hip; the callers
-// have checked h, k and the dimension)
-using NormalsLaunch = hipError_t (*)(icp_handle *h, int k, double *d_normals, size_t first);
-int compute_normals_with(icp_handle *h, int k, NormalsLaunch launch);
-int update_normals_with(icp_handle *h, int k, NormalsLaunch launch);
-// the per-pair scratch of a point-to-plane inner loop, and the staging buffer of its gate (api_ext.hip)
+// ... of a registration under a normal residual (gate_plane.hip): the same compaction, fused with what the gather of the
+// handle's dimension does -- the survivors' PlanePairs (8 doubles each; dz = nz = 0 on a 2-D handle) in d_pairs, their
+// source positions in d_kept (nullable); the count as above.  Needs ensure_workspace(max(n, 256)), ensure_plane_stage(n)
+// and current normals.
+hipError_t launch_gate_normal(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx, double r2,
+                              void *d_pairs, uint32_t *d_kept);
+// the per-pair scratch of an inner loop under a normal residual, and the staging buffer of its gate (api_normal.hip)
 int ensure_plane_buffers(icp_handle *h, size_t n);
 int ensure_plane_stage(icp_handle *h, size_t n);
-// the inner loop (src/lib.rs:59-84 around the plane residual) on the k pairs in h->d_plane_pairs (api_ext.hip)
+// the inner loop (src/lib.rs:59-84 around the plane residual) on the k pairs in h->d_plane_pairs (api_normal.hip)
 int p2pl_loop_on_pairs(icp_handle *h, size_t k, Pose *dT, uint32_t *applied_out);
 
 }  // namespace api
 }  // namespace icp
-// One outer iteration's point-to-plane inner loop for given correspondences of the whole source cloud (api_ext.hip), and
+// One outer iteration's point-to-plane inner loop for given correspondences of the whole source cloud (api_normal.hip), and
 // the same on the inliers of a gate at max_dist (*kept: their number)
 int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
                                icp_pose *dT, uint32_t *applied_out);

@@ -689,14 +689,12 @@ hipError_t multi_wait(hipStream_t s, const unsigned *const *flags, int world, un
 hipError_t multi_sum_hist(hipStream_t s, const void *const *hists, int world, uint32_t *out);
 hipError_t multi_put_pairs(hipStream_t s, const double *a_loc, const double *b_loc, size_t n_total, int rank, int world,
                            double *a_full, double *b_full);
-// EXTENSION: point-to-plane residuals (p2plane.hip)
-hipError_t launch_target_normals(icp_handle *h, int k, double *d_normals, size_t first = 0);
-hipError_t launch_p2pl_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
-                              const double *d_normals, void *d_pairs);
-// ... and their 2-D twins (p2line.hip): line normals (stored m x 3 with nz = +0.0) and the pairs with dz = nz = 0
-hipError_t launch_line_normals(icp_handle *h, int k, double *d_normals, size_t first);
-hipError_t launch_line_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
-                              const double *d_normals, void *d_pairs);
+// EXTENSION: point-to-plane and point-to-line residuals (p2plane.hip)
+// (the normals and the pairs of the handle's dimension: plane normals on 3-D, line normals -- stored m x 3 with
+// nz = +0.0, pairs with dz = nz = 0 -- on 2-D)
+hipError_t launch_normals(icp_handle *h, int k, double *d_normals, size_t first);
+hipError_t launch_normal_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
+                                const double *d_normals, void *d_pairs);
 hipError_t launch_p2pl_eval(icp_handle *h, const void *d_pairs, size_t n, const Pose &T, double *d_fa, double *d_fb);
 size_t p2pl_pair_bytes();
 // unweighted accumulation (gauss_newton_update / error / huber_error)

@@ -564,7 +564,7 @@ __device__ __forceinline__ void normal_estimate_item(const double *__restrict__ 
       hasp = tid < cnt;
       blocks = cnt > 512u ? 2 : 1;
     }
-    // ---- p2pl_loop_on_pairs (api_ext.hip) on the cnt pairs (pair_loop_device.hpp) ----
+    // ---- p2pl_loop_on_pairs (api_normal.hip) on the cnt pairs (pair_loop_device.hpp) ----
     tiny_pair_loop<B>(pr, hasp, cnt, blocks, C, sbuf, sm, tot, [&]() {
       if constexpr (GATED) {
         if (hasp) gate.pair(tid, pr, tg, nrm, src, C);

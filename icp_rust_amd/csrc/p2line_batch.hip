@@ -1,6 +1,6 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 15): batched point-to-LINE registration, one workgroup per
 // item.  Item i's result is what icp_create(2, dst_i) + icp_compute_target_line_normals(k) + icp_estimate_point_to_line
-// return on a fresh handle, bit for bit (section 14; p2line.hip, p2plane.hip, api_ext.hip: p2pl_loop_on_pairs), or the
+// return on a fresh handle, bit for bit (section 14; p2plane.hip, api_normal.hip: p2pl_loop_on_pairs), or the
 // workgroup hands the item back (TinyResult::status = -1) and api_batch.hip serves it through exactly those entries.
 // Nothing crosses workgroups: no flag, no atomic, no barrier across them.  What a workgroup does is
 // normal_batch_device.hpp: normal_estimate_item<2, B, GATED>, the body the plane kernels (p2plane_batch.hip) run with
@@ -22,7 +22,7 @@
 // Hand-back reasons: a box that is not finite; a NaN target coordinate; a rotation update outside the restated range of
 // sin / cos.  A NaN residual is the item's ICP_NAN_INPUT.
 // Section 17, k_line_estimate_gated_batch: the same body with the gate of icp_estimate_point_to_line_gated between the
-// search and the inner loop -- the pairs with d2 <= r^2 (p2line.hip: k_lngate_stage's expressions), compacted in thread
+// search and the inner loop -- the pairs with d2 <= r^2 (gate_plane.hip: k_lngate_stage's expressions), compacted in thread
 // order (NormalGate<2, B>: the moved point and the position of its match), and p2pl_loop_on_pairs on the `kept` of them
 // in the tree of reduce_geometry(kept).
 // The LDS plan of a launch (DESIGN.md sections 9j and 9l): normal_estimate_plan<2, GATED>.

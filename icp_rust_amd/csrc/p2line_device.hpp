@@ -1,4 +1,4 @@
-// What the kernels that compute line normals share (p2line.hip: k_line_normals, through the target grid;
+// What the kernels that compute line normals share (p2plane.hip: k_line_normals, through the target grid;
 // p2line_batch.hip: k_line_estimate_batch and quality_line.hip: k_line_quality_batch, a sweep over the workgroup's own
 // targets, normal_batch_device.hpp: normals_of_sorted_targets<2>): everything behind the k best neighbours -- ONE
 // statement of include/icp_mi355x.h section 14's mean, covariance, Jacobi rotation, column choice, normalisation and
@@ -8,8 +8,6 @@
 #include "tiny_device.hpp"
 
 namespace icp {
-
-constexpr int kLineKMax = kTinyKBestMax;
 
 // The line normal from the `cnt` neighbours found, in their (d^2, index) order: coord(j, d) is coordinate d of the j-th.
 // Fewer than 3 neighbours, or a zero-length eigenvector: the zero vector.

@@ -14,8 +14,23 @@
 //                            sigma == 0, exactly as the reference treats each of its two rows;
 //   Jacobian row           = n_xy^T [R | R (-a_y, a_x)^T] with the reference's jacobian() (:176-184);
 //   Huber error            = sum rho(r^2).
+// Point-to-LINE residuals for 2-D handles (include/icp_mi355x.h section 14, "PLICP") are the same definition with the
+// third coordinate removed:
+//   normal of a target q   = unit eigenvector of the smaller eigenvalue of the 2 x 2 covariance of the k targets nearest
+//                            to q in the xy plane (q itself included; ordered by (d^2, index), d^2 = dx dx + dy dy), one
+//                            Jacobi rotation of the pair (0, 1) in f64 (jacobi3's update sequence; skipped when
+//                            a[0][1] == 0), the smaller diagonal (a tie: column 0), normalised by sqrt(n0 n0 + n1 n1),
+//                            sign: first non-zero of (n_y, n_x) positive; fewer than 3 neighbours or zero length: zero.
+// The normals live in the handle's d_normals with a stride of 3 and nz = +0.0, the pairs are the PlanePair of
+// p2plane_device.hpp with dz = 0, nz = 0: weights, Jacobian row, Huber error and the inner loop are the kernels below
+// (launch_p2pl_eval), which do not know the dimension.  An independent numpy statement of the line normals:
+// tests/test_line_abi.py.
+//   k_target_normals / k_line_normals   one lane per target, Chebyshev rings of the grid, k-best in LDS
+//   k_p2pl_gather / k_line_gather       the pairs of all correspondences (src and dst with a stride of 3 / 2)
+// One body behind each pair of kernels: normal_single_device.hpp.
 #include "common.hpp"
 #include "gn_device.hpp"
+#include "normal_single_device.hpp"
 #include "p2plane_device.hpp"
 
 namespace icp {
@@ -24,100 +39,33 @@ hipError_t launch_stddevs(icp_handle *h, const double *d_a, const double *d_b, s
 __global__ void k_final_reduce(const double *__restrict__ partials, int blocks, int nacc,
                                const GnScalars *__restrict__ scal, GnResult *__restrict__ res);
 
-constexpr int kNormalKMax = 16;
+// (jacobi3 and everything behind the k best neighbours: p2plane_device.hpp, plane_normal_of_neighbours; the 2-D twin:
+// p2line_device.hpp, line_normal_of_neighbours; the bodies of the four kernels below: normal_single_device.hpp)
 
-// (jacobi3 and everything behind the k best neighbours: p2plane_device.hpp, plane_normal_of_neighbours)
-
-// One lane per target: its k nearest targets through the grid (Chebyshev rings of cells around its
-// own cell until the k-th distance is covered by the visited block), then the covariance's smallest
-// eigenvector.  The running k-best lists live in LDS (dynamic indexing).
 __global__ __launch_bounds__(64) void k_target_normals(const double *__restrict__ dst, unsigned m, GridParams g,
                                                        const uint32_t *__restrict__ start,
                                                        const GridPoint *__restrict__ pts, int kk,
                                                        double *__restrict__ normals, unsigned first) {
-  __shared__ double s_d[64][kNormalKMax];
-  __shared__ uint32_t s_i[64][kNormalKMax];
-  const unsigned i = first + blockIdx.x * 64 + threadIdx.x;  // (targets [first, m): all of them, or the appended ones)
-  if (i >= m) return;
-  double *bd = s_d[threadIdx.x];
-  uint32_t *bi = s_i[threadIdx.x];
-  const double p[3] = {dst[(size_t)i * 3], dst[(size_t)i * 3 + 1], dst[(size_t)i * 3 + 2]};
-  int c[3];
-  for (int d = 0; d < 3; ++d) {
-    double t = floor((p[d] - g.lo[d]) * g.inv_h[d]);
-    t = fmin(fmax(t, 0.), (double)(g.n[d] - 1));
-    c[d] = (int)t;
-  }
-  const int k = kk < (int)m ? kk : (int)m;
-  int cnt = 0;
-  const int rmax = max(max(g.n[0], g.n[1]), g.n[2]);
-  for (int r = 1; r <= rmax; ++r) {
-    cnt = 0;
-    const int x0 = max(c[0] - r * g.fx, 0), x1 = min(c[0] + r * g.fx, g.n[0] - 1);
-    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.n[1] - 1);
-    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.n[2] - 1);
-    for (int iz = z0; iz <= z1; ++iz)
-      for (int iy = y0; iy <= y1; ++iy) {
-        const uint32_t row = ((uint32_t)iz * g.n[1] + iy) * g.n[0];
-        const uint32_t s = start[row + x0], e = start[row + x1 + 1];
-        for (uint32_t j = s; j < e; ++j) {
-          const uint32_t ti = pts[j].idx;
-          const double dx = p[0] - dst[(size_t)ti * 3], dy = p[1] - dst[(size_t)ti * 3 + 1],
-                       dz = p[2] - dst[(size_t)ti * 3 + 2];
-          const double dd = (dx * dx + dy * dy) + dz * dz;
-          // A NaN distance (a NaN coordinate in either target) is no neighbour: (d^2, index) does not order it, and a
-          // list that took it in would depend on the order of the records inside a cell, which the grid's scatter
-          // leaves to its atomics -- the normals of such a cloud would differ from one handle to the next.
-          if (dd != dd) continue;
-          // insertion by (d^2, index) into the k best
-          if (cnt == k && !(dd < bd[k - 1] || (dd == bd[k - 1] && ti < bi[k - 1]))) continue;
-          int pos = cnt < k ? cnt : k - 1;
-          while (pos > 0 && (dd < bd[pos - 1] || (dd == bd[pos - 1] && ti < bi[pos - 1]))) {
-            bd[pos] = bd[pos - 1];
-            bi[pos] = bi[pos - 1];
-            --pos;
-          }
-          bd[pos] = dd;
-          bi[pos] = ti;
-          if (cnt < k) ++cnt;
-        }
-      }
-    // is everything outside the visited block strictly farther than the k-th best?
-    double cover = __builtin_huge_val();
-    for (int d = 0; d < 3; ++d) {
-      const int w = d == 0 ? r * g.fx : r;
-      if (c[d] - w > 0) cover = fmin(cover, p[d] - (g.lo[d] + (c[d] - w) * g.h[d]));
-      if (c[d] + w < g.n[d] - 1) cover = fmin(cover, (g.lo[d] + (c[d] + w + 1) * g.h[d]) - p[d]);
-    }
-    if (cover == __builtin_huge_val()) break;  // the whole grid
-    cover -= 1e-9 * (g.scale + fabs(p[0]) + fabs(p[1]) + fabs(p[2]));
-    if (cnt == k && cover > 0. && bd[k - 1] < cover * cover) break;
-  }
-  double nrm[3];
-  plane_normal_of_neighbours(cnt, [&](int j, int d) { return dst[(size_t)bi[j] * 3 + d]; }, nrm);
-  normals[(size_t)i * 3] = nrm[0];
-  normals[(size_t)i * 3 + 1] = nrm[1];
-  normals[(size_t)i * 3 + 2] = nrm[2];
+  target_normals_by_grid<3>(dst, m, g, start, pts, kk, normals, first);
 }
 
-// (PlanePair, the per-pair constants of an inner loop, and plane_residual: p2plane_device.hpp)
+__global__ __launch_bounds__(64) void k_line_normals(const double *__restrict__ dst, unsigned m, GridParams g,
+                                                     const uint32_t *__restrict__ start,
+                                                     const GridPoint *__restrict__ pts, int kk,
+                                                     double *__restrict__ normals, unsigned first) {
+  target_normals_by_grid<2>(dst, m, g, start, pts, kk, normals, first);
+}
+
 __global__ void k_p2pl_gather(const double *__restrict__ src, unsigned n, Pose T, const uint32_t *__restrict__ idx,
                               const double *__restrict__ dst, const double *__restrict__ normals,
                               PlanePair *__restrict__ out) {
-  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double x = src[(size_t)i * 3], y = src[(size_t)i * 3 + 1], z = src[(size_t)i * 3 + 2];
-  const uint32_t j = idx[i];
-  PlanePair o;
-  o.ax = (T.r00 * x + T.r01 * y) + T.tx;  // Transform::transform, src/transform.rs:22-24
-  o.ay = (T.r10 * x + T.r11 * y) + T.ty;
-  o.qx = dst[(size_t)j * 3];
-  o.qy = dst[(size_t)j * 3 + 1];
-  o.dz = z - dst[(size_t)j * 3 + 2];
-  o.nx = normals[(size_t)j * 3];
-  o.ny = normals[(size_t)j * 3 + 1];
-  o.nz = normals[(size_t)j * 3 + 2];
-  out[i] = o;
+  normal_gather<3>(src, n, T, idx, dst, 0u, normals, out);  // (m: only the 2-D gather clamps by it)
+}
+
+__global__ void k_line_gather(const double *__restrict__ src, unsigned n, Pose T, const uint32_t *__restrict__ idx,
+                              const double *__restrict__ dst, unsigned m, const double *__restrict__ normals,
+                              PlanePair *__restrict__ out) {
+  normal_gather<2>(src, n, T, idx, dst, m, normals, out);
 }
 
 // residuals as the pairs ((r, 0), (0, 0)): launch_stddevs under the identity pose then selects the
@@ -161,19 +109,26 @@ __global__ __launch_bounds__(kReduceThreads) void k_p2pl_accumulate(const PlaneP
   block_reduce_store<kNAcc>(acc, partials + (size_t)blockIdx.x * (kNAcc + 1));
 }
 
-hipError_t launch_target_normals(icp_handle *h, int k, double *d_normals, size_t first) {
+// the normals of the targets [first, m) with the kernel of the handle's dimension (m x 3 either way)
+hipError_t launch_normals(icp_handle *h, int k, double *d_normals, size_t first) {
   const unsigned m = (unsigned)h->m;
   if (first >= h->m) return hipSuccess;
-  hipLaunchKernelGGL(k_target_normals, dim3((m - (unsigned)first + 63) / 64), dim3(64), 0, h->stream, h->d_dst, m, h->grid.p,
-                     (const uint32_t *)h->grid.d_start, (const GridPoint *)h->grid.d_pts, k, d_normals, (unsigned)first);
+  hipLaunchKernelGGL(h->dim == 3 ? k_target_normals : k_line_normals, dim3((m - (unsigned)first + 63) / 64), dim3(64), 0,
+                     h->stream, h->d_dst, m, h->grid.p, (const uint32_t *)h->grid.d_start, (const GridPoint *)h->grid.d_pts, k,
+                     d_normals, (unsigned)first);
   return hipGetLastError();
 }
 
-hipError_t launch_p2pl_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
-                              const double *d_normals, void *d_pairs) {
+hipError_t launch_normal_gather(icp_handle *h, const double *d_src, size_t n, const Pose &T, const uint32_t *d_idx,
+                                const double *d_normals, void *d_pairs) {
   if (n == 0) return hipSuccess;  // (an empty scan: no pair, and a grid of no workgroups is not a launch)
-  hipLaunchKernelGGL(k_p2pl_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_src, (unsigned)n, T,
-                     d_idx, h->d_dst, d_normals, (PlanePair *)d_pairs);
+  const dim3 blocks((unsigned)((n + 255) / 256));
+  if (h->dim == 3)
+    hipLaunchKernelGGL(k_p2pl_gather, blocks, dim3(256), 0, h->stream, d_src, (unsigned)n, T, d_idx, h->d_dst, d_normals,
+                       (PlanePair *)d_pairs);
+  else
+    hipLaunchKernelGGL(k_line_gather, blocks, dim3(256), 0, h->stream, d_src, (unsigned)n, T, d_idx, h->d_dst,
+                       (unsigned)h->m, d_normals, (PlanePair *)d_pairs);
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // EXTENSION beyond the reference (include/icp_mi355x.h section 18): batched point-to-PLANE registration, one workgroup per
 // 3-D item.  Item i's result is what icp_create(3, dst_i) + icp_compute_target_normals(k) + icp_estimate_point_to_plane
-// return on a fresh handle, bit for bit (p2plane.hip's header comment and api_ext.hip: p2pl_loop_on_pairs are the
+// return on a fresh handle, bit for bit (p2plane.hip's header comment and api_normal.hip: p2pl_loop_on_pairs are the
 // definition), or the workgroup hands the item back (TinyResult::status = -1) and api_batch.hip serves it through exactly
 // those entries.  Nothing crosses workgroups: no flag, no atomic, no barrier across them; every loop has a static bound
 // (the rounds of the normals, jacobi3's 12 sweeps, ICP_INNER_MAX_ITER, max_iter).  What a workgroup does is

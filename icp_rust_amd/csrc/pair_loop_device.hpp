@@ -1,7 +1,7 @@
 // What the one-workgroup estimators with a normal-based residual share (p2line_batch.hip: k_line_estimate_batch,
 // k_line_estimate_gated_batch; p2plane_batch.hip: k_plane_estimate_batch, k_plane_estimate_gated_batch; their body is
 // normal_batch_device.hpp: normal_estimate_item): the inner loop on the pairs of one outer
-// iteration -- api_ext.hip: p2pl_loop_on_pairs, with k_p2pl_accumulate's statement -- ONE copy, so that the line and the
+// iteration -- api_normal.hip: p2pl_loop_on_pairs, with k_p2pl_accumulate's statement -- ONE copy, so that the line and the
 // plane residual cannot drift apart.  A line pair is a plane pair with nz = dz = +0.0.
 #pragma once
 #include "common.hpp"

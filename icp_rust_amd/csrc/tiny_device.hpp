@@ -468,7 +468,7 @@ struct TinyCtl {
   unsigned applied, evals;
 };
 
-// The decision behind one inner evaluation (src/lib.rs:66-82; api_ext.hip: p2pl_loop_on_pairs takes the same steps),
+// The decision behind one inner evaluation (src/lib.rs:66-82; api_normal.hip: p2pl_loop_on_pairs takes the same steps),
 // on thread 0 alone: the solve, the three break tests in the reference's order, then Transform::new * Ti.  tot: the
 // combined totals, jtj[9] | jtr[3] | error.
 __device__ __forceinline__ void tiny_inner_decide(TinyCtl *C, const double *tot) {

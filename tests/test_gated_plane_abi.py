@@ -159,20 +159,36 @@ def _usage(src):
     return regs
 
 
+# (VGPRs, scratch bytes per lane) of the 3-D kernels as the build reported them while each had a body of its own, before
+# csrc/normal_single_device.hpp and gate_plane.hip's normal_gate_stage put one body behind them and their 2-D twins
+PLANE_KERNELS_BEFORE_SHARING = {
+    "gate_plane.hip": {"k_plgate_stage": (78, 0), "k_plgate_place": (30, 0)},
+    "p2plane.hip": {"k_target_normals": (72, 0), "k_p2pl_gather": (24, 0)},
+}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 def test_plane_gate_kernels_do_not_spill_and_leave_room_for_four_waves_per_simd():
-    """no scratch and at most 128 VGPRs (512 per lane of a SIMD: four waves) in every kernel of gate_plane.hip; the
-    names stay clear of the budgeted search / evaluation kernels (tests/test_registers.py) and of the fragments
-    tests/test_gated_abi.py counts gate.hip's kernels by"""
+    """no scratch and at most 128 VGPRs (512 per lane of a SIMD: four waves) in every kernel of gate_plane.hip -- the
+    stage kernels of both dimensions, the chunk sums, the one place kernel; the names stay clear of the budgeted search /
+    evaluation kernels (tests/test_registers.py) and of the fragments tests/test_gated_abi.py counts gate.hip's kernels
+    by; the 3-D kernels, here and in p2plane.hip, need no more than before they shared a body with their 2-D twins"""
     from test_registers import BUDGET
 
     regs = _usage("gate_plane.hip")
     kernels = [k for k in regs if not k.endswith("#scratch")]
-    for frag in ("k_plgate_stage", "k_compact_chunks", "k_plgate_place"):
+    for frag in ("k_plgate_stage", "k_lngate_stage", "k_compact_chunks", "k_plgate_place"):
         assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
-    assert len(kernels) == 3, kernels
+    assert len(kernels) == 4, kernels
     for k in kernels:
         assert regs.get(k + "#scratch", 0) == 0, (k, regs.get(k + "#scratch"))
         assert regs[k] <= 128, (k, regs[k])
         assert not any(frag in k for frag in BUDGET), k
         assert not any(frag in k for frag in ("k_gate_stage", "k_gate_chunks", "k_gate_place")), k
+    for src, table in PLANE_KERNELS_BEFORE_SHARING.items():
+        regs = _usage(src) if src != "gate_plane.hip" else regs
+        for frag, (vgprs, scratch) in table.items():
+            names = [k for k in regs if frag in k and not k.endswith("#scratch")]
+            assert len(names) == 1, (frag, names)
+            assert regs[names[0]] <= vgprs, f"{names[0]}: {regs[names[0]]} VGPRs > {vgprs}"
+            assert regs.get(names[0] + "#scratch", 0) <= scratch, f"{names[0]}: scratch"

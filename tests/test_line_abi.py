@@ -168,7 +168,7 @@ def test_symbols_are_declared_exported_and_bound():
         assert s in _lib.SIGNATURES and hasattr(L, s), s
         assert hasattr(I.lib(), s)
     mk = open(os.path.join(ROOT, "icp_rust_amd", "csrc", "Makefile")).read()
-    assert "p2line.hip" in mk and "api_line.hip" in mk
+    assert "p2plane.hip" in mk and "gate_plane.hip" in mk and "api_normal.hip" in mk
     for name in ("compute_line_normals", "update_line_normals", "read_line_normals", "estimate_point_to_line"):
         assert callable(getattr(I.Icp2d, name)), name
 
@@ -405,20 +405,41 @@ def _usage(src):
     return regs
 
 
+# (VGPRs, scratch bytes per lane) of the 2-D kernels as the build reported them while each had a body of its own in
+# p2line.hip, before csrc/normal_single_device.hpp put one body behind them and their 3-D twins
+LINE_KERNELS_BEFORE_SHARING = {
+    "p2plane.hip": {"k_line_normals": (54, 0), "k_line_gather": (22, 0)},
+    "gate_plane.hip": {"k_lngate_stage": (72, 0)},
+}
+# every kernel of the two translation units the 2-D kernels live in, beside their 3-D twins
+KERNELS = {
+    "p2plane.hip": ("k_line_normals", "k_line_gather", "k_target_normals", "k_p2pl_gather", "k_p2pl_residual",
+                    "k_p2pl_accumulate"),
+    "gate_plane.hip": ("k_lngate_stage", "k_plgate_stage", "k_compact_chunks", "k_plgate_place"),
+}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 def test_line_kernels_do_not_spill_and_leave_room_for_four_waves_per_simd():
-    """exactly the kernels of p2line.hip; no scratch and at most 128 VGPRs in each; the names stay clear of the budgeted
-    search / evaluation kernels (tests/test_registers.py) and of the fragments the other files' kernels are counted by"""
+    """exactly the kernels of p2plane.hip and gate_plane.hip, which hold the 2-D kernels beside their 3-D twins; no
+    scratch and at most 128 VGPRs in each; the 2-D kernels need no more than before they shared a body with the twins; the
+    names stay clear of the budgeted search / evaluation kernels (tests/test_registers.py) and of the fragments the other
+    file's kernels are counted by"""
     from test_registers import BUDGET
 
-    regs = _usage("p2line.hip")
-    kernels = [k for k in regs if not k.endswith("#scratch")]
-    for frag in ("k_line_normals", "k_line_gather", "k_lngate_stage", "k_compact_chunks"):
-        assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
-    assert len(kernels) == 4, kernels
-    for k in kernels:
-        assert regs.get(k + "#scratch", 0) == 0, (k, regs.get(k + "#scratch"))
-        assert regs[k] <= 128, (k, regs[k])
-        assert not any(frag in k for frag in BUDGET), k
-        assert not any(frag in k for frag in ("k_plgate_stage", "k_plgate_place", "k_gate_stage", "k_target_normals",
-                                              "k_p2pl_gather")), k
+    for src, frags in KERNELS.items():
+        regs = _usage(src)
+        kernels = [k for k in regs if not k.endswith("#scratch")]
+        for frag in frags:
+            assert len([k for k in kernels if frag in k]) == 1, (frag, kernels)
+        assert len(kernels) == len(frags), kernels
+        others = [f for other, fs in KERNELS.items() if other != src for f in fs if f not in frags]
+        for k in kernels:
+            assert regs.get(k + "#scratch", 0) == 0, (k, regs.get(k + "#scratch"))
+            assert regs[k] <= 128, (k, regs[k])
+            assert not any(frag in k for frag in BUDGET), k
+            assert not any(frag in k for frag in others + ["k_gate_stage"]), k
+        for frag, (vgprs, scratch) in LINE_KERNELS_BEFORE_SHARING[src].items():
+            name = [k for k in kernels if frag in k][0]
+            assert regs[name] <= vgprs, f"{name}: {regs[name]} VGPRs > {vgprs}"
+            assert regs.get(name + "#scratch", 0) <= scratch, f"{name}: scratch"
