@@ -267,6 +267,10 @@ SIGNATURES = {
                                                            _vp]),
     "icp_batch_plane_quality_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_debug_plane_quality_batch_plan": (C.c_int, [C.c_uint, C.POINTER(C.c_uint32)]),
+    "icp_batch_estimate_gated": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "icp_batch_estimate_gated_device": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, C.c_double, _vp, _vp, _vp, _vp,
+                                                  _vp]),
+    "icp_batch_gated_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -1097,24 +1097,42 @@ class IcpBatch:
             raise ValueError(f"{len(inits)} initial transforms for {count} items")
         return inits
 
-    def estimate(self, srcs, dsts, inits, max_iter, return_info=False, allow_failures=False):
+    @staticmethod
+    def _bound(max_correspondence_distance):
+        """the gated entries' max_dist, or None for the ungated ones; refused here, before the library is reached"""
+        if max_correspondence_distance is None:
+            return None
+        r = float(max_correspondence_distance)
+        if not r >= 0.0:  # (also a NaN)
+            raise ValueError(f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
+        return r
+
+    def estimate(self, srcs, dsts, inits, max_iter, return_info=False, allow_failures=False,
+                 max_correspondence_distance=None):
         """Register srcs[i] against dsts[i] from inits[i] (a list, one Transform for all, or None: identity).  Returns
         the list of Transforms; with return_info also the per-item indices, the inner counts (count x max_iter) and the
-        statuses.  A failed item raises IcpError naming it, unless allow_failures=True (its Transform is then None)."""
-        src, dst, items = self._pack_items(srcs, dsts, inits)
-        return self.estimate_packed(src, dst, items, max_iter, return_info, allow_failures)
+        statuses.  A failed item raises IcpError naming it, unless allow_failures=True (its Transform is then None).
 
-    def estimate_packed(self, src, dst, items, max_iter, return_info=False, allow_failures=False):
+        `max_correspondence_distance=r` (icp_batch_estimate_gated*, section 21): item i is what
+        Icp{2,3}d(dsts[i]).estimate(srcs[i], inits[i], max_iter, max_correspondence_distance=r) returns, bit for bit --
+        the inner loop of each outer iteration sees only the pairs within r; `return_info` then returns (Ts, idxs,
+        inner, status, inliers), inliers count x max_iter.  None: the ungated call."""
+        src, dst, items = self._pack_items(srcs, dsts, inits)
+        return self.estimate_packed(src, dst, items, max_iter, return_info, allow_failures, max_correspondence_distance)
+
+    def estimate_packed(self, src, dst, items, max_iter, return_info=False, allow_failures=False,
+                        max_correspondence_distance=None):
         """The same over pre-packed clouds: `items` = [(src_first, n, dst_first, m, init Transform), ...] ranges of
-        `src` / `dst` (ranges may overlap).  numpy arrays go through icp_batch_estimate; contiguous float64 CUDA tensors
-        through icp_batch_estimate_device, in place."""
-        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, None)
+        `src` / `dst` (ranges may overlap).  numpy arrays go through icp_batch_estimate[_gated]; contiguous float64 CUDA
+        tensors through icp_batch_estimate[_gated]_device, in place."""
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, None,
+                                     self._bound(max_correspondence_distance))
 
     def _estimate_packed(self, src, dst, items, max_iter, return_info, allow_failures, line_k, max_dist=None,
                          normals_entry="icp_batch_estimate_point_to_line"):
-        """estimate_packed (line_k None), estimate_point_to_line_packed (line_k = the normals' neighbours; max_dist:
-        the gated entries, which also fill the inlier counts) and estimate_point_to_plane_packed (normals_entry: its
-        entry, which takes the same arguments)"""
+        """estimate_packed (line_k None), estimate_point_to_line_packed (line_k = the normals' neighbours) and
+        estimate_point_to_plane_packed (normals_entry: its entry, which takes the same arguments); max_dist: the gated
+        entries of each, which also fill the inlier counts"""
         count = len(items)
         name = "icp_batch_estimate" if line_k is None else normals_entry
         name = what = name + ("" if max_dist is None else "_gated")
@@ -1172,15 +1190,18 @@ class IcpBatch:
         info = (Ts, idxs, inner[:count * max_iter].reshape(count, max_iter), status)
         return info if max_dist is None else info + (inl[:count * max_iter].reshape(count, max_iter),)
 
-    def estimate_hypotheses(self, src, dst, inits, max_iter):
+    def estimate_hypotheses(self, src, dst, inits, max_iter, max_correspondence_distance=None):
         """One scan against one map from K initial poses (one shared src range and dst range: nothing is copied per
         hypothesis).  Returns (Transforms, errors): errors[k] is huber_error of the k-th result on its last
         correspondences (src/lib.rs:45-50, xy of the points), so that the caller can keep the best hypothesis.
-        (evaluate() scores poses on the device instead, on the correspondences AT each returned pose.)"""
+        (evaluate() scores poses on the device instead, on the correspondences AT each returned pose.)
+        `max_correspondence_distance=r`: every hypothesis is registered with the gate (estimate_packed); the errors are
+        scored as without it, on the last correspondences of all points."""
         s, d = _host(src, self.DIM), _host(dst, self.DIM)
         inits = self._inits(inits, len(inits) if not isinstance(inits, Transform) else 1)
         items = [(0, s.shape[0], 0, d.shape[0], T) for T in inits]
-        Ts, idxs, _, _ = self.estimate_packed(s, d, items, max_iter, return_info=True)
+        Ts, idxs = self.estimate_packed(s, d, items, max_iter, return_info=True,
+                                        max_correspondence_distance=max_correspondence_distance)[:2]
         a = np.ascontiguousarray(s[:, :2])
         errs = [huber_error(T, a, np.ascontiguousarray(d[ix.astype(np.int64), :2])) for T, ix in zip(Ts, idxs)]
         return Ts, np.array(errs)
@@ -1212,13 +1233,8 @@ class IcpBatch:
         self._need_2d("estimate_point_to_line_packed")
         if not 3 <= int(k) <= 16:
             raise ValueError(f"k must be in [3, 16], got {k!r}")
-        r = None
-        if max_correspondence_distance is not None:
-            r = float(max_correspondence_distance)
-            if not r >= 0.0:  # (also a NaN)
-                raise ValueError(
-                    f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
-        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), r)
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k),
+                                     self._bound(max_correspondence_distance))
 
     # -- EXTENSION: the same with the point-to-plane residual for 3-D items (icp_batch_estimate_point_to_plane*,
     # section 18) --
@@ -1249,14 +1265,8 @@ class IcpBatch:
         self._need_3d("estimate_point_to_plane_packed")
         if not 3 <= int(k) <= 16:
             raise ValueError(f"k must be in [3, 16], got {k!r}")
-        r = None
-        if max_correspondence_distance is not None:
-            r = float(max_correspondence_distance)
-            if not r >= 0.0:  # (also a NaN)
-                raise ValueError(
-                    f"max_correspondence_distance must be >= 0 (or +inf), got {max_correspondence_distance!r}")
-        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k), r,
-                                     "icp_batch_estimate_point_to_plane")
+        return self._estimate_packed(src, dst, items, max_iter, return_info, allow_failures, int(k),
+                                     self._bound(max_correspondence_distance), "icp_batch_estimate_point_to_plane")
 
     def plane_counters(self):
         """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
@@ -1416,6 +1426,13 @@ class IcpBatch:
         """(items evaluated in a batch launch, items evaluated one by one, launches)"""
         out = (C.c_uint64 * 3)()
         check(lib().icp_batch_evaluate_counters(self._b, out), "icp_batch_evaluate_counters")
+        return tuple(int(x) for x in out)
+
+    def gated_counters(self):
+        """(items served in a batch launch, items served one by one, launches, launches not made for want of LDS) of
+        estimate*(..., max_correspondence_distance=r)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().icp_batch_gated_counters(self._b, out), "icp_batch_gated_counters")
         return tuple(int(x) for x in out)
 
     def counters(self):

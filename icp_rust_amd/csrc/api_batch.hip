@@ -16,6 +16,8 @@
 // icp_compute_target_normals + icp_estimate_point_to_plane_device.
 // Section 19, section 18 with a maximum correspondence distance: k_plane_estimate_gated_batch, driven the same way; one
 // by one: icp_estimate_point_to_plane_gated_device in the last step's place.
+// Section 21, section 8 with a maximum correspondence distance: k_tiny_estimate_gated_batch (gn_fast.hip), driven the
+// same way; one by one: icp_create_device + icp_estimate_gated_device.
 #include <cstring>
 #include <new>
 #include <vector>
@@ -42,11 +44,13 @@ struct icp_batch {
   size_t cap_res = 0;
   uint32_t *h_inner = nullptr;  // pinned: count x max_iter inner counts
   size_t cap_inner = 0;
-  uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (sections 17 and 19)
+  uint32_t *h_inl = nullptr;  // pinned: count x max_iter inlier counts (sections 17, 19 and 21)
   size_t cap_inl = 0;
   // what each family of entries has done, by CounterSet: {items a workgroup served, items served one by one, launches,
   // launches the runtime refused their LDS} (icp_batch_evaluate_counters: the first three)
-  enum CounterSet { kPoint, kLine, kLineGated, kPlane, kPlaneGated, kQuality, kLineQuality, kPlaneQuality, kCounterSets };
+  enum CounterSet {
+    kPoint, kPointGated, kLine, kLineGated, kPlane, kPlaneGated, kQuality, kLineQuality, kPlaneQuality, kCounterSets
+  };
   uint64_t ctr[kCounterSets][4] = {};
   // icp_batch_evaluate (section 9): its item list and the records its workgroups write (pinned)
   QualityBatchItem *d_qitems = nullptr, *h_qitems = nullptr;
@@ -124,7 +128,7 @@ struct Residual {
   uint32_t *inliers = nullptr;
 };
 
-// ---- the five estimates behind run(): what they differ in is a Kind ----
+// ---- the six estimates behind run(): what they differ in is a Kind ----
 //   kMaxN, kMaxM, kMaxIter  the items a workgroup serves
 //   threads(n)              its size
 //   launch(...)             one launch over the items of one size (inl: the pinned inlier counts, or null)
@@ -147,6 +151,25 @@ struct PointKind {  // section 8: k_tiny_estimate_batch (gn_fast.hip); icp_estim
   static int estimate(icp_handle *h, const double *s, size_t n, const icp_pose *init, size_t max_iter, const Residual &,
                       icp_pose *out, uint32_t *d_idx, uint32_t *inner, uint32_t *) {
     return icp_estimate_device(h, s, n, init, max_iter, out, d_idx, inner);
+  }
+};
+
+struct GatedPointKind {  // section 21: k_tiny_estimate_gated_batch (gn_fast.hip); icp_estimate_gated_device
+  static constexpr unsigned kMaxN = kTinyMaxN, kMaxM = kTinyMaxM, kMaxIter = kTinyMaxIter;
+  static constexpr icp_batch::CounterSet kCounters = icp_batch::kPointGated;
+  static constexpr const int (&kPerItem)[4] = PointKind::kPerItem;
+  static unsigned threads(size_t n) { return tiny_threads(n); }
+  static hipError_t launch(icp_batch *b, const Residual &res, unsigned threads, unsigned m_max, const double *d_src,
+                           const double *d_dst, const TinyBatchItem *d_items, unsigned count, unsigned max_iter,
+                           uint32_t *inner, uint32_t *d_idx, uint32_t *inl, bool *granted) {
+    // (max_dist * max_dist in f64 on the host, as icp_estimate_gated_device forms it)
+    return launch_tiny_estimate_gated_batch(b->dim, threads, m_max, d_src, d_dst, d_items, count, max_iter,
+                                            res.max_dist * res.max_dist, b->h_res, inner, d_idx, inl, b->stream, granted);
+  }
+  static int normals(icp_handle *, int) { return ICP_OK; }
+  static int estimate(icp_handle *h, const double *s, size_t n, const icp_pose *init, size_t max_iter, const Residual &res,
+                      icp_pose *out, uint32_t *d_idx, uint32_t *inner, uint32_t *inl) {
+    return icp_estimate_gated_device(h, s, n, init, max_iter, res.max_dist, out, d_idx, inner, inl);
   }
 };
 
@@ -428,6 +451,25 @@ extern "C" int icp_batch_estimate(icp_batch *b, const double *src, size_t src_po
                                   last_idx, inner_iters);
 }
 
+// ---- section 21: section 8's entries with a maximum correspondence distance (max_dist >= 0, or +inf) ----
+extern "C" int icp_batch_estimate_gated_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                               size_t dst_points, const icp_batch_item *items, size_t count,
+                                               size_t max_iter, double max_dist, icp_pose *out, int *status,
+                                               uint32_t *d_last_idx, uint32_t *inner_iters, uint32_t *inliers) {
+  if (!(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_device<GatedPointKind>(b, d_src, src_points, d_dst, dst_points, items, count, max_iter,
+                                         Residual{0, max_dist, inliers}, out, status, d_last_idx, inner_iters);
+}
+
+extern "C" int icp_batch_estimate_gated(icp_batch *b, const double *src, size_t src_points, const double *dst,
+                                        size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
+                                        double max_dist, icp_pose *out, int *status, uint32_t *last_idx,
+                                        uint32_t *inner_iters, uint32_t *inliers) {
+  if (!(max_dist >= 0.)) return ICP_BAD_ARGUMENT;  // (NaN fails the comparison)
+  return estimate_host<GatedPointKind>(b, src, src_points, dst, dst_points, items, count, max_iter,
+                                       Residual{0, max_dist, inliers}, out, status, last_idx, inner_iters);
+}
+
 // ---- section 15: the same two entries with the point-to-line residual (2-D batches, 3 <= k <= 16) ----
 extern "C" int icp_batch_estimate_point_to_line_device(icp_batch *b, const double *d_src, size_t src_points,
                                                        const double *d_dst, size_t dst_points, const icp_batch_item *items,
@@ -511,6 +553,9 @@ extern "C" int icp_batch_estimate_point_to_plane_gated(icp_batch *b, const doubl
 
 // ---- the estimates' counters and the LDS plans of the plane kernels' launches (include/icp_mi355x_debug.h) ----
 extern "C" int icp_batch_counters(icp_batch *b, uint64_t out[4]) { return counters_out(b, icp_batch::kPoint, out); }
+extern "C" int icp_batch_gated_counters(icp_batch *b, uint64_t out[4]) {
+  return counters_out(b, icp_batch::kPointGated, out);
+}
 extern "C" int icp_batch_line_counters(icp_batch *b, uint64_t out[4]) { return counters_out(b, icp_batch::kLine, out); }
 extern "C" int icp_batch_line_gated_counters(icp_batch *b, uint64_t out[4]) {
   return counters_out(b, icp_batch::kLineGated, out);

@@ -541,6 +541,13 @@ size_t tiny_lds_bytes_of(int dim, unsigned m);
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted);
+// EXTENSION: the same with a maximum correspondence distance (gn_fast.hip: k_tiny_estimate_gated_batch, with its own
+// grant): r2 = max_dist^2, formed in f64 by the caller; inliers: count x max_iter kept counts (pinned host memory, or
+// null), laid out like `inner`.
+hipError_t launch_tiny_estimate_gated_batch(int dim, unsigned threads, unsigned m_max, const double *d_src,
+                                            const double *d_dst, const TinyBatchItem *d_items, unsigned count,
+                                            unsigned max_iter, double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
+                                            uint32_t *inliers, hipStream_t stream, bool *granted);
 // EXTENSION: batched registration with a normal-based residual, one workgroup per item (api_batch.hip drives it): the
 // point-to-line residual of 2-D items (DIM 2; p2line_batch.hip: k_line_estimate_batch) and the point-to-plane residual of
 // 3-D items (DIM 3; p2plane_batch.hip: k_plane_estimate_batch).  A workgroup computes its item's normals (k neighbours)

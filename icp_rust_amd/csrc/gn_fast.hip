@@ -447,23 +447,54 @@ __device__ __forceinline__ bool tiny_select_window(unsigned long long k0, unsign
 
 // (TinyResult and the size limits kTinyMax*: common.hpp, shared with the batch call's host side, api_batch.hip)
 
+// The gate's words of a gated registration (k_tiny_estimate_gated_batch): a record per kept pair,
+// in pair order -- the moved point (x | y, f64) and the sorted position of its match -- and the 16 wave counts.  They
+// lie in the sorting path's buffers (p), which nobody uses between an outer iteration's search and its first
+// selection: a record is written and read once, in between.
+constexpr size_t kTinySortBufBytes = sizeof(unsigned long long) * 2 * 2 * 1024;
+constexpr size_t tiny_gate_bytes(unsigned threads) {
+  return (size_t)threads * (2 * sizeof(double) + sizeof(uint32_t)) + 16 * sizeof(uint32_t);
+}
+template <unsigned B>
+struct TinyGate {
+  double *qx, *qy;
+  uint32_t *nb, *cnt;
+  __device__ __forceinline__ explicit TinyGate(unsigned char *p)
+      : qx(reinterpret_cast<double *>(p)), qy(qx + B), nb(reinterpret_cast<uint32_t *>(qy + B)), cnt(nb + B) {}
+};
+
 template <int DIM, unsigned B>
 __global__ __launch_bounds__(B) void k_tiny_estimate(const double *__restrict__ src, unsigned n,
                                                         const double *__restrict__ dst, unsigned m, Pose T0,
                                                         unsigned max_iter, double cx, double cy, double cz, double scale,
                                                         TinyResult *res, uint32_t *inner_out, uint32_t *idx_out) {
+  constexpr bool GATED = false;
+  constexpr double r2 = 0.;
+  constexpr uint32_t *inl_out = nullptr;
 #include "tiny_estimate_body.inc"
 }
 
-static size_t tiny_lds_bytes(int dim, unsigned m) {
+// the LDS plan of a workgroup whose targets number at most m; the same with and without the gate
+static constexpr size_t tiny_lds_bytes(int dim, unsigned m) {
   const size_t mp = (m + 63u) & ~63u;
   size_t b = mp * (size_t)dim * sizeof(double) + (mp + 4) * sizeof(float4) + 16;
-  b += sizeof(unsigned long long) * 2 * 2 * 1024;
+  b += kTinySortBufBytes;
   b += (sizeof(TinySel) + 15) & ~size_t(15);
   b += sizeof(double) * 18 * (kNSum + 1);
   b += 512;  // Ctl
   return b;
 }
+static_assert(tiny_gate_bytes(512) == 10304 && tiny_gate_bytes(768) == 15424 && tiny_gate_bytes(1024) == 20544 &&
+                  tiny_gate_bytes(1024) <= kTinySortBufBytes,
+              "the gate's words of every workgroup size fit in the sorting path's buffers: nothing on top of the plan");
+static_assert(kTinyMaxN == 1024 && kTinyMaxM == 2048, "the corners below");
+static_assert(tiny_lds_bytes(2, 1) == 1024 + 68 * 16 + 16 + kTinySortBufBytes + ((sizeof(TinySel) + 15) & ~size_t(15)) + 2880 + 512 &&
+                  tiny_lds_bytes(3, 1) == tiny_lds_bytes(2, 1) + 512 && tiny_lds_bytes(3, 1) <= 64 * 1024,
+              "m = 1, every workgroup size, gated or not: below what needs a grant");
+static_assert(tiny_lds_bytes(2, kTinyMaxM) == tiny_lds_bytes(2, 1) + (2048 - 64) * 32 &&
+                  tiny_lds_bytes(3, kTinyMaxM) == tiny_lds_bytes(3, 1) + (2048 - 64) * 40 &&
+                  tiny_lds_bytes(3, kTinyMaxM) <= 124 * 1024 && tiny_lds_bytes(3, kTinyMaxM) <= kTinyLdsGrant,
+              "m = 2048, every workgroup size, gated or not: about 120 KB of the grant");
 
 // Icp{2,3}d::estimate for a small cloud in one launch.  *status: 0 done, 3 NaN, -1 not served (too large,
 // no bounding box, disabled, or the kernel handed the call back): the caller runs the general path.
@@ -534,58 +565,91 @@ hipError_t launch_tiny_estimate(icp_handle *h, const double *d_src, size_t n, co
 // workgroup first finds the box of its own targets (tiny_device.hpp: tiny_batch_box; a box that is not finite reports -1,
 // not served, as a single call whose handle builds no grid takes the general path).  Items are independent: no barrier,
 // flag or atomic across workgroups.
+// (the head of both batch kernels, in a macro: behind a function of its own k_tiny_estimate_batch loses its instruction
+// stream.  It puts in scope what tiny_estimate_body.inc names, but for GATED, r2 and inl_out)
+#define ICP_TINY_BATCH_ITEM_HEAD                                                                                      \
+  const TinyBatchItem &item = items[blockIdx.x]; /* (read in place: a copy of the pose would live in scratch) */     \
+  const unsigned n = item.n, m = item.m;                                                                              \
+  const double *__restrict__ src = src_all + item.src_first * DIM;                                                    \
+  const double *__restrict__ dst = dst_all + item.dst_first * DIM;                                                    \
+  TinyResult *res = res_all + item.slot;                                                                              \
+  uint32_t *inner_out = inner_all ? inner_all + (size_t)item.slot * max_iter : nullptr;                               \
+  uint32_t *idx_out = idx_all ? idx_all + item.idx_first : nullptr;                                                   \
+  const Pose &T0 = item.init;                                                                                         \
+  double cx, cy, cz, scale;                                                                                           \
+  extern __shared__ unsigned char lds_raw[]; /* (its start is the box's scratch; the body carves it up afterwards) */ \
+  if (!tiny_batch_box<DIM, B>(dst, m, reinterpret_cast<double *>(lds_raw), &cx, &cy, &cz, &scale)) {                  \
+    if (threadIdx.x == 0) res->status = -1;                                                                           \
+    return;                                                                                                           \
+  }
+
 template <int DIM, unsigned B>
 __global__ __launch_bounds__(B) void k_tiny_estimate_batch(const double *__restrict__ src_all,
                                                               const double *__restrict__ dst_all,
                                                               const TinyBatchItem *__restrict__ items, unsigned max_iter,
                                                               TinyResult *res_all, uint32_t *inner_all, uint32_t *idx_all) {
-  const TinyBatchItem &item = items[blockIdx.x];  // (read in place: a copy of the pose would live in scratch)
-  const unsigned n = item.n, m = item.m;
-  const double *__restrict__ src = src_all + item.src_first * DIM;
-  const double *__restrict__ dst = dst_all + item.dst_first * DIM;
-  TinyResult *res = res_all + item.slot;
-  uint32_t *inner_out = inner_all ? inner_all + (size_t)item.slot * max_iter : nullptr;
-  uint32_t *idx_out = idx_all ? idx_all + item.idx_first : nullptr;
-  const Pose &T0 = item.init;
-  double cx, cy, cz, scale;
-  extern __shared__ unsigned char lds_raw[];  // (its start is the box's scratch; the body carves it up afterwards)
-  if (!tiny_batch_box<DIM, B>(dst, m, reinterpret_cast<double *>(lds_raw), &cx, &cy, &cz, &scale)) {
-    if (threadIdx.x == 0) res->status = -1;
-    return;
-  }
+  ICP_TINY_BATCH_ITEM_HEAD
+  constexpr bool GATED = false;
+  constexpr double r2 = 0.;
+  constexpr uint32_t *inl_out = nullptr;
 #include "tiny_estimate_body.inc"
 }
 
+// EXTENSION (include/icp_mi355x.h section 21): the same with the gate of icp_estimate_gated
+// (section 10) in every item's outer iterations.  r2 = max_dist^2, formed in f64 by the caller; inl_all: count x max_iter
+// kept counts, laid out like inner_all, or null.
+template <int DIM, unsigned B>
+__global__ __launch_bounds__(B) void k_tiny_estimate_gated_batch(const double *__restrict__ src_all,
+                                                                 const double *__restrict__ dst_all,
+                                                                 const TinyBatchItem *__restrict__ items,
+                                                                 unsigned max_iter, double r2, TinyResult *res_all,
+                                                                 uint32_t *inner_all, uint32_t *idx_all,
+                                                                 uint32_t *inl_all) {
+  ICP_TINY_BATCH_ITEM_HEAD
+  constexpr bool GATED = true;
+  uint32_t *inl_out = inl_all ? inl_all + (size_t)item.slot * max_iter : nullptr;
+#include "tiny_estimate_body.inc"
+}
+#undef ICP_TINY_BATCH_ITEM_HEAD
+
 size_t tiny_lds_bytes_of(int dim, unsigned m) { return tiny_lds_bytes(dim, m); }
+
+// One launch of a family of six such kernels, k[DIM - 2][workgroup size: 512 | 768 | 1024], behind the family's grant
+// (the same grant as the single kernels', asked for the six once per process).
+template <class... P, class... A>
+static hipError_t launch_tiny_batch(TinyLdsGrant &grant, void (*const (&k)[2][3])(P...), int dim, unsigned threads,
+                                    unsigned m_max, unsigned count, hipStream_t stream, bool *granted, A... args) {
+  *granted = grant.ask({reinterpret_cast<const void *>(k[0][0]), reinterpret_cast<const void *>(k[0][1]),
+                        reinterpret_cast<const void *>(k[0][2]), reinterpret_cast<const void *>(k[1][0]),
+                        reinterpret_cast<const void *>(k[1][1]), reinterpret_cast<const void *>(k[1][2])},
+                       kTinyLdsGrant);
+  if (!*granted || count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k[dim == 3 ? 1 : 0][threads == 512u ? 0 : (threads == 768u ? 1 : 2)], dim3(count), dim3(threads),
+                     tiny_lds_bytes(dim, m_max), stream, args...);
+  return hipGetLastError();
+}
 
 hipError_t launch_tiny_estimate_batch(int dim, unsigned threads, unsigned m_max, const double *d_src, const double *d_dst,
                                       const TinyBatchItem *d_items, unsigned count, unsigned max_iter, TinyResult *res,
                                       uint32_t *inner, uint32_t *d_idx, hipStream_t stream, bool *granted) {
-  // the same grant as the single kernels', asked for these six once per process
   static TinyLdsGrant grant;
-  *granted = grant.ask({reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 512>),
-                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 768>),
-                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<2, 1024>),
-                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 512>),
-                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 768>),
-                        reinterpret_cast<const void *>(&k_tiny_estimate_batch<3, 1024>)},
-                       kTinyLdsGrant);
-  if (!*granted || count == 0) return hipSuccess;
-  const size_t lds = tiny_lds_bytes(dim, m_max);
-#define ICP_TINY_BATCH_LAUNCH(D, BB)                                                                                   \
-  hipLaunchKernelGGL((k_tiny_estimate_batch<D, BB>), dim3(count), dim3(BB), lds, stream, d_src, d_dst, d_items, max_iter, \
-                     res, inner, d_idx)
-  if (dim == 3) {
-    if (threads == 512u) ICP_TINY_BATCH_LAUNCH(3, 512);
-    else if (threads == 768u) ICP_TINY_BATCH_LAUNCH(3, 768);
-    else ICP_TINY_BATCH_LAUNCH(3, 1024);
-  } else {
-    if (threads == 512u) ICP_TINY_BATCH_LAUNCH(2, 512);
-    else if (threads == 768u) ICP_TINY_BATCH_LAUNCH(2, 768);
-    else ICP_TINY_BATCH_LAUNCH(2, 1024);
-  }
-#undef ICP_TINY_BATCH_LAUNCH
-  return hipGetLastError();
+  static constexpr decltype(&k_tiny_estimate_batch<2, 512>) k[2][3] = {
+      {&k_tiny_estimate_batch<2, 512>, &k_tiny_estimate_batch<2, 768>, &k_tiny_estimate_batch<2, 1024>},
+      {&k_tiny_estimate_batch<3, 512>, &k_tiny_estimate_batch<3, 768>, &k_tiny_estimate_batch<3, 1024>}};
+  return launch_tiny_batch(grant, k, dim, threads, m_max, count, stream, granted, d_src, d_dst, d_items, max_iter, res,
+                           inner, d_idx);
+}
+
+hipError_t launch_tiny_estimate_gated_batch(int dim, unsigned threads, unsigned m_max, const double *d_src,
+                                            const double *d_dst, const TinyBatchItem *d_items, unsigned count,
+                                            unsigned max_iter, double r2, TinyResult *res, uint32_t *inner, uint32_t *d_idx,
+                                            uint32_t *inliers, hipStream_t stream, bool *granted) {
+  static TinyLdsGrant grant;  // (these kernels' own)
+  static constexpr decltype(&k_tiny_estimate_gated_batch<2, 512>) k[2][3] = {
+      {&k_tiny_estimate_gated_batch<2, 512>, &k_tiny_estimate_gated_batch<2, 768>, &k_tiny_estimate_gated_batch<2, 1024>},
+      {&k_tiny_estimate_gated_batch<3, 512>, &k_tiny_estimate_gated_batch<3, 768>, &k_tiny_estimate_gated_batch<3, 1024>}};
+  return launch_tiny_batch(grant, k, dim, threads, m_max, count, stream, granted, d_src, d_dst, d_items, max_iter, r2, res,
+                           inner, d_idx, inliers);
 }
 
 hipError_t launch_weighted_gn_fast(icp_handle *h, const double *d_a, const double *d_b, size_t n_, const Pose &T) {

@@ -71,7 +71,8 @@ extern "C" {
  * (icp_batch_estimate_point_to_line_gated*; icp_batch_line_gated_counters in icp_mi355x_debug.h); so was section 18
  * (icp_batch_estimate_point_to_plane*; icp_batch_plane_counters in icp_mi355x_debug.h); so was section 19
  * (icp_batch_estimate_point_to_plane_gated*; icp_batch_plane_gated_counters in icp_mi355x_debug.h); so was section 20
- * (icp_batch_evaluate_point_to_plane*; icp_batch_plane_quality_counters in icp_mi355x_debug.h) */
+ * (icp_batch_evaluate_point_to_plane*; icp_batch_plane_quality_counters in icp_mi355x_debug.h); so was section 21
+ * (icp_batch_estimate_gated*; icp_batch_gated_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -1059,6 +1060,32 @@ int icp_batch_evaluate_point_to_plane(icp_batch *b, const double *src, size_t sr
 int icp_batch_evaluate_point_to_plane_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
                                              size_t dst_points, const icp_batch_item *items, size_t count, int k,
                                              double max_dist, icp_plane_quality *out, int *status);
+
+/* ================================================================================
+ * 21. EXTENSION (not in the reference): section 8's call with a maximum correspondence distance
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  K hypotheses of one scan, loop-closure
+ * candidates, a log replayed against keyframes overlap their targets only partly: they need section 10's gate.  Item i's
+ * out[i], status[i], indices, inner counts and inlier counts are what icp_create(dim, dst + dim dst_first, m) +
+ * icp_estimate_gated(src + dim src_first, n, &init, max_iter, max_dist) return on a fresh handle, bit for bit, for 2-D
+ * and 3-D batches: per outer iteration the inner loop sees only the pairs with d2 = (ex ex + ey ey) + ez ez <=
+ * max_dist * max_dist (ez: 3-D batches only; no FMA; max_dist * max_dist in f64; a NaN d2 is never kept, so a NaN source
+ * point is gated out and is not ICP_NAN_INPUT: that is reported for a kept pair with a NaN residual, as in section 10),
+ * in the caller's order.  Every item within section 8's limits runs as ONE workgroup (one launch per workgroup size, at
+ * most three); the other items, and those a workgroup hands back, go through exactly those two entries one after
+ * another.  An item is never approximated.  DESIGN.md section 9r.
+ * Arguments, ranges, last_idx (the search result of ALL n points in the last iteration), inner_iters, statuses and the
+ * return value are section 8's.  inliers: count * max_iter words, nullable, laid out like inner_iters: the number of
+ * kept pairs of each outer iteration.  In addition ICP_BAD_ARGUMENT for max_dist NaN or negative (+inf and 0.0 are
+ * allowed: +inf keeps every pair with a d2 that is not NaN) -- checked, like every argument, before the device is
+ * touched.  count == 0 is a successful no-op. */
+int icp_batch_estimate_gated(icp_batch *b, const double *src, size_t src_points, const double *dst, size_t dst_points,
+                             const icp_batch_item *items, size_t count, size_t max_iter, double max_dist, icp_pose *out,
+                             int *status, uint32_t *last_idx, uint32_t *inner_iters, uint32_t *inliers);
+int icp_batch_estimate_gated_device(icp_batch *b, const double *d_src, size_t src_points, const double *d_dst,
+                                    size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
+                                    double max_dist, icp_pose *out, int *status, uint32_t *d_last_idx,
+                                    uint32_t *inner_iters, uint32_t *inliers);
 
 #ifdef __cplusplus
 }

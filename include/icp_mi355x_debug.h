@@ -146,6 +146,11 @@ int icp_batch_plane_quality_counters(icp_batch *b, uint64_t out[4]);
  * (x | y | z, the screen records, the normals, 256 B of control words), out[3] dynamic LDS of the launch (out[1] +
  * out[2]).  Host arithmetic: no device use. */
 int icp_debug_plane_quality_batch_plan(unsigned m, uint32_t out[4]);
+/* ... and of icp_batch_estimate_gated[_device] (icp_mi355x.h section 21): out[0] items served inside a batch launch,
+ * out[1] items served one by one through icp_create_device + icp_estimate_gated_device (outside the limits, handed back
+ * by their workgroup, or no LDS grant), out[2] batch launches, out[3] launches not made because the runtime refused the
+ * kernels their LDS.  Section 8's counters (icp_batch_counters) do not move with these calls. */
+int icp_batch_gated_counters(icp_batch *b, uint64_t out[4]);
 
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
