@@ -68,6 +68,53 @@ def _vec(v, n):
     return a
 
 
+def _voxel_size(voxel_size):
+    v = float(voxel_size)
+    if not (np.isfinite(v) and v >= np.finfo(np.float64).tiny):
+        raise ValueError(f"a voxel size must be finite and at least DBL_MIN, got {v}")
+    return v
+
+
+def voxel_downsample(points, voxel_size, return_index=False, device=-1):
+    """EXTENSION (icp_voxel_downsample[_device], include/icp_mi355x.h section 22): the first point of every voxel, in
+    order.  The cell of a point is floor(p / voxel_size) per axis in f64; two points share a voxel iff their cells
+    are equal; a point with a NaN or infinite coordinate is dropped.  `points` is (n, 2) or (n, 3): a numpy array
+    (or anything numpy converts) gives numpy arrays; a contiguous float64 CUDA tensor gives CUDA tensors, computed on
+    torch's current stream.  Returns the kept points; with return_index=True also their indices in `points`
+    (ascending; uint32 in numpy, int32 bits in torch)."""
+    v = _voxel_size(voxel_size)
+    kept = C.c_size_t(0)
+    if _is_device_tensor(points):
+        import torch
+
+        if points.dim() != 2 or points.shape[1] not in (2, 3):
+            raise ValueError(f"points: expected (n, 2) or (n, 3), got {tuple(points.shape)}")
+        dim = points.shape[1]
+        _dev_points(points, dim, None if device < 0 else device)
+        n = points.shape[0]
+        out = torch.empty_like(points)
+        index = torch.empty(max(n, 1), dtype=torch.int32, device=points.device) if return_index else None
+        with torch.cuda.device(points.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().icp_voxel_downsample_device(dim, C.c_void_p(points.data_ptr()), n, v, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(index.data_ptr()) if return_index else None,
+                                                    C.byref(kept), points.device.index, C.c_void_p(stream)),
+                  "icp_voxel_downsample_device")
+        out = out[:kept.value]
+        return (out, index[:kept.value]) if return_index else out
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] not in (2, 3):
+        raise ValueError(f"points: expected (n, 2) or (n, 3), got {p.shape}")
+    n, dim = p.shape
+    out = np.empty((max(n, 1), dim), dtype=np.float64)
+    index = np.zeros(max(n, 1), dtype=np.uint32) if return_index else None
+    check(lib().icp_voxel_downsample(dim, _ptr(p), n, v, C.c_void_p(out.ctypes.data),
+                                     C.c_void_p(index.ctypes.data) if return_index else None, C.byref(kept),
+                                     int(device)), "icp_voxel_downsample")
+    out = out[:kept.value].copy()
+    return (out, index[:kept.value].copy()) if return_index else out
+
+
 class Transform:
     """`icp::Transform` (src/transform.rs:6-51)."""
 
@@ -747,6 +794,29 @@ class _Icp:
         check(lib().icp_grid_crop_counters(self._h, out), "icp_grid_crop_counters")
         return int(out[0]), int(out[1])
 
+    def thin(self, voxel_size, return_index=False):
+        """Keep the first target of every voxel of size `voxel_size` and remove the others (icp_thin_targets,
+        include/icp_mi355x.h section 22; the rule is voxel_downsample's).  Like crop: the kept targets keep their
+        order and their normals, and afterwards the handle behaves like a fresh Icp*::new on the kept cloud.  Returns
+        the number of targets removed; with return_index=True also new_index (uint32, one per old target: its new
+        index, 0xffffffff if removed)."""
+        v = _voxel_size(voxel_size)
+        m_before = self.target_count
+        index = np.zeros(max(m_before, 1), dtype=np.uint32) if return_index else None
+        removed = C.c_size_t(0)
+        check(lib().icp_thin_targets(self._h, v, C.c_void_p(index.ctypes.data) if return_index else None,
+                                     C.byref(removed)), "icp_thin_targets")
+        if removed.value:
+            self._keep = None  # the kept cloud lives in the handle's own storage
+        self.m = self.target_count
+        return (int(removed.value), index[:m_before]) if return_index else int(removed.value)
+
+    def thin_counters(self):
+        """(thins served by moving the search grid's sorted records, thins that rebuilt the grid)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().icp_grid_thin_counters(self._h, out), "icp_grid_thin_counters")
+        return int(out[0]), int(out[1])
+
     def reserve(self, capacity):
         check(lib().icp_reserve_targets(self._h, int(capacity)), "icp_reserve_targets")
         self._keep = None if capacity > self.m else self._keep
@@ -979,6 +1049,14 @@ class IcpMulti:
         removed = C.c_size_t(0)
         check(lib().icp_multi_crop_targets(self._h, c.ctypes.data_as(_dp), float(radius), C.byref(removed)),
               "icp_multi_crop_targets")
+        return int(removed.value)
+
+    def thin(self, voxel_size):
+        """EXTENSION (icp_multi_thin_targets): every rank thins its replica of the target cloud to one target per
+        voxel; returns the number of targets removed"""
+        removed = C.c_size_t(0)
+        check(lib().icp_multi_thin_targets(self._h, _voxel_size(voxel_size), C.byref(removed)),
+              "icp_multi_thin_targets")
         return int(removed.value)
 
     @property

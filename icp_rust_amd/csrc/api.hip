@@ -467,6 +467,7 @@ extern "C" void icp_destroy(icp_handle *h) {
     h->grid.built = false;
     h->grid.appends_moved = h->grid.appends_rebuilt = 0;
     h->grid.crops_moved = h->grid.crops_rebuilt = 0;
+    h->grid.thins_moved = h->grid.thins_rebuilt = 0;
     h->qsort.valid = false;
     h->qsort.have_prev = false;
     h->qsort.slot_order = false;
@@ -515,6 +516,7 @@ extern "C" void icp_trim_pool(void) {
     take.swap(g_pool);
   }
   for (icp_handle *h : take) free_handle(h);
+  voxel_trim();
 }
 
 extern "C" int icp_set_nn_mode(icp_handle *h, int mode) {

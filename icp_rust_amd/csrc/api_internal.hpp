@@ -114,6 +114,21 @@ int ensure_plane_stage(icp_handle *h, size_t n);
 // the inner loop (src/lib.rs:59-84 around the plane residual) on the k pairs in h->d_plane_pairs (api_normal.hip)
 int p2pl_loop_on_pairs(icp_handle *h, size_t k, Pose *dT, uint32_t *applied_out);
 
+// ---- removing targets from a handle (crop.hip): the half icp_crop_targets and icp_thin_targets (voxel.hip) share ----
+// a removed target's mark, and its entry of the new_index table
+constexpr uint32_t kCropGone = 0xffffffffu;
+// Waits for everything in flight on the handle, then hands out the device words a keep rule fills for the h->m > 0
+// targets: *w, one mark per target (0 or kCropGone), and *cnt, the kept targets of every tile of kCompactTile
+// consecutive ones (the words behind them are remove_marked_targets' own).  Both are build temporaries of the grid.
+int target_marks(icp_handle *h, uint32_t **w, uint32_t **cnt);
+// Everything a removal does behind its mark launch (enqueued on h->stream, marks from target_marks): the chunk sums, the
+// "nothing to remove" exit, the kept points and normals into the second buffers, new_index (nullable, host), the grid's
+// records moved (++moved) or the grid rebuilt (++rebuilt), the brute engine's arrays, the swap and the way back.
+int remove_marked_targets(icp_handle *h, uint32_t *w, uint32_t *cnt, unsigned long long &moved,
+                          unsigned long long &rebuilt, uint32_t *new_index, size_t *removed);
+// the cached workspace of icp_voxel_downsample* and icp_thin_targets (voxel.hip), for icp_trim_pool
+void voxel_trim();
+
 }  // namespace api
 }  // namespace icp
 // One outer iteration's point-to-plane inner loop for given correspondences of the whole source cloud (api_normal.hip), and

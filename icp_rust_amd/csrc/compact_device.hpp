@@ -1,4 +1,5 @@
-// The stable compaction the gate (gate.hip), the plane gate (gate_plane.hip) and the crop (crop.hip) share.  A tile =
+// The stable compaction the gate (gate.hip), the plane gate (gate_plane.hip), the crop (crop.hip) and the voxel thinning
+// (voxel.hip) share.  A tile =
 // kCompactTile consecutive elements = one workgroup of four waves, four rounds of 256 elements.  A first launch counts
 // the survivors of every tile (a ballot per round and wave gives the wave's count and the lane's rank among its wave's
 // survivors; the sixteen counts meet in LDS) into cnt[tile]; k_compact_chunks adds the counts up in chunks of

@@ -12,6 +12,9 @@
 //                                   the number of survivors in front of it, its idx rewritten; that number is left in
 //                                   w[p] for EVERY p, so that
 //             k_crop_starts         start2[c] = w[start[c]] (one gather), and the sentinel records follow the last one
+// The host side is in two halves (api_internal.hpp): target_marks hands out the mark and count words, and
+// remove_marked_targets does everything behind a mark launch; icp_crop_targets runs k_crop_mark between them and
+// icp_thin_targets (voxel.hip) its own keep rule.
 // No float reductions.  The grid keeps the box and the cell size of its last full build (upper bounds of the kept
 // cloud's: exact, like the grid of an incremental append).
 #include <cmath>
@@ -26,7 +29,6 @@ using namespace icp::api;
 namespace icp {
 namespace {
 
-constexpr uint32_t kCropGone = 0xffffffffu;
 // The kept cloud has fallen below 1 / kRebuildShrink of the cloud the grid's cell size was chosen for: rebuild (the
 // mirror of append_grid's kRebuildGrowth)
 constexpr double kRebuildShrink = 1.5;
@@ -197,24 +199,28 @@ hipError_t crop_move_records(icp_handle *h, unsigned m_old, unsigned kept, const
   return hipGetLastError();
 }
 
-int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *new_index, size_t *removed) {
-  if (removed) *removed = 0;
+}  // namespace
+
+int api::target_marks(icp_handle *h, uint32_t **w, uint32_t **cnt) {
   ICP_TRY_RC(crop_quiesce(h));
-  if (h->m == 0) return ICP_OK;
+  Grid &G = h->grid;
+  const unsigned tiles = compact_tiles(h->m), chunks = compact_chunks(tiles);
+  // the marks, later the new_index table: the grid's build temporary of m words, free between builds; the tile counts,
+  // the chunk sums and one word for the normals: the append's shift table, free between appends
+  HIP_TRY(reserve(G.t_cell_of, G.cap_tcell, h->m));
+  HIP_TRY(reserve(G.t_shift, G.cap_shift, (size_t)tiles + chunks + 1));
+  *w = G.t_cell_of;
+  *cnt = G.t_shift;
+  return ICP_OK;
+}
+
+int api::remove_marked_targets(icp_handle *h, uint32_t *w, uint32_t *cnt, unsigned long long &moved,
+                               unsigned long long &rebuilt, uint32_t *new_index, size_t *removed) {
   Grid &G = h->grid;
   hipStream_t s = h->stream;
   const unsigned m_old = (unsigned)h->m, tiles = compact_tiles(m_old), chunks = compact_chunks(tiles);
   const int dim = h->dim;
-  // the new_index table: the grid's build temporary of m words, free between builds; the tile counts, the chunk sums and
-  // one word for the normals: the append's shift table, free between appends
-  HIP_TRY(reserve(G.t_cell_of, G.cap_tcell, (size_t)m_old));
-  HIP_TRY(reserve(G.t_shift, G.cap_shift, (size_t)tiles + chunks + 1));
-  uint32_t *w = G.t_cell_of, *cnt = G.t_shift, *sums = cnt + tiles, *aux = sums + chunks;
-  const double r2 = radius * radius;
-  if (dim == 3)
-    hipLaunchKernelGGL(k_crop_mark<3>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
-  else
-    hipLaunchKernelGGL(k_crop_mark<2>, dim3(tiles), dim3(kCompactThreads), 0, s, h->d_dst, m_old, cx, cy, r2, w, cnt);
+  uint32_t *sums = cnt + tiles, *aux = sums + chunks;
   HIP_TRY(launch_compact_chunks(cnt, tiles, sums, s));
   std::vector<uint32_t> host(chunks + 1);
   HIP_TRY(hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -312,9 +318,28 @@ int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *n
     (void)hipStreamSynchronize(s);
     return map_hip(e);
   }
-  ++(move ? G.crops_moved : G.crops_rebuilt);
+  ++(move ? moved : rebuilt);
   if (removed) *removed = (size_t)m_old - kept;
   return ICP_OK;
+}
+
+namespace {
+
+int crop_targets(icp_handle *h, double cx, double cy, double radius, uint32_t *new_index, size_t *removed) {
+  if (removed) *removed = 0;
+  if (h->m == 0) {
+    ICP_TRY_RC(crop_quiesce(h));
+    return ICP_OK;
+  }
+  uint32_t *w, *cnt;
+  ICP_TRY_RC(target_marks(h, &w, &cnt));
+  const unsigned m_old = (unsigned)h->m, tiles = compact_tiles(m_old);
+  const double r2 = radius * radius;
+  if (h->dim == 3)
+    hipLaunchKernelGGL(k_crop_mark<3>, dim3(tiles), dim3(kCompactThreads), 0, h->stream, h->d_dst, m_old, cx, cy, r2, w, cnt);
+  else
+    hipLaunchKernelGGL(k_crop_mark<2>, dim3(tiles), dim3(kCompactThreads), 0, h->stream, h->d_dst, m_old, cx, cy, r2, w, cnt);
+  return remove_marked_targets(h, w, cnt, h->grid.crops_moved, h->grid.crops_rebuilt, new_index, removed);
 }
 
 }  // namespace

@@ -509,6 +509,20 @@ extern "C" int icp_multi_crop_targets(icp_multi *M, const double center_xy[2], d
   if (removed) *removed = gone;
   return ICP_OK;
 }
+// EXTENSION (include/icp_mi355x.h section 22 across the ranks): every rank thins its replica by the same voxel size; the
+// replicas hold the same points and the rule is a pure function of them, so every rank removes the same ones.
+extern "C" int icp_multi_thin_targets(icp_multi *M, double voxel, size_t *removed) {
+  if (!M || !(voxel >= DBL_MIN && voxel <= DBL_MAX)) return ICP_BAD_ARGUMENT;
+  if (removed) *removed = 0;
+  size_t gone = 0;
+  for (auto &R : M->r) {
+    const int rc = icp_thin_targets(R.h, voxel, nullptr, &gone);
+    if (rc != ICP_OK) return rc;  // (a rank that failed leaves the replicas different: the object is then unusable)
+  }
+  M->m -= gone;
+  if (removed) *removed = gone;
+  return ICP_OK;
+}
 extern "C" size_t icp_multi_target_count(const icp_multi *M) { return M ? M->m : 0; }
 
 extern "C" int icp_multi_counters(const icp_multi *M, uint64_t out[2]) {

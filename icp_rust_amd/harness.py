@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .api import Icp2d, Icp3d, Transform
+from .api import Icp2d, Icp3d, Transform, voxel_downsample
 from .scans import PacketFile, load_scan2d, write_packets
 from .synth import PACKETS_PER_FRAME, remove_invalid_values
 
@@ -130,7 +130,7 @@ def run_scan3d(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, p
 
 def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, max_frames=None,
                     point_to_plane=None, max_correspondence_distance=None, map_radius=None, quality_distance=None,
-                    qualities=None):
+                    qualities=None, scan_voxel=None, map_voxel=None):
     """EXTENSION, not in the reference (BASELINE.json configs[4]): the
     scan3d frames registered against a map that grows.  The map starts as frame 0 (filtered as
     examples/scan3d.rs:63-69 does); every later frame is registered against the whole map with
@@ -153,19 +153,29 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
     world.evaluate_point_to_plane(scan, transform, quality_distance or inf) (a PlaneQuality, include/icp_mi355x.h
     section 13), otherwise world.evaluate(scan, transform, quality_distance or inf) (a Quality, section 9).  None calls
     nothing.
+    `scan_voxel=v`: every incoming scan, frame 0 included, is thinned to the first point of every voxel of size v
+    (voxel_downsample, include/icp_mi355x.h section 22) before it is registered and appended; None calls nothing.
+    `map_voxel=v` (either residual): right after every frame's append the map is thinned the same way, world.thin(v):
+    the lowest index wins, so every older map point stays and exactly the new points that fall into an occupied voxel
+    go -- before update_normals, so that only survivors get a normal, and before the crop; None calls nothing.
     Returns (transforms, path_xy, map_handle)."""
     if point_to_plane and max_correspondence_distance is not None:
         raise ValueError("max_correspondence_distance applies to the point-to-point registration only")
     icp_factory = icp_factory or Icp3d
     packets = np.asarray(packets, dtype=np.float64)
-    world = icp_factory(remove_invalid_values(packets[0:step]))
+
+    def frame(first):
+        scan = remove_invalid_values(packets[first:first + step])
+        return scan if scan_voxel is None else voxel_downsample(scan, scan_voxel)
+
+    world = icp_factory(frame(0))
     if point_to_plane:
         world.compute_normals(point_to_plane)
     transform = Transform.identity()
     transforms, path = [], []
     index = step
     while index + step <= packets.shape[0] and (max_frames is None or len(transforms) < max_frames):
-        scan = remove_invalid_values(packets[index:index + step])
+        scan = frame(index)
         index += step
         if point_to_plane:
             transform = world.estimate_point_to_plane(scan, transform, max_iter)
@@ -181,6 +191,8 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
             else:
                 qualities.append(world.evaluate(scan, transform, bound))
         world.append(scan, transform)
+        if map_voxel is not None:
+            world.thin(map_voxel)
         if point_to_plane:
             world.update_normals(point_to_plane)
         if map_radius is not None:
@@ -211,6 +223,10 @@ def main(argv=None):
                     help="scan2d: register with point-to-line residuals, line normals from K nearest targets (extension)")
     ap.add_argument("--map-radius", type=float, default=None, metavar="R",
                     help="scan2map: keep the map within R of the registered position (sliding window, extension)")
+    ap.add_argument("--scan-voxel", type=float, default=None, metavar="V",
+                    help="scan2map: thin every scan to one point per voxel of size V before it is registered (extension)")
+    ap.add_argument("--map-voxel", type=float, default=None, metavar="V",
+                    help="scan2map: thin the map to one point per voxel of size V after every append (extension)")
     args = ap.parse_args(argv)
     if args.loop == "scan2d":
         if not args.scan_dir:
@@ -229,7 +245,8 @@ def main(argv=None):
         stream = PacketFile(args.scan_dir).as_array() if args.scan_dir else \
             synth.synthetic_scan3d_packets(PACKETS_PER_FRAME * (args.frames + 1))
         _, path, world = run_scan_to_map(stream, max_iter=args.max_iter, point_to_plane=args.point_to_plane or None,
-                                         map_radius=args.map_radius)
+                                         map_radius=args.map_radius, scan_voxel=args.scan_voxel,
+                                         map_voxel=args.map_voxel)
         print(f"# map: {world.target_count} points")
     for k, (x, y) in enumerate(path):
         print(f"{k:4d} {x:+.9f} {y:+.9f}")

@@ -72,7 +72,8 @@ extern "C" {
  * (icp_batch_estimate_point_to_plane*; icp_batch_plane_counters in icp_mi355x_debug.h); so was section 19
  * (icp_batch_estimate_point_to_plane_gated*; icp_batch_plane_gated_counters in icp_mi355x_debug.h); so was section 20
  * (icp_batch_evaluate_point_to_plane*; icp_batch_plane_quality_counters in icp_mi355x_debug.h); so was section 21
- * (icp_batch_estimate_gated*; icp_batch_gated_counters in icp_mi355x_debug.h) */
+ * (icp_batch_estimate_gated*; icp_batch_gated_counters in icp_mi355x_debug.h); so was section 22
+ * (icp_voxel_downsample*, icp_thin_targets, icp_multi_thin_targets; icp_grid_thin_counters in icp_mi355x_debug.h) */
 #define ICP_ABI_VERSION 8
 
 typedef enum icp_status {
@@ -1086,6 +1087,53 @@ int icp_batch_estimate_gated_device(icp_batch *b, const double *d_src, size_t sr
                                     size_t dst_points, const icp_batch_item *items, size_t count, size_t max_iter,
                                     double max_dist, icp_pose *out, int *status, uint32_t *d_last_idx,
                                     uint32_t *inner_iters, uint32_t *inliers);
+
+/* ================================================================================
+ * 22. EXTENSION (not in the reference): voxel thinning -- one point per voxel, for clouds and for a handle's targets
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  A map fed by icp_append_targets (section 6)
+ * gains a layer of near-duplicates at every revisit of a place, and a lidar front end thins a frame before it registers
+ * it (the "voxel-thinned frames" of section 18): both keep at most one point per voxel.  The reference has no such
+ * thing: no parity claim; DESIGN.md section 9s restates the definition.
+ *
+ * The rule.  For a point p with dim coordinates and a voxel size v:
+ *   the cell coordinate on axis a is the f64 value floor(p_a / v): ONE IEEE division, then floor; never a product with
+ *   1 / v (the two differ, e.g. for 195 of the 2 000 inputs k * 0.1, k in [-1000, 1000), at v = 0.1);
+ *   two points share a voxel iff their cell coordinates compare equal as doubles on every axis: -0.0 == +0.0; a quotient
+ *   that overflows to +-inf is a cell coordinate like any other; cell coordinates are never narrowed to an integer type,
+ *   so there is no range to exceed and no status for it;
+ *   a point with a NaN or infinite coordinate belongs to no voxel and is dropped;
+ *   of every voxel the point with the LOWEST INDEX is kept, the others are dropped;
+ *   kept points keep their relative order and their bits (a kept -0.0 stays -0.0).
+ * v must be finite and at least DBL_MIN: a NaN, zero, negative, subnormal or infinite v is ICP_BAD_ARGUMENT.
+ * In numpy:  ok = isfinite(p).all(axis=1);  c = floor(p / v) + 0.0;  _, first = unique(c[ok], axis=0, return_index=True);
+ *            kept_index = sort(flatnonzero(ok)[first]).
+ * The result is a pure function of the input: the same bytes from every call.
+ *
+ * icp_voxel_downsample (host arrays) and icp_voxel_downsample_device (device arrays; everything is enqueued on
+ * hip_stream, NULL: the default stream, and the entry waits for that stream to deliver *kept): dim is 2 or 3; pts holds n
+ * points; out (nullable) receives the kept points and needs room for n of them; it must not overlap pts; kept_index
+ * (nullable) receives their indices in pts, ascending, room for n; *kept (required) their number.  n == 0 gives
+ * *kept = 0 and ICP_OK.  device: -1 = the current one.  Statuses: ICP_BAD_ARGUMENT (dim, v as above, kept NULL, pts NULL
+ * with n > 0, n > 2^32 - 2, device < -1: all decided before the device is touched; a device number past the last one),
+ * ICP_NO_DEVICE, ICP_HIP_ERROR, ICP_OUT_OF_MEMORY.  The workspace (a hash table of 2^ceil(log2(2 n)) words, one mark per
+ * point, the tile counts; for the host entry also the staging buffers) is kept per device between calls and grown when a
+ * larger cloud comes: no allocation per frame.  The calls of one process take turns.  icp_trim_pool releases it.
+ *
+ * icp_thin_targets: section 11's call with this keep rule in place of the disc.  Everything section 11 says of the
+ * handle after a crop holds after a thin: order, bits, new_index (nullable, host, m_before words; 0xffffffff = removed),
+ * *removed (nullable), correspondences and poses of a fresh icp_create on the kept cloud, normals carried over and their
+ * count, the edges (nothing removed: the handle is untouched and keeps borrowing; everything else: it owns its cloud;
+ * a cloud of only non-finite points: all removed), the statuses (ICP_BAD_ARGUMENT: h NULL or v as above, before any
+ * device use) and the way back on failure.  Because the lowest index wins, a thin after an append keeps every target
+ * that was kept by the thin before it and drops exactly the new points that fall into an occupied voxel.
+ * icp_multi_thin_targets: every rank thins its replica, as icp_multi_crop_targets crops it. */
+int icp_voxel_downsample(int dim, const double *pts, size_t n, double voxel, double *out, uint32_t *kept_index,
+                         size_t *kept, int device);
+int icp_voxel_downsample_device(int dim, const double *d_pts, size_t n, double voxel, double *d_out,
+                                uint32_t *d_kept_index, size_t *kept, int device, void *hip_stream);
+int icp_thin_targets(icp_handle *h, double voxel, uint32_t *new_index, size_t *removed);
+int icp_multi_thin_targets(icp_multi *M, double voxel, size_t *removed);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,11 @@ int icp_grid_append_counters(const icp_handle *h, uint64_t out[2]);
  * neither. */
 int icp_grid_crop_counters(const icp_handle *h, uint64_t out[2]);
 
+/* ... and of icp_thin_targets (icp_mi355x.h section 22), which shares the crop's back half and counts for itself:
+ * out[0] = thins served by moving the grid's sorted records, out[1] = thins that rebuilt the grid, under the same
+ * conditions.  A thin that removes nothing counts in neither; a thin never moves the crop's counters. */
+int icp_grid_thin_counters(const icp_handle *h, uint64_t out[2]);
+
 int icp_multi_counters(const icp_multi *M, uint64_t out[2]);
 
 /* ... and of the one-launch inner loop across the ranks (section 5b): out[0] launches (per rank), out[1] evaluations they
