@@ -1,7 +1,7 @@
 // C ABI of the MI355X ICP core (include/icp_mi355x.h): handle lifecycle, the outer ICP
 // loop (src/lib.rs:105-130, 148-173) and the inner robust Gauss-Newton loop
 // (src/lib.rs:59-84) driven from the host over the device stages in nn_brute.hip /
-// gn.hip.  Nothing here falls back to a CPU computation: without a HIP device every
+// gn_pull.hip.  Nothing here falls back to a CPU computation: without a HIP device every
 // compute entry point fails with ICP_NO_DEVICE.
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -105,7 +105,7 @@ void free_workspace(Workspace &w) {
 
 hipError_t alloc_ctx(GnCtx &c, hipStream_t s) {
   hipError_t e;
-  const size_t hist_bytes = (size_t)kSelRoles * kSelProblems * kSelBins * sizeof(uint32_t);
+  const size_t hist_bytes = (size_t)kSelRolesAll * kSelProblems * kSelBins * sizeof(uint32_t);
   if ((e = hipMalloc(&c.d_hist, hist_bytes)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(c.d_hist, 0, hist_bytes, s)) != hipSuccess) return e;
   if ((e = hipMalloc(&c.d_cand, (size_t)2 * kSelProblems * kSelCap * sizeof(unsigned long long))) != hipSuccess) return e;
@@ -781,7 +781,7 @@ static int wgn_step(icp_handle *h, const double *d_a, const double *d_b, size_t 
     p_med[d] = own ? w.win_kind[kind].med[d] : w.win_med[d];
     p_sigma[d] = own ? w.win_kind[kind].sigma[d] : w.win_sigma[d];
   }
-  if (w.gn_dirty) {  // first use, or the radix path / a NaN left its state behind (the short pipelines clean up after themselves)
+  if (w.gn_dirty) {  // first use, or a NaN left its flag behind (every pipeline cleans up after itself)
     HIP_TRY(launch_sel_init(h, n));
     w.gn_dirty = false;
   }
@@ -855,13 +855,11 @@ static int wgn_step(icp_handle *h, const double *d_a, const double *d_b, size_t 
     done = !w.h_res->overflow;
     has_median = done && n > 1024;  // gn_pull.hip reports the median, the single-workgroup kernel does not
   }
-  if (!done) {  // heavy duplicates around a median: the general 6-pass radix select
-    ++w.radix_evals;
-    HIP_TRY(launch_sel_init(h, n));
-    HIP_TRY(launch_weighted_gn(h, d_a, d_b, n, T));
+  if (!done) {  // heavy duplicates around a median: the full-key selection, which always answers (its median is not
+    ++w.radix_evals;  // recorded).  The scratch is at rest: an overflowed short pipeline ran to its end, k_tiny_eval has none
+    HIP_TRY(launch_weighted_gn_full(h, d_a, d_b, n, T));
     if (!hooked) HIP_TRY(after_launch());
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    w.gn_dirty = true;
+    HIP_TRY(wait_result(h));
   }
   const GnResult &r = *w.h_res;
   record_statistics(w, kind, has_median, r);
@@ -1583,13 +1581,18 @@ extern "C" int icp_residual_stddevs(const icp_pose *T, const double *a, const do
   if (rc != ICP_OK) return rc;
   if (n == 0) return ICP_NONE;  // mutable_median of an empty input, src/stats.rs:15-17
   if ((rc = stage_pairs(h, a, b, n)) != ICP_OK) return rc;
-  HIP_TRY(launch_sel_init(h, n));
+  if (h->ws.gn_dirty) {
+    HIP_TRY(launch_sel_init(h, n));
+    h->ws.gn_dirty = false;
+  }
   HIP_TRY(launch_stddevs(h, h->ws.d_a, h->ws.d_b, n, *T));
-  h->ws.gn_dirty = true;
   GnScalars s;
   HIP_TRY(hipMemcpyAsync(&s, h->ws.d_scal, sizeof(s), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (s.nan_flag) return ICP_NAN_INPUT;
+  if (s.nan_flag) {
+    h->ws.gn_dirty = true;
+    return ICP_NAN_INPUT;
+  }
   sigma[0] = s.sigma[0];
   sigma[1] = s.sigma[1];
   return ICP_OK;

@@ -137,7 +137,3 @@ int icp_p2pl_inner_loop_device(icp_handle *h, const double *d_src, size_t n, con
                                icp_pose *dT, uint32_t *applied_out);
 int icp_p2pl_gated_inner_loop_device(icp_handle *h, const double *d_src, size_t n, const icp_pose *T, const uint32_t *d_idx,
                                      double max_dist, icp_pose *dT, uint32_t *applied_out, size_t *kept);
-namespace icp {
-hipError_t launch_sel_init(icp_handle *h, size_t n);  // (gn.hip)
-hipError_t launch_stddevs(icp_handle *h, const double *d_a, const double *d_b, size_t n, const Pose &T);
-}  // namespace icp

@@ -63,7 +63,10 @@ int p2pl_loop_on_pairs(icp_handle *h, size_t k, Pose *dT, uint32_t *applied_out)
       HIP_TRY(launch_p2pl_eval(h, h->d_plane_pairs, k, Ti, h->d_plane_fa, h->d_plane_fb));
       HIP_TRY(hipStreamSynchronize(h->stream));
       const GnResult &r = *w.h_res;
-      if (r.nan_flag) return ICP_NAN_INPUT;
+      if (r.nan_flag) {
+        w.gn_dirty = true;  // (the flag stays in the selection scratch)
+        return ICP_NAN_INPUT;
+      }
       double delta[3];
       if (!solve_update(r.acc, r.acc + 9, delta)) break;
       if ((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2] < ICP_DELTA_NORM_THRESHOLD) break;

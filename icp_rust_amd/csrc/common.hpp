@@ -49,7 +49,8 @@ constexpr int kNSum = 19;             // S_x[9] | S_y[9] | huber error
 constexpr int kSelProblems = 4;       // {x, y} x {lower, upper middle order statistic}
 constexpr int kSelBins = 4096;        // 12-bit radix digits
 constexpr int kSelPasses = 6;         // 12+12+12+12+12+4 bits
-constexpr int kSelRoles = 6;          // fast path: histogram buffers {median, MAD} x {digit 0, 1, 2}
+constexpr int kSelRoles = 6;          // histogram buffers {median, MAD} x {digit 0, 1, 2}: every pull pipeline's
+constexpr int kSelRolesAll = 12;      // ... + {median, MAD} x {digit 3, 4, 5}: the full-key selection's
 constexpr int kSelCap = 1024;         // fast path: candidates kept per problem after two passes
 // window path (gn_win.hip): one piecewise-linear histogram per dimension instead of radix digits
 constexpr int kWinFine = 512;         // bins of each of the three fine windows (median, median -+ MAD)
@@ -94,7 +95,7 @@ struct GnScalars {
   double median[2];
   double sigma[2];
   int nan_flag;
-  int overflow;  // fast selection path gave up (too many candidates): redo with the radix path
+  int overflow;  // the short pipeline gave up (too many candidates): redo with the full-key selection
 };
 
 // Arrival tickets of one kernel role: 16 shard counters + one top counter, each on a
@@ -158,7 +159,7 @@ struct GnResult {
   double sigma[2];
   double median[2];       // gn_pull.hip / gn_win.hip only: centre of the next evaluation's window
   int nan_flag;
-  int overflow;  // 1: too many candidates (radix path needed), 2: the window missed (gn_pull.hip needed)
+  int overflow;  // 1: too many candidates (full-key selection needed), 2: the window missed (gn_pull.hip needed)
   unsigned seq;  // written last, system scope: the host polls it instead of waiting for the stream
   unsigned pad;  // no evaluation touches it: gate.hip leaves the survivors' count of a gate here (k_gate_place; api::gate_count)
   // sharded evaluations: how many ranks answered {OK, RETRY_REPLICATED, NONE, anything else} in the hist stage
@@ -189,7 +190,7 @@ struct GnCtx {
   double *d_rx = nullptr;  // residual x, cap_n
   double *d_ry = nullptr;  // residual y, cap_n
   // selection + reduction scratch (fixed size)
-  uint32_t *d_hist = nullptr;   // kSelRoles x kSelProblems x kSelBins (role 0 also serves the radix path)
+  uint32_t *d_hist = nullptr;   // kSelRolesAll x kSelProblems x kSelBins (gn_pull.hip: launch_pull has the layout)
   unsigned long long *d_cand = nullptr;  // 2 stages x kSelProblems x kSelCap candidate keys
   SelCtl *d_ctl = nullptr;
   SelState *d_sel = nullptr;    // 2 x kSelProblems (gn_pull.hip ping-pongs between the halves)
@@ -197,7 +198,7 @@ struct GnCtx {
   double *d_partials = nullptr; // kTreeMaxBlocks x (kNSum+1)
   GnResult *h_res = nullptr;    // pinned coherent host memory, written by the last workgroup
   unsigned seq = 0;             // sequence number of the last fast evaluation launched
-  bool gn_dirty = true;         // selection scratch is not in its all-zero rest state: k_sel_init first
+  bool gn_dirty = true;         // selection scratch is not in its rest state (first use, or a NaN's flag): k_sel_init first
   // window path (gn_win.hip)
   uint32_t *d_whist = nullptr;  // 2 x kWinBins, zero between evaluations
   WinState *d_wstate = nullptr;
@@ -500,16 +501,20 @@ hipError_t launch_nn_grid(icp_handle *h, const double *d_src, size_t n, const Po
 hipError_t launch_nn_grid_ahead(icp_handle *h, const double *d_src, size_t n, const AheadPose *d_pose, double *d_a,
                                 double *d_b, uint32_t *d_idx, bool *launched);
 
-// one inner Gauss-Newton iteration's device work; results land in h->ws.h_res after the
-// stream is synchronised
-hipError_t launch_weighted_gn(icp_handle *h, const double *d_a, const double *d_b, size_t n,
-                              const Pose &T);
-// the same through the short pipeline (7 launches, or 3 when n <= kSelCap); sets
-// h_res->overflow when the caller has to redo the evaluation with launch_weighted_gn
+// one inner Gauss-Newton iteration's device work through the short pipeline (gn_pull.hip: 7 or 9 launches; one
+// when n <= kSelCap); the result lands in h->ws.h_res (api::wait_result), with `overflow` set when the caller has
+// to redo the evaluation with launch_weighted_gn_full
 hipError_t launch_weighted_gn_fast(icp_handle *h, const double *d_a, const double *d_b, size_t n,
                                    const Pose &T);
 hipError_t launch_weighted_gn_pull(icp_handle *h, const double *d_a, const double *d_b, size_t n,
                                    const Pose &T);
+// the same through the full-key selection (15 launches): always answers
+hipError_t launch_weighted_gn_full(icp_handle *h, const double *d_a, const double *d_b, size_t n,
+                                   const Pose &T);
+// the full-key selection alone (14 launches): sigma in h->ws.d_scal, for callers that accumulate themselves.  Both
+// expect the scratch's rest state and leave it (launch_sel_init when Workspace::gn_dirty)
+hipError_t launch_stddevs(icp_handle *h, const double *d_a, const double *d_b, size_t n, const Pose &T);
+hipError_t launch_sel_init(icp_handle *h, size_t n);
 // the whole Icp::estimate of a small cloud in one launch (gn_fast.hip); *status = -1: not served
 struct TinyResult {  // pinned host memory
   Pose pose;

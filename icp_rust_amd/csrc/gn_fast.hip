@@ -2,8 +2,9 @@
 // pipelines, and the single-workgroup kernel for tiny inputs.
 //
 //   n <= 1024            k_tiny_eval below: ONE workgroup, ONE launch
-//   otherwise            gn_pull.hip (7 or 9 launches); icp_estimate's loop prefers gn_win.hip
-//                        (3 launches) once it has a prediction -- see api.hip:wgn_step
+//   otherwise            gn_pull.hip (7 or 9 launches; 15 with the full key, when either reports an
+//                        overflow); icp_estimate's loop prefers gn_win.hip (3 launches) once it has a
+//                        prediction -- see api.hip:wgn_step
 //
 // (The first short pipeline, whose launches ended in a last-workgroup tail, lived here; the
 // "pull" variant replaced it: +8 % per step, same bits.  Its lessons are in DESIGN.md.)

@@ -34,8 +34,6 @@
 #include "p2plane_device.hpp"
 
 namespace icp {
-hipError_t launch_sel_init(icp_handle *h, size_t n);
-hipError_t launch_stddevs(icp_handle *h, const double *d_a, const double *d_b, size_t n, const Pose &T);
 __global__ void k_final_reduce(const double *__restrict__ partials, int blocks, int nacc,
                                const GnScalars *__restrict__ scal, GnResult *__restrict__ res);
 
@@ -68,8 +66,8 @@ __global__ void k_line_gather(const double *__restrict__ src, unsigned n, Pose T
   normal_gather<2>(src, n, T, idx, dst, m, normals, out);
 }
 
-// residuals as the pairs ((r, 0), (0, 0)): launch_stddevs under the identity pose then selects the
-// exact median and MAD of r (dimension 0); dimension 1 is all zeros
+// residuals as the pairs ((r, 0), (0, 0)): launch_stddevs (gn_pull.hip, the full key) under the identity pose then
+// selects the exact median and MAD of r (dimension 0); dimension 1 is all zeros
 __global__ void k_p2pl_residual(const PlanePair *__restrict__ pp, unsigned n, Pose T, double2 *__restrict__ fa,
                                 double2 *__restrict__ fb) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -139,7 +137,11 @@ hipError_t launch_p2pl_eval(icp_handle *h, const void *d_pairs, size_t n_, const
   hipError_t e;
   hipLaunchKernelGGL(k_p2pl_residual, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const PlanePair *)d_pairs, n, T,
                      (double2 *)d_fa, (double2 *)d_fb);
-  if ((e = launch_sel_init(h, n_)) != hipSuccess) return e;
+  if (w.gn_dirty) {  // (first use, or a NaN left its flag behind: the caller sets it when it reads one)
+    if ((e = launch_sel_init(h, n_)) != hipSuccess) return e;
+    w.gn_dirty = false;
+  }
+  // (the full key: dimension 1 is n equal keys, which no candidate list holds)
   if ((e = launch_stddevs(h, d_fa, d_fb, n_, transform_identity())) != hipSuccess) return e;
   int blocks, threads;
   reduce_geometry(n_, &blocks, &threads);
@@ -147,7 +149,6 @@ hipError_t launch_p2pl_eval(icp_handle *h, const void *d_pairs, size_t n_, const
                      (const GnScalars *)w.d_scal, w.d_partials);
   hipLaunchKernelGGL(k_final_reduce, dim3(1), dim3(kReduceThreads), 0, h->stream, (const double *)w.d_partials, blocks,
                      kNAcc, (const GnScalars *)w.d_scal, w.h_res);
-  w.gn_dirty = true;  // the radix path leaves its selection state behind
   return hipGetLastError();
 }
 

@@ -24,7 +24,6 @@
 
 namespace icp {
 
-hipError_t launch_sel_init(icp_handle *h, size_t n);
 __global__ void k_win_hist_sums(const double2 *__restrict__ a, const double2 *__restrict__ b, Pose T,
                                 double *__restrict__ rx, double *__restrict__ ry, unsigned n, WinParams P, uint32_t *whist,
                                 WinState *st, GnScalars *scal, double *partials, int status_cls);

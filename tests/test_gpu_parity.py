@@ -608,14 +608,11 @@ def test_auto_mode_picks_grid_for_large_targets_and_brute_for_small():
     assert I.lib().icp_get_nn_mode(small._h) == I.NN_BRUTE
 
 
-# ------------------------------------- fast selection pipeline: overflow -> radix fallback --
+# ------------------------------- short selection pipeline: overflow -> the full-key selection --
 
 
-@pytest.mark.parametrize("n", [900, 10_000, 200_001])
-def test_weighted_gn_with_a_run_of_duplicates_at_the_median(n):
-    """30 % of the x residuals are one exact value sitting on the median: more equal-prefix
-    keys than the candidate buffer holds, so the short pipeline must hand over to the general
-    radix select -- same bits either way."""
+def run_at_the_median(n):
+    """residuals whose x has a run of 30 % exact zeros on the median, the rest evenly either side"""
     rng = np.random.default_rng(n)
     a = rng.normal(size=(n, 2)) * 10
     r = rng.normal(size=(n, 2)) * 0.2
@@ -623,13 +620,123 @@ def test_weighted_gn_with_a_run_of_duplicates_at_the_median(n):
     r[:k, 0] = 0.0
     r[k:k + (n - k) // 2, 0] = -np.abs(r[k:k + (n - k) // 2, 0]) - 1e-3
     r[k + (n - k) // 2:, 0] = np.abs(r[k + (n - k) // 2:, 0]) + 1e-3
-    b = a - r  # identity pose: residual = a - b = r exactly? (a - (a - r)) may round; fine, oracle sees the same
+    return a, a - r  # identity pose: residual = a - b = r exactly? (a - (a - r)) may round; fine, oracle sees the same
+
+
+@pytest.mark.parametrize("n", [900, 10_000, 200_001])
+def test_weighted_gn_with_a_run_of_duplicates_at_the_median(n):
+    """30 % of the x residuals are one exact value sitting on the median: more equal-prefix
+    keys than the candidate buffer holds, so the short pipeline must hand over to the full-key
+    selection -- same bits either way."""
+    a, b = run_at_the_median(n)
     T = I.Transform()
     got = I.weighted_gauss_newton_update(T, a, b)
     blocks, threads = I.reduce_geometry(n)
     rc, want, _ = O.weighted_gauss_newton_update_tree(opose(T), a, b, blocks, threads)
     assert rc == O.OK and got is not None
     assert np.array_equal(got, want)
+
+
+def exact_x_pairs(rx, seed):
+    """pairs whose x residual under the identity pose is exactly rx (((1 rx + 0 a_y) + 0) - 0), so equal values stay
+    equal keys; y: ordinary residuals"""
+    rng = np.random.default_rng(seed)
+    rx = rng.permutation(np.asarray(rx, dtype=np.float64))
+    ay = rng.normal(size=rx.size) * 10
+    ry = rng.normal(size=rx.size) * 0.2
+    return np.stack([rx, ay], axis=1), np.stack([np.zeros(rx.size), ay - ry], axis=1)
+
+
+def stddevs_and_update_equal_the_oracle(a, b):
+    """the full-key selection alone (residual_stddevs) and whatever serves the weighted update, bit for bit; returns
+    how far (short pipeline, full-key selection) of icp_gn_path_counters moved with the update"""
+    T = I.Transform()
+    rc, want_sigma = O.calc_stddevs(a - b)  # (the identity pose's residuals: a - b, exactly)
+    assert rc == O.OK
+    got_sigma = I.residual_stddevs(T, a, b)
+    assert np.array_equal(got_sigma, want_sigma), (got_sigma, want_sigma)
+    blocks, threads = I.reduce_geometry(len(a))
+    rc, want, _ = O.weighted_gauss_newton_update_tree(opose(T), a, b, blocks, threads)
+    assert rc == O.OK and np.all(np.isfinite(want))
+    c0 = I.gn_path_counters()
+    got = I.weighted_gauss_newton_update(T, a, b)
+    c1 = I.gn_path_counters()
+    assert got is not None and np.array_equal(got, want), (got, want)
+    return c1[2] - c0[2], c1[3] - c0[3]
+
+
+def test_the_two_middle_keys_differ_in_the_last_bit_only():
+    """n = 4000: 1500 copies of 0.5 and 1500 of the next double sit on the median of x, so the lower and upper middle
+    statistics share every digit but the last, 4-bit one: the pair of searches splits there, in the launch that ends
+    the stage."""
+    rng = np.random.default_rng(4000)
+    lo, hi = -1.0 - rng.permutation(500) / 512.0, 2.0 + rng.permutation(500) / 512.0  # (distinct, exact)
+    rx = np.concatenate([lo, np.full(1500, 0.5), np.full(1500, np.nextafter(0.5, 1.0)), hi])
+    a, b = exact_x_pairs(rx, 1)
+    assert len(np.unique(a[:, 0])) == 1002
+    short, full = stddevs_and_update_equal_the_oracle(a, b)
+    assert full == 1, (short, full)
+
+
+def test_only_the_mad_stage_overflows_the_candidate_lists():
+    """n = 4001: the median of x is one of 1001 distinct values, the MAD lies in a run of 1500 equal distances -- the
+    short pipeline gets through its median stage and gives up in the second."""
+    rx = np.concatenate([np.full(1500, -1.0), np.full(1500, 1.0), (np.arange(1001) - 499) / 1024.0])  # (median 2^-10)
+    a, b = exact_x_pairs(rx, 2)
+    short, full = stddevs_and_update_equal_the_oracle(a, b)
+    assert short == 1 and full == 1, (short, full)
+
+
+@pytest.mark.parametrize("n", [1025, 5001])
+def test_a_run_at_the_median_of_an_odd_count_and_just_past_the_single_workgroup(n):
+    """Odd n: one order statistic per dimension, the paired searches never split.  1025: the first size the
+    one-workgroup evaluation does not take (its run of 307 fits the candidate lists; residual_stddevs selects on the
+    full key regardless)."""
+    a, b = run_at_the_median(n)
+    a, b = exact_x_pairs(a[:, 0] - b[:, 0], n)
+    short, full = stddevs_and_update_equal_the_oracle(a, b)
+    assert full == (1 if int(0.3 * n) > 1024 else 0), (short, full)
+
+
+def test_the_sigma_only_selection_leaves_the_rest_state_behind():
+    """residual_stddevs twice, then a weighted update of clean pairs, all on the scratch handle: the second and third
+    calls start from what the selection without sums cleared itself."""
+    a, b = run_at_the_median(5000)
+    T = I.Transform()
+    _, want = O.calc_stddevs(a - b)
+    for _ in range(2):
+        assert np.array_equal(I.residual_stddevs(T, a, b), want)
+    a2, b2 = make_pairs(5000, 77)
+    T2 = I.Transform([0.39, -0.31, 0.0199])
+    blocks, threads = I.reduce_geometry(5000)
+    rc, want2, _ = O.weighted_gauss_newton_update_tree(opose(T2), a2, b2, blocks, threads)
+    assert rc == O.OK
+    assert np.array_equal(I.weighted_gauss_newton_update(T2, a2, b2), want2)
+
+
+def test_a_point_to_point_estimate_after_a_point_to_line_estimate_on_one_handle():
+    """The line estimate's evaluations select on the full key and leave the handle's selection scratch at rest: the
+    point-to-point estimate behind them (>= 4096 sources: the host-stepped pipelines) finds what a fresh handle finds."""
+    dst = load_scan2d(os.path.join(GOLDEN, "scans2d", "002.txt"))
+    src = load_scan2d(os.path.join(GOLDEN, "scans2d", "001.txt"))
+    rng = np.random.default_rng(5)
+    big = np.concatenate([src + rng.normal(size=src.shape) * 0.02 for _ in range(4096 // len(src) + 1)])
+    assert len(big) >= 4096
+
+    def line(icp):
+        icp.compute_line_normals(10)
+        T, idx, inner = icp.estimate_point_to_line(src, I.Transform(), 5, return_info=True)
+        return T.as_array(), idx, inner
+
+    def point(icp):
+        T, idx, inner = icp.estimate(big, I.Transform(), 5, return_info=True)
+        return T.as_array(), idx, inner
+
+    one = I.Icp2d(dst)
+    got_line, got_point = line(one), point(one)
+    for got, want in ((got_line, line(I.Icp2d(dst))), (got_point, point(I.Icp2d(dst)))):
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w)
 
 
 def test_estimate_transform_small_inputs_use_the_single_launch_stages():

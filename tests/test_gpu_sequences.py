@@ -44,7 +44,7 @@ class GpuDevice:
       * single_launch_counters: one launch exactly where the call is ungated, n <= 1 024, m <= 2 048 and the grid is not
         forced; such a call moves no other counter;
       * icp_last_fold_order: a cell-sorted snapshot exactly beyond 65 536 sources on the grid engine;
-      * gn_path_counters / gn_loop_counters: the six-pass radix select, the evaluation's last resort, never runs; below
+      * gn_path_counters / gn_loop_counters: the full-key selection, the evaluation's last resort, never runs; below
         4 096 pairs no window is started and no loop launched, and a call that applied an update was served by the short
         pipeline; from 4 096 sources on an ungated call that applied an update was served by a window, the one-launch
         loop (which counts as windows started) or the short pipeline, and launched a loop or placed a bet.  Which of
@@ -169,7 +169,7 @@ class GpuDevice:
         if small:  # the whole call was that launch
             assert not any(gn) and not any(loop) and certs == 0, ("a single-launch call moved another counter", what)
         else:
-            assert radix == 0, ("the six-pass radix select ran", what)
+            assert radix == 0, ("the full-key selection ran", what)
             if pairs < KWIN_MIN_N:
                 assert tried == 0 and missed == 0 and not any(loop), ("a window or a loop below 4 096 pairs", what)
                 if applied:

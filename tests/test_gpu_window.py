@@ -92,7 +92,7 @@ def test_window_with_changing_scale():
 def test_window_duplicates_overload_a_bin():
     """30 % of the x residuals are one exact value on the median: more candidates in the median
     bin than the window pipeline keeps -> it reports a miss; the seven-launch pipeline overflows
-    too and the radix path serves the evaluation.  Same bits."""
+    too and the full-key selection serves the evaluation.  Same bits."""
     n = 200_001
     rng = np.random.default_rng(n)
     a = rng.normal(size=(n, 2)) * 10
