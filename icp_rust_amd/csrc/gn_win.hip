@@ -960,11 +960,11 @@ struct PickLds {  // (the descriptor lists are dead when the selections start: t
 // what the other needs write-through (WinJoin), drains, and takes the evaluation's ticket; the one that draws the
 // second ticket of the pair reads the other's part (sc1 loads), solves for the run-ahead search and releases the result.
 // Nobody waits for anybody: a workgroup that arrives first simply leaves.
-struct PickDimLds {  // (the descriptor lists are dead when the selections start: their LDS is overlaid)
+struct PickDimLds {  // (the candidate lists are in registers when the selections start: their LDS is overlaid)
   union {
     struct {
       uint32_t cum[kWinBins];
-      uint32_t med[kWinCapMed], ring[kWinCapRing];
+      double med[kWinCapMed], ring[kWinCapRing];  // the candidates themselves, dense, in no particular order
     } g;
     SelectLds<1> sel;
   };
@@ -1094,8 +1094,8 @@ struct PickArgs {
   WinJoin *join;
 };
 
-// Dimension d of the evaluation A.  primary: this launch keeps the evaluation's state in A.st (k_win_pick2's second
-// evaluation does not: nothing reads it on that path).
+// Dimension d of the evaluation A.  primary (a run-time value, uniform in the workgroup): this workgroup keeps the
+// evaluation's state in A.st (k_win_pick2's second evaluation does not: nothing reads it on that path).
 __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d, const bool primary, PickDimLds &L) {
   const unsigned n = A.n;
   WinState *const st = A.st;
@@ -1104,9 +1104,8 @@ __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d
   WinJoin *const J = A.join;
   constexpr int PM = kWinCapMed / kReduceThreads, PR = kWinCapRing / kReduceThreads;
   static_assert(kReduceMaxBlocks * 2 == kReduceThreads, "two threads per segment");
-  static_assert(kBktStage <= (1 << 12), "descriptor: segment << 12 | position");
   __shared__ double s_tot[kNSum + 1];
-  __shared__ unsigned s_cnt[2];
+  __shared__ unsigned s_wcnt[kReduceThreads / 64];  // the waves' candidate counts
   __shared__ int s_last;
   __shared__ unsigned s_pflags;
   __shared__ double s_pms[2];
@@ -1119,7 +1118,6 @@ __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d
 #else
 #define PSTAMP(k)
 #endif
-  if (tid < 2) s_cnt[tid] = 0;
   // (the two flags of the launch in front of this one are asked for first: the lists' branch needs them at once)
   const int nan_flag = __hip_atomic_load(&A.scal->nan_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const unsigned stage_overflow = __hip_atomic_load(&st->stage_overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1134,57 +1132,88 @@ __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d
   double med = 0., sig = 0.;
   {
     const bool usable = !fail && !bucket_miss;  // (uniform)
+    // Lists by scan, candidates by their listers: thread (segment w, part) reads the directory of segment w for the median
+    // run (part 0) or the ring's two arcs (part 1) -- the members of a run of consecutive bins are contiguous in the
+    // segment: the run's first offset .. the offset behind its last bin -- and at once asks for its OWN members: kPickU
+    // predicated loads in flight (a segment holds 3 to 4.5 of the ~800 to ~1100 ring candidates of a 1M-pair evaluation,
+    // 0.3 to 0.7 of the median's: past 12 in one of 256 lists once in ~6 launches at most; the rest, if any, goes through the
+    // loop below).  While they travel the counts are scanned -- the wave's DPP scan and the eight wave totals, waves 0-3
+    // the median's, 4-7 the ring's -- which gives every lister its place in the dense value array and the workgroup the
+    // two totals.  (Until round 9: a returning LDS atomic per lister, (segment, position) words in LDS, a barrier, and
+    // only then the loads, by whoever drew the slot.)
+    constexpr int kPickU = 12;
     const unsigned w = tid & (unsigned)(kReduceMaxBlocks - 1), part = tid / (unsigned)kReduceMaxBlocks;
+    const unsigned lane = tid & 63u, wave = tid >> 6;
+    unsigned p0 = 0, l0 = 0, p1 = 0, l1 = 0;  // the thread's members: [p0, p0 + l0) then [p1, p1 + l1) of its segment
     if (usable && (int)w < A.segments) {
       const unsigned short *dir = dir_all + (size_t)w * kBktDir;
-      // (the members of a run of consecutive bins are contiguous in the segment: the run's first offset .. the offset
-      // behind its last bin)
       if (part == 0) {
         const unsigned fm = word_to_fine(d, R.mlo), len_m = R.mhi - R.mlo + 1u;
         const unsigned m0 = dir[fm], m_end = dir[fm + len_m];
-        const unsigned cm = m_end - m0;
-        if (cm) {
-          const unsigned pos = atomicAdd(&s_cnt[0], cm);
-          for (unsigned k = 0; k < cm; ++k)
-            if (pos + k < (unsigned)kWinCapMed) L.g.med[pos + k] = (w << 12) | (m0 + k);
-        }
+        p0 = m0;
+        l0 = m_end - m0;
       } else {
         const unsigned fa = word_to_fine(d, R.a0), fb = word_to_fine(d, R.i1 + 1u);
         const unsigned len_a = R.i0 - R.a0, len_b = R.b1 - R.i1;
         const unsigned a_beg = dir[fa], a_end = dir[fa + len_a], b_beg = dir[fb], b_end = dir[fb + len_b];
-        const unsigned cr = (a_end - a_beg) + (b_end - b_beg);
-        if (cr) {
-          unsigned pos = atomicAdd(&s_cnt[1], cr);
-          for (unsigned k = a_beg; k < a_end; ++k, ++pos)
-            if (pos < (unsigned)kWinCapRing) L.g.ring[pos] = (w << 12) | k;
-          for (unsigned k = b_beg; k < b_end; ++k, ++pos)
-            if (pos < (unsigned)kWinCapRing) L.g.ring[pos] = (w << 12) | k;
-        }
+        p0 = a_beg;
+        l0 = a_end - a_beg;
+        p1 = b_beg;
+        l1 = b_end - b_beg;
+      }
+    }
+    const unsigned cnt = l0 + l1;
+    // (what is loaded stays inside the segment whatever the directory says; the totals below take the counts as they are)
+    const unsigned nld = cnt < (unsigned)kBktStage ? cnt : (unsigned)kBktStage;
+    const double *const seg = seg_all + (size_t)w * kBktStage;
+    auto member = [&](unsigned k) -> unsigned { return k < l0 ? p0 + k : p1 + (k - l0); };  // k-th member's place
+    double own[kPickU];
+#pragma unroll
+    for (int u = 0; u < kPickU; ++u) {
+      const unsigned at = member((unsigned)u);
+      own[u] = ((unsigned)u < nld && at < (unsigned)kBktStage) ? seg[at] : 0.;
+    }
+    const unsigned inc = wave_scan_inclusive(cnt);
+    if (lane == 63u) s_wcnt[wave] = inc;
+    __syncthreads();
+    PSTAMP(2);
+    unsigned before = 0, tot_m = 0, tot_r = 0;
+    {
+      constexpr unsigned HW = kReduceThreads / 64 / 2;  // waves per part
+#pragma unroll
+      for (unsigned q = 0; q < 2 * HW; ++q) {
+        const unsigned x = s_wcnt[q];
+        if (q < HW) tot_m += x;
+        else tot_r += x;
+        before += (q < wave && (q < HW) == (wave < HW)) ? x : 0u;
+      }
+    }
+    // (the listed counts are cross-checked against the histogram: a mismatch is a miss)
+    if (usable) bucket_miss = tot_m != sel.med_cnt || tot_r != sel.ring_cnt;
+    const bool go = usable && !bucket_miss;
+    if (go) {  // (uniform; the totals are the histogram's, which resolve_window holds to the caps)
+      double *const vals = part ? L.g.ring : L.g.med;
+      const unsigned cap = part ? (unsigned)kWinCapRing : (unsigned)kWinCapMed;
+      const unsigned off = before + inc - cnt;
+#pragma unroll
+      for (int u = 0; u < kPickU; ++u)
+        if ((unsigned)u < nld && off + (unsigned)u < cap) vals[off + (unsigned)u] = own[u];
+      for (unsigned k = kPickU; k < nld; ++k) {  // a crowded lister's rest
+        const unsigned at = member(k);
+        if (at < (unsigned)kBktStage && off + k < cap) vals[off + k] = seg[at];
       }
     }
     __syncthreads();
-    PSTAMP(2);
-    // (the listed counts are cross-checked against the histogram: a mismatch is a miss)
-    if (usable) bucket_miss = s_cnt[0] != sel.med_cnt || s_cnt[1] != sel.ring_cnt;
-    const bool go = usable && !bucket_miss;
     double vm[1][PM], vr[1][PR];
 #pragma unroll
     for (int u = 0; u < PM; ++u) {
       const unsigned e = tid + u * kReduceThreads;
-      vm[0][u] = 0.;
-      if (go && e < sel.med_cnt) {
-        const uint32_t x = L.g.med[e];
-        vm[0][u] = seg_all[(size_t)(x >> 12) * kBktStage + (x & 0xfffu)];
-      }
+      vm[0][u] = (go && e < sel.med_cnt) ? L.g.med[e] : 0.;
     }
 #pragma unroll
     for (int u = 0; u < PR; ++u) {
       const unsigned e = tid + u * kReduceThreads;
-      vr[0][u] = 0.;
-      if (go && e < sel.ring_cnt) {
-        const uint32_t x = L.g.ring[e];
-        vr[0][u] = seg_all[(size_t)(x >> 12) * kBktStage + (x & 0xfffu)];
-      }
+      vr[0][u] = (go && e < sel.ring_cnt) ? L.g.ring[e] : 0.;
     }
     // this dimension's histogram row starts from zero for the next evaluation (write-through, drained before the
     // ticket: the host may hand the next evaluation to the handle's other stream as soon as it sees the result)
@@ -1195,7 +1224,7 @@ __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d
         __hip_atomic_store(&row[tid + u * kReduceThreads], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     fold256_half_reduce(fx, A.sum_blocks, s_tot + d * kFoldH);  // (a barrier inside)
-    __syncthreads();  // (the descriptor lists are read: the selections may overlay them)
+    __syncthreads();  // (the value arrays are read: the selections may overlay them)
     PSTAMP(3);
     const unsigned klo = (n - 1) / 2, khi = n / 2;
     if (go) {
@@ -1235,7 +1264,7 @@ __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d
   if (!s_last) {
 #ifdef ICP_WIN_DEBUG
     if (tid == 0 && A.seq % 16 == 5)
-      printf("[P%d first] resolve %lld list %lld load+fold %lld sel1 %lld sel2 %lld store %lld (x10ns) cnt %u %u\n", d,
+      printf("[P%d first] resolve %lld dir+scan %lld place+fold %lld sel1 %lld sel2 %lld store %lld (x10ns) cnt %u %u\n", d,
              pst[1] - pst[0], pst[2] - pst[1], pst[3] - pst[2], pst[4] - pst[3], pst[5] - pst[4], pst[6] - pst[5],
              sel.med_cnt, sel.ring_cnt);
 #endif
@@ -1285,7 +1314,7 @@ __device__ __forceinline__ void win_pick_dim_body(const PickArgs &A, const int d
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   PSTAMP(9);
   if (tid == 0 && A.seq % 16 == 5)
-    printf("[P%d last] resolve %lld list %lld load+fold %lld sel1 %lld sel2 %lld store %lld ticket+loads %lld ahead %lld "
+    printf("[P%d last] resolve %lld dir+scan %lld place+fold %lld sel1 %lld sel2 %lld store %lld ticket+loads %lld ahead %lld "
            "publish %lld (x10ns) cnt %u %u\n", d, pst[1] - pst[0], pst[2] - pst[1], pst[3] - pst[2], pst[4] - pst[3],
            pst[5] - pst[4], pst[6] - pst[5], pst[7] - pst[6], pst[8] - pst[7], pst[9] - pst[8], sel.med_cnt, sel.ring_cnt);
 #endif
@@ -1308,12 +1337,18 @@ __global__ __launch_bounds__(kWinThreads, 4) void k_win_hist_sums_bkt2(HistBktAr
   if (blockIdx.x < half) win_hist_sums_bkt_body(A, blockIdx.x, half, S);
   else win_hist_sums_bkt_body(B, blockIdx.x - half, half, S);
 }
-// four workgroups: 0 and 1 finish dimensions x and y of A, 2 and 3 those of B (whose `st` is not maintained -- nothing
-// reads it on this path)
-__global__ __launch_bounds__(kReduceThreads) void k_win_pick2(PickArgs A, PickArgs B) {
+// four workgroups: 0 and 1 finish dimensions x and y of e[0], 2 and 3 those of e[1] (whose `st` is not maintained --
+// nothing reads it on this path).  ONE copy of the body in the kernel's code (two were 59 KB, each fetched cold by every
+// launch): the evaluation is an index into ONE kernel argument, which stays where it is -- scalar loads at an offset
+// that is uniform in the workgroup, as the dimension's window always was.  (Two PickArgs chosen between by reference or
+// member by member were copied to scratch memory: the window's bounds are picked by selects that become an index.)
+struct PickPairArgs {
+  PickArgs e[2];
+};
+__global__ __launch_bounds__(kReduceThreads) void k_win_pick2(PickPairArgs X) {
   __shared__ PickDimLds L;
-  if (blockIdx.x < 2u) win_pick_dim_body(A, (int)blockIdx.x, true, L);
-  else win_pick_dim_body(B, (int)blockIdx.x - 2, false, L);
+  const unsigned second = blockIdx.x >> 1;
+  win_pick_dim_body(X.e[second], (int)(blockIdx.x & 1u), second == 0u, L);
 }
 
 // ---- P across ranks (round 6): the finishing workgroup of an evaluation whose points are SHARDED -----------------
@@ -1913,9 +1948,10 @@ hipError_t launch_bkt_pair(icp_handle *h, hipStream_t s, GnCtx &first, const dou
   hipLaunchKernelGGL(k_win_hist_sums_bkt2, dim3(2 * blocks), dim3(kWinThreads), 0, s,
                      bkt_hist_args(first, (const double2 *)a1, (const double2 *)b1, transform_identity(), n, P1),
                      bkt_hist_args(second, (const double2 *)a2, (const double2 *)b2, T2, n, P2));
-  hipLaunchKernelGGL(k_win_pick2, dim3(4), dim3(kReduceThreads), 0, s,
-                     bkt_pick_args(first, n, P1, ahead_on, ahead_outer, w.d_ahead),
-                     bkt_pick_args(second, n, P2, false, transform_identity()));
+  PickPairArgs X;
+  X.e[0] = bkt_pick_args(first, n, P1, ahead_on, ahead_outer, w.d_ahead);
+  X.e[1] = bkt_pick_args(second, n, P2, false, transform_identity());
+  hipLaunchKernelGGL(k_win_pick2, dim3(4), dim3(kReduceThreads), 0, s, X);
   second.bkt_pair_launched = true;
   return hipGetLastError();
 }
