@@ -232,6 +232,11 @@ SIGNATURES = {
     "icp_thin_targets": (C.c_int, [_vp, C.c_double, _vp, C.POINTER(_sz)]),
     "icp_multi_thin_targets": (C.c_int, [_vp, C.c_double, C.POINTER(_sz)]),
     "icp_grid_thin_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_target_neighbours": (C.c_int, [_vp, C.c_int, _sz, _sz, _vp, _vp]),
+    "icp_target_neighbours_device": (C.c_int, [_vp, C.c_int, _sz, _sz, _vp, _vp]),
+    "icp_remove_radius_outliers": (C.c_int, [_vp, C.c_double, _sz, _vp, C.POINTER(_sz)]),
+    "icp_remove_statistical_outliers": (C.c_int, [_vp, C.c_int, C.c_double, _vp, C.POINTER(_sz), _dp]),
+    "icp_grid_outlier_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "icp_evaluate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_evaluate_point_to_plane_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_compute_target_line_normals": (C.c_int, [_vp, C.c_int]),

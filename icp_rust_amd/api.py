@@ -115,6 +115,78 @@ def voxel_downsample(points, voxel_size, return_index=False, device=-1):
     return (out, index[:kept.value].copy()) if return_index else out
 
 
+def _list_length(k, most, what="k"):
+    if int(k) != k or not 1 <= int(k) <= most:
+        raise ValueError(f"{what} must be an integer in [1, {most}], got {k}")
+    return int(k)
+
+
+def _radius_rule(radius, min_neighbours):
+    r = float(radius)
+    if not r >= 0.0:  # (also a NaN)
+        raise ValueError(f"a radius must be >= 0 (or +inf), got {r}")
+    if int(min_neighbours) != min_neighbours or min_neighbours < 0:
+        raise ValueError(f"min_neighbours must be a count, got {min_neighbours}")
+    return r, int(min_neighbours)
+
+
+def _statistical_rule(k, std_ratio):
+    ratio = float(std_ratio)
+    if ratio != ratio:
+        raise ValueError("std_ratio must not be NaN")
+    return _list_length(k, 31), ratio
+
+
+def _filter_cloud(points, what, rule):
+    """the module-level filters: a temporary handle on `points`, one removal, the kept points (and their indices) from
+    its new_index table.  numpy in, numpy out; a contiguous float64 CUDA tensor in, CUDA tensors out."""
+    on_device = _is_device_tensor(points)
+    if on_device:
+        if points.dim() != 2 or points.shape[1] not in (2, 3):
+            raise ValueError(f"{what}: expected (n, 2) or (n, 3), got {tuple(points.shape)}")
+        dim, n = points.shape[1], points.shape[0]
+        _dev_points(points, dim, None, what)
+        p = points
+    else:
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] not in (2, 3):
+            raise ValueError(f"{what}: expected (n, 2) or (n, 3), got {p.shape}")
+        n, dim = p.shape
+    if n == 0:
+        kept = np.zeros(0, dtype=np.uint32)
+    else:
+        icp = (Icp2d if dim == 2 else Icp3d)(p)
+        try:
+            _, new_index = rule(icp)
+        finally:
+            icp.close()
+        kept = np.flatnonzero(new_index != 0xFFFFFFFF).astype(np.uint32)
+    if on_device:
+        import torch
+
+        index = torch.from_numpy(kept.astype(np.int64)).to(points.device)
+        return points[index], index.to(torch.int32)
+    return p[kept], kept
+
+
+def remove_radius_outliers(points, radius, min_neighbours, return_index=False):
+    """EXTENSION (icp_remove_radius_outliers, include/icp_mi355x.h section 23): the points with at least
+    `min_neighbours` points, themselves included, within `radius` (d^2 <= radius * radius), in order.  `points` as for
+    voxel_downsample; with return_index=True also the kept points' ascending indices."""
+    r, need = _radius_rule(radius, min_neighbours)
+    out, index = _filter_cloud(points, "points", lambda icp: icp.remove_radius_outliers(r, need, return_index=True))
+    return (out, index) if return_index else out
+
+
+def remove_statistical_outliers(points, k, std_ratio, return_index=False):
+    """EXTENSION (icp_remove_statistical_outliers, section 23): the points whose mean distance to their k nearest other
+    points is not above mean + std_ratio * deviation of that figure over the cloud, in order."""
+    kk, ratio = _statistical_rule(k, std_ratio)
+    out, index = _filter_cloud(points, "points",
+                               lambda icp: icp.remove_statistical_outliers(kk, ratio, return_index=True))
+    return (out, index) if return_index else out
+
+
 class Transform:
     """`icp::Transform` (src/transform.rs:6-51)."""
 
@@ -815,6 +887,55 @@ class _Icp:
         """(thins served by moving the search grid's sorted records, thins that rebuilt the grid)"""
         out = (C.c_uint64 * 2)()
         check(lib().icp_grid_thin_counters(self._h, out), "icp_grid_thin_counters")
+        return int(out[0]), int(out[1])
+
+    # -- EXTENSION (not in the reference): neighbour lists and outlier removal, include/icp_mi355x.h section 23 --
+    def neighbours(self, k, first=0, count=None):
+        """(idx uint32, d2 float64), both (count, k): for each target of [first, first + count) its min(k, m) nearest
+        targets, itself included, ordered by (d^2, index); rows padded with 0xffffffff / +inf (icp_target_neighbours)."""
+        k = _list_length(k, 32)
+        count = self.target_count - first if count is None else int(count)
+        idx = np.empty((max(count, 0), k), dtype=np.uint32)
+        d2 = np.empty((max(count, 0), k), dtype=np.float64)
+        check(lib().icp_target_neighbours(self._h, k, int(first), count, _ptr(idx), _ptr(d2)), "icp_target_neighbours")
+        return idx, d2
+
+    def _removal(self, entry, call, return_index):
+        m_before = self.target_count
+        index = np.zeros(max(m_before, 1), dtype=np.uint32) if return_index else None
+        removed = C.c_size_t(0)
+        check(call(C.c_void_p(index.ctypes.data) if return_index else None, C.byref(removed)), entry)
+        if removed.value:
+            self._keep = None  # the kept cloud lives in the handle's own storage
+        self.m = self.target_count
+        return int(removed.value), (index[:m_before] if return_index else None)
+
+    def remove_radius_outliers(self, radius, min_neighbours, return_index=False):
+        """Remove the targets with fewer than `min_neighbours` targets, themselves included, within `radius` (d^2 <=
+        radius * radius; icp_remove_radius_outliers).  Like crop: order and normals are kept and the handle then
+        behaves like a fresh one on the kept cloud.  Returns the number removed; with return_index=True also new_index."""
+        r, need = _radius_rule(radius, min_neighbours)
+        removed, index = self._removal("icp_remove_radius_outliers",
+                                       lambda ix, rm: lib().icp_remove_radius_outliers(self._h, r, need, ix, rm),
+                                       return_index)
+        return (removed, index) if return_index else removed
+
+    def remove_statistical_outliers(self, k=16, std_ratio=2.0, return_index=False, return_stats=False):
+        """Remove the targets whose mean distance to their k nearest other targets exceeds mean + std_ratio * deviation
+        of that figure over all targets (icp_remove_statistical_outliers).  Returns the number removed, then new_index
+        (return_index) and (mean, deviation, threshold) (return_stats) where asked for."""
+        kk, ratio = _statistical_rule(k, std_ratio)
+        stats = (C.c_double * 3)()
+        removed, index = self._removal(
+            "icp_remove_statistical_outliers",
+            lambda ix, rm: lib().icp_remove_statistical_outliers(self._h, kk, ratio, ix, rm, stats), return_index)
+        out = (removed,) + ((index,) if return_index else ()) + ((tuple(float(s) for s in stats),) if return_stats else ())
+        return out if len(out) > 1 else removed
+
+    def outlier_counters(self):
+        """(outlier filters served by moving the search grid's sorted records, filters that rebuilt the grid)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().icp_grid_outlier_counters(self._h, out), "icp_grid_outlier_counters")
         return int(out[0]), int(out[1])
 
     def reserve(self, capacity):

@@ -128,6 +128,8 @@ int remove_marked_targets(icp_handle *h, uint32_t *w, uint32_t *cnt, unsigned lo
                           unsigned long long &rebuilt, uint32_t *new_index, size_t *removed);
 // the cached workspace of icp_voxel_downsample* and icp_thin_targets (voxel.hip), for icp_trim_pool
 void voxel_trim();
+// ... of icp_target_neighbours and the two outlier filters (outlier.hip)
+void outlier_trim();
 
 }  // namespace api
 }  // namespace icp

@@ -341,6 +341,7 @@ struct Grid {
   unsigned long long appends_moved = 0, appends_rebuilt = 0;  // observability (icp_grid_append_counters)
   unsigned long long crops_moved = 0, crops_rebuilt = 0;      // ... and of icp_crop_targets (icp_grid_crop_counters)
   unsigned long long thins_moved = 0, thins_rebuilt = 0;      // ... and of icp_thin_targets (icp_grid_thin_counters)
+  unsigned long long filters_moved = 0, filters_rebuilt = 0;  // ... and of the outlier filters (icp_grid_outlier_counters)
   uint32_t *d_flag = nullptr;   // one word: a new point outside the grid's box (or not finite)
 };
 

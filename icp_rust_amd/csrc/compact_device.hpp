@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact_chunks(const uint32
   if (threadIdx.x == 0) sums[blockIdx.x] = s;
 }
 
-hipError_t launch_compact_chunks(const uint32_t *cnt, unsigned tiles, uint32_t *sums, hipStream_t stream) {
+[[maybe_unused]] hipError_t launch_compact_chunks(const uint32_t *cnt, unsigned tiles, uint32_t *sums, hipStream_t stream) {
   hipLaunchKernelGGL(k_compact_chunks, dim3(compact_chunks(tiles)), dim3(kCompactThreads), 0, stream, cnt, tiles, sums);
   return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // What the single-handle kernels of the two normal residuals share -- point-to-plane on a 3-D handle (include/icp_mi355x.h
 // section 7) and point-to-line on a 2-D one (section 14) -- beside normal_batch_device.hpp's NormalResidual<DIM> for the
 // one-workgroup kernels: ONE body per piece, DIM = 2 or 3, so that the dimensions cannot drift apart.
+//   grid_k_nearest<DIM, KMAX>     the ring search and the (d^2, index) insertion, shared with outlier.hip's lists
 //   target_normals_by_grid<DIM>   k_target_normals / k_line_normals (p2plane.hip): one lane per target, its k nearest
 //                                 targets through the grid, the normal from them
 //   normal_gather<DIM>            k_p2pl_gather / k_line_gather (p2plane.hip): the pairs of all correspondences
@@ -29,31 +30,22 @@ struct NormalSingle {
   static constexpr bool kClampGather = DIM == 2;
 };
 
-// One lane per target: its k nearest targets through the grid (Chebyshev rings of cells around its own cell -- x cells
-// finer by fx; a 2-D grid has one layer, n[2] == 1 -- until the k-th distance is covered by the visited block), then the
-// covariance's smallest eigenvector.  The running k-best lists live in LDS (dynamic indexing).  Workgroups of 64.
-template <int DIM>
-__device__ __forceinline__ void target_normals_by_grid(const double *__restrict__ dst, unsigned m, const GridParams &g,
-                                                       const uint32_t *__restrict__ start,
-                                                       const GridPoint *__restrict__ pts, int kk,
-                                                       double *__restrict__ normals, unsigned first) {
-  using G = NormalSingle<DIM>;
-  __shared__ double s_d[64][kNormalKMax];
-  __shared__ uint32_t s_i[64][kNormalKMax];
-  const unsigned i = first + blockIdx.x * 64 + threadIdx.x;  // (targets [first, m): all of them, or the appended ones)
-  if (i >= m) return;
-  double *bd = s_d[threadIdx.x];
-  uint32_t *bi = s_i[threadIdx.x];
-  double p[DIM];
+// The k nearest targets of the point p by (d^2, index), through the grid: Chebyshev rings of cells around p's own cell
+// (x cells finer by fx; a 2-D grid has one layer, n[2] == 1) until the k-th distance is covered by the visited block.
+// The running lists bd / bi (KMAX entries each, the caller's LDS row: dynamic indexing) end sorted; returns their
+// length.  ONE body behind the normals kernels (KMAX = 16, guards of NormalSingle<DIM>) and the neighbour lists of
+// section 23 (outlier.hip: KMAX = 16 or 32, the 3-D guards in both dimensions).  1 <= k <= min(KMAX, m) unless CLAMP.
+template <int DIM, int KMAX, bool SKIP_NAN, bool CLAMP>
+__device__ __forceinline__ int grid_k_nearest(const double *__restrict__ dst, unsigned m, const GridParams &g,
+                                              const uint32_t *__restrict__ start, const GridPoint *__restrict__ pts,
+                                              const double (&p)[DIM], int k, double *bd, uint32_t *bi) {
   int c[DIM];
   for (int d = 0; d < DIM; ++d) {
-    p[d] = dst[(size_t)i * DIM + d];
     double t = floor((p[d] - g.lo[d]) * g.inv_h[d]);
     t = fmin(fmax(t, 0.), (double)(g.n[d] - 1));
     c[d] = (int)t;
   }
-  int k = kk < (int)m ? kk : (int)m;
-  if (G::kClampNeighbours) k = k < kNormalKMax ? k : kNormalKMax;  // (this only keeps the lists inside their rows)
+  if (CLAMP) k = k < KMAX ? k : KMAX;  // (this only keeps the lists inside their rows)
   int cnt = 0;
   int rmax = max(g.n[0], g.n[1]);
   if (DIM == 3) rmax = max(rmax, g.n[2]);
@@ -68,7 +60,7 @@ __device__ __forceinline__ void target_normals_by_grid(const double *__restrict_
         const uint32_t s = start[row + x0], e = start[row + x1 + 1];
         for (uint32_t j = s; j < e; ++j) {
           uint32_t ti = pts[j].idx;
-          if (G::kClampNeighbours && ti >= m) ti = 0;  // (a record's idx is always < m: this only keeps the reads in bounds)
+          if (CLAMP && ti >= m) ti = 0;  // (a record's idx is always < m: this only keeps the reads in bounds)
           const double dx = p[0] - dst[(size_t)ti * DIM], dy = p[1] - dst[(size_t)ti * DIM + 1];
           double dd = dx * dx + dy * dy;
           if (DIM == 3) {
@@ -78,7 +70,7 @@ __device__ __forceinline__ void target_normals_by_grid(const double *__restrict_
           // A NaN distance (a NaN coordinate in either target) is no neighbour: (d^2, index) does not order it, and a
           // list that took it in would depend on the order of the records inside a cell, which the grid's scatter
           // leaves to its atomics -- the normals of such a cloud would differ from one handle to the next.
-          if (G::kSkipNanDistance && dd != dd) continue;
+          if (SKIP_NAN && dd != dd) continue;
           // insertion by (d^2, index) into the k best
           if (cnt == k && !(dd < bd[k - 1] || (dd == bd[k - 1] && ti < bi[k - 1]))) continue;
           int pos = cnt < k ? cnt : k - 1;
@@ -105,6 +97,28 @@ __device__ __forceinline__ void target_normals_by_grid(const double *__restrict_
     cover -= 1e-9 * mag;
     if (cnt == k && cover > 0. && bd[k - 1] < cover * cover) break;
   }
+  return cnt;
+}
+
+// One lane per target: its k nearest targets through the grid (grid_k_nearest), then the covariance's smallest
+// eigenvector.  The running k-best lists live in LDS (dynamic indexing).  Workgroups of 64.
+template <int DIM>
+__device__ __forceinline__ void target_normals_by_grid(const double *__restrict__ dst, unsigned m, const GridParams &g,
+                                                       const uint32_t *__restrict__ start,
+                                                       const GridPoint *__restrict__ pts, int kk,
+                                                       double *__restrict__ normals, unsigned first) {
+  using G = NormalSingle<DIM>;
+  __shared__ double s_d[64][kNormalKMax];
+  __shared__ uint32_t s_i[64][kNormalKMax];
+  const unsigned i = first + blockIdx.x * 64 + threadIdx.x;  // (targets [first, m): all of them, or the appended ones)
+  if (i >= m) return;
+  double *bd = s_d[threadIdx.x];
+  uint32_t *bi = s_i[threadIdx.x];
+  double p[DIM];
+  for (int d = 0; d < DIM; ++d) p[d] = dst[(size_t)i * DIM + d];
+  const int k = kk < (int)m ? kk : (int)m;
+  const int cnt = grid_k_nearest<DIM, kNormalKMax, G::kSkipNanDistance, G::kClampNeighbours>(dst, m, g, start, pts, p, k,
+                                                                                             bd, bi);
   double nrm[3] = {0., 0., 0.};  // (the tails behind the k best: shared with the batch kernels)
   const auto coord = [&](int j, int d) { return dst[(size_t)bi[j] * DIM + d]; };
   if constexpr (DIM == 3)

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .api import Icp2d, Icp3d, Transform, voxel_downsample
+from .api import Icp2d, Icp3d, Transform, remove_statistical_outliers, voxel_downsample
 from .scans import PacketFile, load_scan2d, write_packets
 from .synth import PACKETS_PER_FRAME, remove_invalid_values
 
@@ -130,7 +130,7 @@ def run_scan3d(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, p
 
 def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=None, max_frames=None,
                     point_to_plane=None, max_correspondence_distance=None, map_radius=None, quality_distance=None,
-                    qualities=None, scan_voxel=None, map_voxel=None):
+                    qualities=None, scan_voxel=None, map_voxel=None, scan_outliers=None):
     """EXTENSION, not in the reference (BASELINE.json configs[4]): the
     scan3d frames registered against a map that grows.  The map starts as frame 0 (filtered as
     examples/scan3d.rs:63-69 does); every later frame is registered against the whole map with
@@ -158,6 +158,9 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
     `map_voxel=v` (either residual): right after every frame's append the map is thinned the same way, world.thin(v):
     the lowest index wins, so every older map point stays and exactly the new points that fall into an occupied voxel
     go -- before update_normals, so that only survivors get a normal, and before the crop; None calls nothing.
+    `scan_outliers=(k, std_ratio)`: every incoming scan, frame 0 included, loses its statistical outliers
+    (remove_statistical_outliers, include/icp_mi355x.h section 23) after the scan_voxel thinning and before it is
+    registered and appended; None calls nothing.
     Returns (transforms, path_xy, map_handle)."""
     if point_to_plane and max_correspondence_distance is not None:
         raise ValueError("max_correspondence_distance applies to the point-to-point registration only")
@@ -166,7 +169,11 @@ def run_scan_to_map(packets, step=PACKETS_PER_FRAME, max_iter=20, icp_factory=No
 
     def frame(first):
         scan = remove_invalid_values(packets[first:first + step])
-        return scan if scan_voxel is None else voxel_downsample(scan, scan_voxel)
+        if scan_voxel is not None:
+            scan = voxel_downsample(scan, scan_voxel)
+        if scan_outliers is not None:
+            scan = remove_statistical_outliers(scan, scan_outliers[0], scan_outliers[1])
+        return scan
 
     world = icp_factory(frame(0))
     if point_to_plane:
@@ -227,6 +234,9 @@ def main(argv=None):
                     help="scan2map: thin every scan to one point per voxel of size V before it is registered (extension)")
     ap.add_argument("--map-voxel", type=float, default=None, metavar="V",
                     help="scan2map: thin the map to one point per voxel of size V after every append (extension)")
+    ap.add_argument("--scan-outliers", nargs=2, default=None, metavar=("K", "RATIO"),
+                    help="scan2map: drop every scan's statistical outliers (mean distance to the K nearest points above "
+                         "mean + RATIO deviations) before it is registered (extension)")
     args = ap.parse_args(argv)
     if args.loop == "scan2d":
         if not args.scan_dir:
@@ -246,7 +256,9 @@ def main(argv=None):
             synth.synthetic_scan3d_packets(PACKETS_PER_FRAME * (args.frames + 1))
         _, path, world = run_scan_to_map(stream, max_iter=args.max_iter, point_to_plane=args.point_to_plane or None,
                                          map_radius=args.map_radius, scan_voxel=args.scan_voxel,
-                                         map_voxel=args.map_voxel)
+                                         map_voxel=args.map_voxel,
+                                         scan_outliers=(int(args.scan_outliers[0]), float(args.scan_outliers[1]))
+                                         if args.scan_outliers else None)
         print(f"# map: {world.target_count} points")
     for k, (x, y) in enumerate(path):
         print(f"{k:4d} {x:+.9f} {y:+.9f}")

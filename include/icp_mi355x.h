@@ -1135,6 +1135,55 @@ int icp_voxel_downsample_device(int dim, const double *d_pts, size_t n, double v
 int icp_thin_targets(icp_handle *h, double voxel, uint32_t *new_index, size_t *removed);
 int icp_multi_thin_targets(icp_multi *M, double voxel, size_t *removed);
 
+/* ================================================================================
+ * 23. EXTENSION (not in the reference): exact k-nearest target lists and neighbourhood outlier removal
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  The cloud-hygiene step beside the voxel filter
+ * of section 22: dropping targets whose neighbourhood is too sparse (dust, rain, mixed pixels, ghost points), by the
+ * radius rule or by the statistical rule, and the lists both rest on.  The reference has no such thing: no parity claim;
+ * DESIGN.md section 9u restates the definitions, tests/test_outlier_abi.py restates them in numpy.
+ *
+ * Throughout, d2(i, j) = dx dx + dy dy (+ dz dz) with dx = p_i - p_j, a left fold without FMA, exactly as sections 7 and
+ * 14 form it; a d2 that overflows to +inf is a distance like any other.  All three calls need the handle's grid: a
+ * handle whose targets are not all finite has none and answers ICP_BAD_ARGUMENT (as icp_compute_target_normals).
+ *
+ * icp_target_neighbours (host out) / icp_target_neighbours_device (device out, enqueued on the handle's stream:
+ * icp_synchronize before reading).  Row i - first holds, for target i in [first, first + count), its min(k, m) nearest
+ * targets, ITSELF INCLUDED, ordered by (d2, index) ascending -- the tie rule of sections 7 and 14.  idx and d2 are
+ * count x k, row-major; either may be NULL.  With m < k the tail of a row is idx = 0xffffffff, d2 = +inf.
+ * 1 <= k <= 32.  Statuses: ICP_BAD_ARGUMENT (h NULL or k out of range: before any device use; first + count > m or no
+ * grid: from the handle's state), ICP_EMPTY_DST (m == 0), ICP_OK for count == 0, ICP_NO_DEVICE, ICP_HIP_ERROR,
+ * ICP_OUT_OF_MEMORY.  In numpy: order = lexsort((arange(m), d2[i])); idx = order[:k]; d2 = d2[i][order[:k]].
+ *
+ * icp_remove_radius_outliers.  Target i is KEPT iff  #{ j : d2(i, j) <= radius * radius } >= min_neighbours,  j over
+ * ALL targets, i included (so min_neighbours <= 1 keeps everything and min_neighbours > m removes everything);
+ * radius * radius is one f64 product.  radius >= 0 or +inf; a NaN or negative radius is ICP_BAD_ARGUMENT (with h NULL:
+ * before any device use).  In numpy: keep = (d2 <= r * r).sum(1) >= min_neighbours.
+ *
+ * icp_remove_statistical_outliers.  1 <= k <= 31; std_ratio any double but a NaN (both, and h NULL: ICP_BAD_ARGUMENT
+ * before any device use).  Every step is the definition of the bits:
+ *   ke = min(k, m - 1); with m <= 1 nothing is removed and stats are +0.0;
+ *   u_i = (sum of sqrt(d2) over the first ke entries, other than the one whose index is i, of target i's list of length
+ *         ke + 1) / (double)ke: a left fold from the nearest that starts from the first term, the correctly rounded
+ *         sqrt, a division (never a product with a reciprocal);
+ *   mean = fold(u) / (double)m;  deviation = sqrt(fold((u - mean)^2) / (double)(m - 1)), fold = the tree of section 9
+ *         (groups of 256, s = 128 ... 1, level after level);
+ *   threshold = mean + std_ratio * deviation: two roundings, no FMA;
+ *   target i is KEPT iff !(u_i > threshold): a NaN threshold (an infinite u; std_ratio = +-inf with deviation == 0)
+ *         keeps everything.
+ * stats (nullable) receives {mean, deviation, threshold}.
+ *
+ * After either filter everything section 11 says of a handle after a crop holds: order, bits, new_index (nullable, host,
+ * m_before words; 0xffffffff = removed), *removed (nullable), the results of a fresh icp_create on the kept cloud, normals
+ * carried over, the edges (nothing removed: the handle is untouched and keeps borrowing; everything removed) and the way
+ * back on failure.  The scratch (8 B per target, the tree's records, three scalars; the host list entry's staging rows)
+ * is kept per device between calls; icp_trim_pool releases it.  Results are pure functions of the input. */
+int icp_target_neighbours(icp_handle *h, int k, size_t first, size_t count, uint32_t *idx, double *d2);
+int icp_target_neighbours_device(icp_handle *h, int k, size_t first, size_t count, uint32_t *d_idx, double *d_d2);
+int icp_remove_radius_outliers(icp_handle *h, double radius, size_t min_neighbours, uint32_t *new_index, size_t *removed);
+int icp_remove_statistical_outliers(icp_handle *h, int k, double std_ratio, uint32_t *new_index, size_t *removed,
+                                    double stats[3]);
+
 #ifdef __cplusplus
 }
 #endif

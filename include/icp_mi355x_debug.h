@@ -72,6 +72,10 @@ int icp_grid_crop_counters(const icp_handle *h, uint64_t out[2]);
  * out[0] = thins served by moving the grid's sorted records, out[1] = thins that rebuilt the grid, under the same
  * conditions.  A thin that removes nothing counts in neither; a thin never moves the crop's counters. */
 int icp_grid_thin_counters(const icp_handle *h, uint64_t out[2]);
+/* ... and of icp_remove_radius_outliers / icp_remove_statistical_outliers (icp_mi355x.h section 23), which count
+ * together and for themselves: out[0] = filters served by moving the grid's sorted records, out[1] = filters that rebuilt
+ * the grid, under the same conditions.  A filter that removes nothing counts in neither. */
+int icp_grid_outlier_counters(const icp_handle *h, uint64_t out[2]);
 
 int icp_multi_counters(const icp_multi *M, uint64_t out[2]);
 
