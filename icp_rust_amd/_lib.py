@@ -237,6 +237,15 @@ SIGNATURES = {
     "icp_remove_radius_outliers": (C.c_int, [_vp, C.c_double, _sz, _vp, C.POINTER(_sz)]),
     "icp_remove_statistical_outliers": (C.c_int, [_vp, C.c_int, C.c_double, _vp, C.POINTER(_sz), _dp]),
     "icp_grid_outlier_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_query_neighbours": (C.c_int, [_vp, _vp, _sz, _pp, C.c_int, _vp, _vp]),
+    "icp_query_neighbours_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_int, _vp, _vp]),
+    "icp_count_within": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, C.c_uint32, _vp]),
+    "icp_count_within_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, C.c_uint32, _vp]),
+    "icp_remove_targets": (C.c_int, [_vp, _vp, _vp, C.POINTER(_sz)]),
+    "icp_remove_targets_device": (C.c_int, [_vp, _vp, _vp, C.POINTER(_sz)]),
+    "icp_grid_remove_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_query_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "icp_query_force_order": (C.c_int, [_vp, C.c_int]),
     "icp_evaluate_point_to_plane": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_evaluate_point_to_plane_device": (C.c_int, [_vp, _vp, _sz, _pp, C.c_double, _vp, _vp]),
     "icp_compute_target_line_normals": (C.c_int, [_vp, C.c_int]),

@@ -130,6 +130,15 @@ def _radius_rule(radius, min_neighbours):
     return r, int(min_neighbours)
 
 
+def _count_rule(radius, cap):
+    r, _ = _radius_rule(radius, 0)
+    if cap is None:
+        return r, 0xFFFFFFFF
+    if int(cap) != cap or not 1 <= int(cap) <= 0xFFFFFFFF:
+        raise ValueError(f"cap must be an integer in [1, 2^32 - 1] (or None: the full count), got {cap}")
+    return r, int(cap)
+
+
 def _statistical_rule(k, std_ratio):
     ratio = float(std_ratio)
     if ratio != ratio:
@@ -936,6 +945,112 @@ class _Icp:
         """(outlier filters served by moving the search grid's sorted records, filters that rebuilt the grid)"""
         out = (C.c_uint64 * 2)()
         check(lib().icp_grid_outlier_counters(self._h, out), "icp_grid_outlier_counters")
+        return int(out[0]), int(out[1])
+
+    # -- EXTENSION (not in the reference): queries of arbitrary points and removal by mask, icp_mi355x.h section 24 --
+    def _query_points(self, points, what="points"):
+        """(pointer, n, on_device, device) of a query cloud: a contiguous float64 CUDA tensor goes to the device
+        entries, anything else through numpy to the host entries"""
+        if _is_device_tensor(points):
+            self._dev(points, what)
+            return C.c_void_p(points.data_ptr() if points.shape[0] else None), points.shape[0], True, points.device, points
+        p = _host(points, self.DIM)
+        return _ptr(p), p.shape[0], False, None, p
+
+    def query(self, points, k, transform=None):
+        """(idx uint32, d2 float64), both (n, k): for each of the n `points`, moved by `transform` first if given
+        (Transform::transform on xy, z kept), its min(k, m) nearest targets by (d^2, index); rows padded with
+        0xffffffff / +inf; a point with a NaN coordinate gets padding only (icp_query_neighbours[_device]).  numpy in
+        gives numpy out; a contiguous float64 CUDA tensor gives CUDA tensors (idx as int32 bits)."""
+        k = _list_length(k, 32)
+        ptr, n, on_device, device, keep = self._query_points(points)
+        tp = C.byref(transform.pose) if transform is not None else None
+        if on_device:
+            import torch
+
+            idx = torch.empty((n, k), dtype=torch.int32, device=device)
+            d2 = torch.empty((n, k), dtype=torch.float64, device=device)
+            check(lib().icp_query_neighbours_device(self._h, ptr, n, tp, k, C.c_void_p(idx.data_ptr() if n else None),
+                                                    C.c_void_p(d2.data_ptr() if n else None)),
+                  "icp_query_neighbours_device")
+            if self._own_stream:
+                self.synchronize()  # (torch's streams are not ordered behind the handle's private one)
+            return idx, d2
+        idx = np.empty((n, k), dtype=np.uint32)
+        d2 = np.empty((n, k), dtype=np.float64)
+        check(lib().icp_query_neighbours(self._h, ptr, n, tp, k, _ptr(idx), _ptr(d2)), "icp_query_neighbours")
+        return idx, d2
+
+    def count_within(self, points, radius, transform=None, cap=None):
+        """uint32 (n,): for each of `points` (moved by `transform` first if given) the number of targets with d^2 <=
+        radius * radius, at most `cap` (None: the full count; a count stops at cap, which keeps a large radius cheap).
+        points=None: the targets themselves, in index order (then no transform); `count_within(None, r, cap=n) >= n`
+        is the keep rule of remove_radius_outliers(r, n) (icp_count_within[_device])."""
+        r, cp = _count_rule(radius, cap)
+        if points is None:
+            if transform is not None:
+                raise ValueError("count_within(None, ...) counts around the targets themselves: no transform")
+            n = self.target_count
+            counts = np.empty(n, dtype=np.uint32)
+            check(lib().icp_count_within(self._h, None, n, None, r, cp, _ptr(counts)), "icp_count_within")
+            return counts
+        ptr, n, on_device, device, keep = self._query_points(points)
+        tp = C.byref(transform.pose) if transform is not None else None
+        if n == 0 and not on_device:  # (no points have no address, and to the C entry no address means "the targets")
+            return np.empty(0, dtype=np.uint32)
+        if on_device:
+            import torch
+
+            counts = torch.empty(n, dtype=torch.int32, device=device)
+            if n == 0:
+                return counts
+            check(lib().icp_count_within_device(self._h, ptr, n, tp, r, cp, C.c_void_p(counts.data_ptr() if n else None)),
+                  "icp_count_within_device")
+            if self._own_stream:
+                self.synchronize()
+            return counts
+        counts = np.empty(n, dtype=np.uint32)
+        check(lib().icp_count_within(self._h, ptr, n, tp, r, cp, _ptr(counts)), "icp_count_within")
+        return counts
+
+    def remove(self, keep, return_index=False):
+        """Remove the targets i with keep[i] == 0 (`keep`: one value per target, anything numpy reads as a truth value,
+        or a CUDA bool / uint8 tensor; icp_remove_targets[_device]).  Like crop: order and normals are kept and the
+        handle then behaves like a fresh one on the kept cloud.  Returns the number removed; with return_index=True also
+        new_index (uint32, one per old target: its new index, 0xffffffff if removed)."""
+        if _is_device_tensor(keep):
+            if keep.dim() != 1 or keep.element_size() != 1 or keep.dtype.is_floating_point or not keep.is_contiguous():
+                raise ValueError(f"keep: expected a contiguous 1-D bool / uint8 CUDA tensor, got {tuple(keep.shape)} "
+                                 f"{keep.dtype}")
+            if self._device is not None and keep.device.index != self._device:
+                raise ValueError(f"keep: tensor lives on cuda:{keep.device.index}, the handle on cuda:{self._device}")
+            if keep.shape[0] != self.target_count:
+                raise ValueError(f"keep: expected {self.target_count} values, got {keep.shape[0]}")
+            self._after_producer(keep)
+            entry, arg = "icp_remove_targets_device", C.c_void_p(keep.data_ptr())
+        else:
+            mask = np.asarray(keep)
+            if mask.ndim != 1:
+                raise ValueError(f"keep: expected one value per target, got shape {mask.shape}")
+            mask = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+            if mask.shape[0] != self.target_count:
+                raise ValueError(f"keep: expected {self.target_count} values, got {mask.shape[0]}")
+            entry, arg = "icp_remove_targets", C.c_void_p(mask.ctypes.data)
+        if self.target_count == 0:  # (nothing to remove, and an empty mask has no address to hand over)
+            return (0, np.zeros(0, dtype=np.uint32)) if return_index else 0
+        removed, index = self._removal(entry, lambda ix, rm: getattr(lib(), entry)(self._h, arg, ix, rm), return_index)
+        return (removed, index) if return_index else removed
+
+    def remove_counters(self):
+        """(removals by mask served by moving the search grid's sorted records, removals that rebuilt the grid)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().icp_grid_remove_counters(self._h, out), "icp_grid_remove_counters")
+        return int(out[0]), int(out[1])
+
+    def query_counters(self):
+        """(query / count calls whose lanes ran in cell order, calls served in the caller's order)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().icp_query_counters(self._h, out), "icp_query_counters")
         return int(out[0]), int(out[1])
 
     def reserve(self, capacity):

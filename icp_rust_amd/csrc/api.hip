@@ -469,6 +469,9 @@ extern "C" void icp_destroy(icp_handle *h) {
     h->grid.crops_moved = h->grid.crops_rebuilt = 0;
     h->grid.thins_moved = h->grid.thins_rebuilt = 0;
     h->grid.filters_moved = h->grid.filters_rebuilt = 0;
+    h->grid.removes_moved = h->grid.removes_rebuilt = 0;
+    h->grid.queries_cell = h->grid.queries_caller = 0;
+    h->grid.query_force = 0;
     h->qsort.valid = false;
     h->qsort.have_prev = false;
     h->qsort.slot_order = false;
@@ -519,6 +522,7 @@ extern "C" void icp_trim_pool(void) {
   for (icp_handle *h : take) free_handle(h);
   voxel_trim();
   outlier_trim();
+  query_trim();
 }
 
 extern "C" int icp_set_nn_mode(icp_handle *h, int mode) {

@@ -130,6 +130,8 @@ int remove_marked_targets(icp_handle *h, uint32_t *w, uint32_t *cnt, unsigned lo
 void voxel_trim();
 // ... of icp_target_neighbours and the two outlier filters (outlier.hip)
 void outlier_trim();
+// ... of the query entries and icp_remove_targets (query.hip)
+void query_trim();
 
 }  // namespace api
 }  // namespace icp

@@ -342,6 +342,11 @@ struct Grid {
   unsigned long long crops_moved = 0, crops_rebuilt = 0;      // ... and of icp_crop_targets (icp_grid_crop_counters)
   unsigned long long thins_moved = 0, thins_rebuilt = 0;      // ... and of icp_thin_targets (icp_grid_thin_counters)
   unsigned long long filters_moved = 0, filters_rebuilt = 0;  // ... and of the outlier filters (icp_grid_outlier_counters)
+  unsigned long long removes_moved = 0, removes_rebuilt = 0;  // ... and of icp_remove_targets (icp_grid_remove_counters)
+  // query.hip: calls whose lanes ran in cell order / in the caller's order (icp_query_counters), and the order forced
+  // for a measurement (icp_query_force_order: 0 = the library's threshold)
+  unsigned long long queries_cell = 0, queries_caller = 0;
+  int query_force = 0;
   uint32_t *d_flag = nullptr;   // one word: a new point outside the grid's box (or not finite)
 };
 

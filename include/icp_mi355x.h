@@ -1184,6 +1184,68 @@ int icp_remove_radius_outliers(icp_handle *h, double radius, size_t min_neighbou
 int icp_remove_statistical_outliers(icp_handle *h, int k, double std_ratio, uint32_t *new_index, size_t *removed,
                                     double stats[3]);
 
+/* ================================================================================
+ * 24. EXTENSION (not in the reference): neighbour queries of arbitrary points, and target removal by the caller's mask
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  Section 23 answers only for points that are
+ * targets already, and removes only by its own two rules.  These calls answer for ANY points -- cloud-to-map distance,
+ * density, change detection, local fits around scan points -- and remove by a verdict the caller computed: query,
+ * decide, remove.  The reference has no such thing: no parity claim; DESIGN.md section 9v restates the definitions,
+ * tests/test_query_abi.py restates them in numpy.  Every step below is the definition of the bits.
+ *
+ * The query point.  q holds n points of dim coordinates each (AoS).  With pose == NULL the coordinates are used exactly
+ * as given.  Otherwise  px = (r00 x + r01 y) + tx,  py = (r10 x + r11 y) + ty,  z kept: Transform::transform as section 7
+ * forms it -- the two products, their sum, then + t, no FMA.  NULL is NOT a product with the identity: 0 * inf is NaN, so
+ * a point with an infinite coordinate differs between the two.
+ * The distance.  d2 = dx dx + dy dy (+ dz dz) with dx = p - t, a left fold without FMA, as sections 7, 14 and 23 form
+ * it.  A d2 that overflows to +inf is a distance like any other.  A NaN d2 (a NaN coordinate of p) is no neighbour.
+ * All four query calls need the handle's grid: a handle whose targets are not all finite has none and answers
+ * ICP_BAD_ARGUMENT (as section 23).
+ *
+ * icp_query_neighbours (host in, host out) / icp_query_neighbours_device (device in and out, enqueued on the handle's
+ * stream: icp_synchronize before reading).  Row i holds the min(k, m) nearest targets of query i by (d2, index)
+ * ascending; idx and d2 are n x k, row-major, padded with 0xffffffff / +inf; either may be NULL.  1 <= k <= 32.  A query
+ * with a NaN coordinate gets a row of padding only.  A query with an infinite coordinate (and no NaN) has d2 = +inf to
+ * every target and so gets the targets 0 .. min(k, m) - 1 with d2 = +inf.
+ * In numpy:  cand = flatnonzero(~isnan(d2[i]));  order = cand[lexsort((cand, d2[i][cand]))][:k].
+ *
+ * icp_count_within / icp_count_within_device.  counts[i] = min(cap, #{ j : d2(p_i, t_j) <= radius * radius });
+ * radius * radius is one f64 product; radius >= 0 or +inf, a NaN or negative radius is ICP_BAD_ARGUMENT; cap >= 1, and
+ * cap = 0xffffffff gives the full count (a count stops at cap: with a small cap a large radius stays cheap).  A NaN query
+ * counts 0; an infinite one counts min(cap, m) iff radius * radius is +inf, else 0 -- both by the arithmetic above.
+ * q == NULL: the queries are the handle's targets in index order; this takes pose == NULL and n == m (else
+ * ICP_BAD_ARGUMENT: for the pose before any device use, for n from the handle's state).  Then  counts[i] >= min_neighbours  with cap = min_neighbours is the keep rule of
+ * icp_remove_radius_outliers.
+ *
+ * Order of service.  Results are per query, so the order in which the device serves the queries changes no bit.  Calls
+ * with at least 250 000 points sort them by target-grid cell first (the sort of icp_sort_source_device), smaller ones go
+ * in the caller's order.  Such a call treats the handle's search snapshot as icp_sort_source_device does: the snapshot
+ * belongs to the call and is invalid afterwards, and icp_last_fold_order reports the identity until the next estimate
+ * call.  An estimate call after a query returns the bits it returns without the query.
+ *
+ * icp_remove_targets (keep: m bytes on the host) / icp_remove_targets_device (d_keep: m bytes on the handle's device,
+ * complete when the call is made).  Target i is kept iff keep[i] != 0.  Everything section 11 says of a handle after a
+ * crop holds: order, bits, new_index (nullable, host, m_before words; 0xffffffff = removed), *removed (nullable), the
+ * results of a fresh icp_create on the kept cloud, normals carried over, the edges (nothing removed: the handle is
+ * untouched and keeps borrowing; everything removed) and the way back on failure.  Like a crop it needs no grid.
+ * m == 0 is a successful no-op.  It counts in its own pair (icp_grid_remove_counters, icp_mi355x_debug.h).
+ *
+ * Statuses.  ICP_BAD_ARGUMENT before any device use: h NULL, k outside [1, 32], cap == 0, radius NaN or negative, q NULL
+ * with n > 0 (icp_query_neighbours*), q NULL with a pose (icp_count_within*), counts NULL with n > 0, n >= 2^32 - 1,
+ * keep NULL.  Then ICP_NO_DEVICE.  Then, from the handle's state, for the four query calls: ICP_EMPTY_DST (m == 0),
+ * ICP_BAD_ARGUMENT (no grid; q NULL with n != m).  Then ICP_OK for n == 0.  ICP_OUT_OF_MEMORY when the host entries' staging cannot be allocated,
+ * ICP_HIP_ERROR.  The staging (the points, the rows, the counts, the mask) is kept per device between calls; the calls
+ * of one process that use it take turns; icp_trim_pool releases it.  Results are pure functions of the input. */
+int icp_query_neighbours(icp_handle *h, const double *q, size_t n, const icp_pose *pose, int k, uint32_t *idx, double *d2);
+int icp_query_neighbours_device(icp_handle *h, const double *d_q, size_t n, const icp_pose *pose, int k, uint32_t *d_idx,
+                                double *d_d2);
+int icp_count_within(icp_handle *h, const double *q, size_t n, const icp_pose *pose, double radius, uint32_t cap,
+                     uint32_t *counts);
+int icp_count_within_device(icp_handle *h, const double *d_q, size_t n, const icp_pose *pose, double radius, uint32_t cap,
+                            uint32_t *d_counts);
+int icp_remove_targets(icp_handle *h, const uint8_t *keep, uint32_t *new_index, size_t *removed);
+int icp_remove_targets_device(icp_handle *h, const uint8_t *d_keep, uint32_t *new_index, size_t *removed);
+
 #ifdef __cplusplus
 }
 #endif

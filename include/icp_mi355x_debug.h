@@ -160,6 +160,17 @@ int icp_debug_plane_quality_batch_plan(unsigned m, uint32_t out[4]);
  * by their workgroup, or no LDS grant), out[2] batch launches, out[3] launches not made because the runtime refused the
  * kernels their LDS.  Section 8's counters (icp_batch_counters) do not move with these calls. */
 int icp_batch_gated_counters(icp_batch *b, uint64_t out[4]);
+/* icp_remove_targets[_device] (icp_mi355x.h section 24): out[0] removals served by moving the search grid's sorted
+ * records, out[1] removals that rebuilt the grid.  Its own pair: the crop's, the thin's and the outlier filters' pairs do
+ * not move with it. */
+int icp_grid_remove_counters(const icp_handle *h, uint64_t out[2]);
+/* icp_query_neighbours* / icp_count_within* (section 24): out[0] calls whose lanes ran in cell order (the per-call sort;
+ * for icp_count_within* without points, the targets' record order), out[1] calls served in the caller's order.  Calls
+ * that launch nothing (n == 0, no output asked for) count in neither. */
+int icp_query_counters(const icp_handle *h, uint64_t out[2]);
+/* For measurements of the two orders: mode 0 = the library's threshold, 1 = cell order for every call the handle's sort
+ * orders at all (more than 65 536 points), -1 = the caller's order.  Reset to 0 when the handle is destroyed. */
+int icp_query_force_order(icp_handle *h, int mode);
 
 /* Live kernel timing for the benchmark: with enable = k > 0, HIP events bracket every
  * k-th launch of the nearest-neighbour search kernel on the handle's stream (an event pair
