@@ -115,6 +115,68 @@ def voxel_downsample(points, voxel_size, return_index=False, device=-1):
     return (out, index[:kept.value].copy()) if return_index else out
 
 
+def voxel_centroids(points, voxel_size, return_counts=False, return_index=False, return_inverse=False, device=-1):
+    """EXTENSION (icp_voxel_centroids[_device], include/icp_mi355x.h section 25): the mean of the points of every
+    occupied voxel.  Membership is voxel_downsample's (the cell is floor(p / voxel_size) per axis in f64; a point with a
+    NaN or infinite coordinate is in no voxel); the voxels come in ascending order of their lowest member index, which
+    is the order of voxel_downsample's kept points; a sum is the fixed fold tree of section 9 over the members in
+    ascending index, then one division by the count: the same bytes from every call.  `points` is (n, 2) or (n, 3): a
+    numpy array (or anything numpy converts) gives numpy arrays; a contiguous float64 CUDA tensor gives CUDA tensors,
+    computed on torch's current stream.  Returns the means, then -- each only if asked for, in this order -- the
+    members per voxel (return_counts), every voxel's lowest member index (return_index: voxel_downsample's index) and
+    per point the number of its voxel, 0xffffffff for a dropped point (return_inverse); uint32 in numpy, int32 bits in
+    torch."""
+    v = _voxel_size(voxel_size)
+    voxels = C.c_size_t(0)
+    if _is_device_tensor(points):
+        import torch
+
+        if points.dim() != 2 or points.shape[1] not in (2, 3):
+            raise ValueError(f"points: expected (n, 2) or (n, 3), got {tuple(points.shape)}")
+        dim = points.shape[1]
+        _dev_points(points, dim, None if device < 0 else device)
+        n = points.shape[0]
+        means = torch.empty_like(points)
+
+        def words(wanted):
+            return torch.empty(max(n, 1), dtype=torch.int32, device=points.device) if wanted else None
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        counts, index, inverse = words(return_counts), words(return_index), words(return_inverse)
+        with torch.cuda.device(points.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().icp_voxel_centroids_device(dim, C.c_void_p(points.data_ptr()), n, v, ptr(means), ptr(counts),
+                                                   ptr(index), ptr(inverse), C.byref(voxels), points.device.index,
+                                                   C.c_void_p(stream)), "icp_voxel_centroids_device")
+        k = voxels.value
+        out = [means[:k]]
+        out += [counts[:k]] if return_counts else []
+        out += [index[:k]] if return_index else []
+        out += [inverse[:n]] if return_inverse else []
+        return tuple(out) if len(out) > 1 else out[0]
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] not in (2, 3):
+        raise ValueError(f"points: expected (n, 2) or (n, 3), got {p.shape}")
+    n, dim = p.shape
+    means = np.empty((max(n, 1), dim), dtype=np.float64)
+    counts, index, inverse = (np.zeros(max(n, 1), dtype=np.uint32) if wanted else None
+                              for wanted in (return_counts, return_index, return_inverse))
+
+    def ptr(a):
+        return C.c_void_p(a.ctypes.data) if a is not None else None
+
+    check(lib().icp_voxel_centroids(dim, _ptr(p), n, v, ptr(means), ptr(counts), ptr(index), ptr(inverse),
+                                    C.byref(voxels), int(device)), "icp_voxel_centroids")
+    k = voxels.value
+    out = [means[:k].copy()]
+    out += [counts[:k].copy()] if return_counts else []
+    out += [index[:k].copy()] if return_index else []
+    out += [inverse[:n].copy()] if return_inverse else []
+    return tuple(out) if len(out) > 1 else out[0]
+
+
 def _list_length(k, most, what="k"):
     if int(k) != k or not 1 <= int(k) <= most:
         raise ValueError(f"{what} must be an integer in [1, {most}], got {k}")

@@ -14,10 +14,13 @@
 //                                  of a voxel walks the same slots and ends on the same one, whatever the order they
 //                                  arrive in, and the word ends as the voxel's lowest index: a pure function of the
 //                                  input.  No thread waits for another: at most `slots` probes at a load of <= 0.5.
+//                                  Of the lanes of a wave that share the cell of its first inserting lane only that
+//                                  lane walks (it has the lowest index of them).
 //             k_voxel_mark<DIM>    walks the same slots read-only: kept iff the walk ends on a word that holds i;
 //                                  w[i] = kept ? 0 : kCropGone, cnt[tile] (compact_device.hpp)
 //             k_voxel_place<DIM>   the stand-alone call's compaction: kept points and / or their indices
 // No float reductions.  The hash only chooses where a walk starts: it has no part in the result.
+// The cell, the hash, the read-only walk and the workspace are voxel_device.hpp's: voxel_mean.hip (section 25) shares them.
 #include <cfloat>
 #include <cmath>
 #include <map>
@@ -26,59 +29,29 @@
 
 #include "api_internal.hpp"
 #include "compact_device.hpp"
+#include "voxel_device.hpp"
 
 using namespace icp;
 using namespace icp::api;
 
 namespace icp {
-namespace {
-
-constexpr uint32_t kVoxelEmpty = 0xffffffffu;
-constexpr unsigned kVoxelThreads = 256;
-
-// the cell of point i (2-D: the third coordinate is +0.0); false: a coordinate is NaN or infinite
-template <int DIM>
-__device__ __forceinline__ bool voxel_cell(const double *__restrict__ pts, size_t i, double v, double (&c)[3]) {
-  bool finite = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (a < DIM) {
-      const double p = pts[i * DIM + a];
-      finite = finite && fabs(p) <= DBL_MAX;  // (false for a NaN)
-      c[a] = floor(p / v) + 0.0;
-    } else {
-      c[a] = 0.0;
-    }
-  }
-  return finite;
-}
-
-__device__ __forceinline__ bool voxel_same(const double (&a)[3], const double (&b)[3]) {
-  return a[0] == b[0] && a[1] == b[1] && a[2] == b[2];
-}
-
-// where the walk of a cell starts: a 64-bit mix of the three bit patterns (canonical: no -0.0, no NaN)
-__device__ __forceinline__ unsigned long long voxel_hash(const double (&c)[3]) {
-  unsigned long long h = (unsigned long long)__double_as_longlong(c[0]) * 0x9e3779b97f4a7c15ull;
-  h ^= h >> 32;
-  h = (h ^ (unsigned long long)__double_as_longlong(c[1])) * 0xc2b2ae3d27d4eb4full;
-  h ^= h >> 29;
-  h = (h ^ (unsigned long long)__double_as_longlong(c[2])) * 0x165667b19e3779f9ull;
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  return h;
-}
-
-}  // namespace
 
 template <int DIM>
 __global__ __launch_bounds__(kVoxelThreads) void k_voxel_insert(const double *__restrict__ pts, size_t n, double v,
                                                                 uint32_t *__restrict__ tab, size_t mask) {
   const size_t i = (size_t)blockIdx.x * kVoxelThreads + threadIdx.x;
-  if (i >= n) return;
   double c[3], o[3];
-  if (!voxel_cell<DIM>(pts, i, v, c)) return;
+  const bool live = voxel_cell<DIM>(pts, i < n ? i : n - 1, v, c) && i < n;
+  // A lane whose cell is that of the wave's first inserting lane adds nothing: that lane holds a lower index of the same
+  // voxel (indices ascend with the lanes), and the word ends as the voxel's lowest index with or without this one.  A
+  // cloud crowded into one voxel then sends one lane per wave to the voxel's word, not sixty-four.
+  const unsigned long long all = __ballot(live);
+  if (all == 0ull) return;
+  const int lead = __ffsll((long long)all) - 1;
+  double c0[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) c0[a] = __shfl(c[a], lead, 64);
+  if (!live || ((int)(threadIdx.x & 63u) != lead && voxel_same(c, c0))) return;
   size_t s = (size_t)voxel_hash(c) & mask;
   for (size_t probe = 0; probe <= mask; ++probe) {
     const uint32_t cur = atomicCAS(&tab[s], kVoxelEmpty, (uint32_t)i);
@@ -90,23 +63,6 @@ __global__ __launch_bounds__(kVoxelThreads) void k_voxel_insert(const double *__
     }
     s = (s + 1) & mask;
   }
-}
-
-// is point i (finite, cell c) the word of its voxel's slot
-template <int DIM>
-__device__ __forceinline__ bool voxel_owns(const double *__restrict__ pts, size_t n, double v,
-                                           const uint32_t *__restrict__ tab, size_t mask, size_t i, const double (&c)[3]) {
-  double o[3];
-  size_t s = (size_t)voxel_hash(c) & mask;
-  for (size_t probe = 0; probe <= mask; ++probe) {
-    const uint32_t cur = tab[s];
-    if (cur == (uint32_t)i) return true;
-    if (cur >= n) return false;  // (an empty slot on the walk of an inserted point: cannot be)
-    (void)voxel_cell<DIM>(pts, cur, v, o);
-    if (voxel_same(c, o)) return false;  // its voxel's slot, and a lower index has it
-    s = (s + 1) & mask;
-  }
-  return false;
 }
 
 template <int DIM>
@@ -123,7 +79,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_voxel_mark(const double *__
     in[k] = false;
     if (i < n) {
       double c[3];
-      in[k] = voxel_cell<DIM>(pts, i, v, c) && voxel_owns<DIM>(pts, n, v, tab, mask, i, c);
+      in[k] = voxel_cell<DIM>(pts, i, v, c) && voxel_leader<DIM>(pts, n, v, tab, mask, i, c) == (uint32_t)i;
       w[i] = in[k] ? 0u : kCropGone;
     }
   }
@@ -164,21 +120,16 @@ __global__ __launch_bounds__(kCompactThreads) void k_voxel_place(const double *_
 }
 
 namespace {
-
-// What the calls keep between them, per device: the table, the marks, the tile counts and chunk sums, and the host
-// entry's staging buffers.  One call at a time (g_mu is held for the length of a call).
-struct VoxelWs {
-  uint32_t *tab = nullptr, *w = nullptr, *cnt = nullptr, *idx = nullptr;
-  double *in = nullptr, *out = nullptr;
-  size_t cap_tab = 0, cap_w = 0, cap_cnt = 0, cap_idx = 0, cap_in = 0, cap_out = 0;
-  hipStream_t stream = nullptr;  // the host entry's
-};
 std::mutex g_mu;
 std::map<int, VoxelWs> g_ws;
+}  // namespace
+
+std::mutex &voxel_mutex() { return g_mu; }
+VoxelWs &voxel_ws(int device) { return g_ws[device]; }
 
 bool voxel_size_ok(double v) { return v >= DBL_MIN && v <= DBL_MAX; }  // (false for a NaN)
 
-size_t voxel_slots(size_t n) {
+static size_t voxel_slots(size_t n) {
   size_t slots = 2;
   while (slots < 2 * n) slots <<= 1;
   return slots;
@@ -213,6 +164,8 @@ hipError_t launch_voxel_marks(int dim, const double *d_pts, size_t n, double v, 
   return hipGetLastError();
 }
 
+namespace {
+
 // the stand-alone call on device buffers (g_mu held, the device current): everything on `s`, which is waited for
 int voxel_downsample_on(VoxelWs &W, int dim, const double *d_pts, size_t n, double v, double *d_out,
                         uint32_t *d_kept_index, size_t *kept, hipStream_t s) {
@@ -242,6 +195,8 @@ int voxel_downsample_on(VoxelWs &W, int dim, const double *d_pts, size_t n, doub
   return ICP_OK;
 }
 
+}  // namespace
+
 bool voxel_args_ok(int dim, const void *pts, size_t n, double v, const size_t *kept) {
   return (dim == 2 || dim == 3) && kept && (n == 0 || pts) && voxel_size_ok(v) && n <= 0xfffffffeull;
 }
@@ -255,13 +210,13 @@ int voxel_device(int *device) {
   return ICP_OK;
 }
 
-}  // namespace
-
 void api::voxel_trim() {
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto &kv : g_ws) {
     VoxelWs &W = kv.second;
-    for (void *p : {(void *)W.tab, (void *)W.w, (void *)W.cnt, (void *)W.idx, (void *)W.in, (void *)W.out})
+    for (void *p : {(void *)W.tab, (void *)W.w, (void *)W.cnt, (void *)W.idx, (void *)W.in, (void *)W.out, (void *)W.key,
+                    (void *)W.perm, (void *)W.start, (void *)W.ctr, (void *)W.count, (void *)W.of, (void *)W.items,
+                    (void *)W.bigs, (void *)W.rec, W.sort_tmp})
       if (p) (void)hipFree(p);
     if (W.stream) (void)hipStreamDestroy(W.stream);
   }

@@ -1,0 +1,103 @@
+// What voxel thinning (voxel.hip, include/icp_mi355x.h section 22) and voxel centroids (voxel_mean.hip, section 25)
+// share: the cell of a point, the equality of cells, the hash that starts a walk, the read-only walk of the table to a
+// voxel's lowest index, and -- host side -- the per-device workspace with the launches that fill the table and the
+// marks.  One copy of the rule: both features decide membership with exactly these functions.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
+
+namespace icp {
+
+constexpr uint32_t kVoxelEmpty = 0xffffffffu;
+constexpr unsigned kVoxelThreads = 256;
+
+// the cell of point i (2-D: the third coordinate is +0.0); false: a coordinate is NaN or infinite
+template <int DIM>
+__device__ __forceinline__ bool voxel_cell(const double *__restrict__ pts, size_t i, double v, double (&c)[3]) {
+  bool finite = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (a < DIM) {
+      const double p = pts[i * DIM + a];
+      finite = finite && fabs(p) <= DBL_MAX;  // (false for a NaN)
+      c[a] = floor(p / v) + 0.0;
+    } else {
+      c[a] = 0.0;
+    }
+  }
+  return finite;
+}
+
+__device__ __forceinline__ bool voxel_same(const double (&a)[3], const double (&b)[3]) {
+  return a[0] == b[0] && a[1] == b[1] && a[2] == b[2];
+}
+
+// where the walk of a cell starts: a 64-bit mix of the three bit patterns (canonical: no -0.0, no NaN)
+__device__ __forceinline__ unsigned long long voxel_hash(const double (&c)[3]) {
+  unsigned long long h = (unsigned long long)__double_as_longlong(c[0]) * 0x9e3779b97f4a7c15ull;
+  h ^= h >> 32;
+  h = (h ^ (unsigned long long)__double_as_longlong(c[1])) * 0xc2b2ae3d27d4eb4full;
+  h ^= h >> 29;
+  h = (h ^ (unsigned long long)__double_as_longlong(c[2])) * 0x165667b19e3779f9ull;
+  h ^= h >> 33;
+  h *= 0xff51afd7ed558ccdull;
+  h ^= h >> 33;
+  return h;
+}
+
+// The walk of the finished table, read-only: the word of the slot that the voxel of point i (finite, cell c) owns, which
+// is the voxel's lowest index.  kVoxelEmpty: the walk met an empty slot (cannot be for an inserted point).
+template <int DIM>
+__device__ __forceinline__ uint32_t voxel_leader(const double *__restrict__ pts, size_t n, double v,
+                                                 const uint32_t *__restrict__ tab, size_t mask, size_t i,
+                                                 const double (&c)[3]) {
+  double o[3];
+  size_t s = (size_t)voxel_hash(c) & mask;
+  for (size_t probe = 0; probe <= mask; ++probe) {
+    const uint32_t cur = tab[s];
+    if (cur == (uint32_t)i) return cur;
+    if (cur >= n) return kVoxelEmpty;
+    (void)voxel_cell<DIM>(pts, cur, v, o);
+    if (voxel_same(c, o)) return cur;  // its voxel's slot, and a lower index has it
+    s = (s + 1) & mask;
+  }
+  return kVoxelEmpty;
+}
+
+// ---- host side (voxel.hip defines them) ----
+// What the calls keep between them, per device: the table, the marks, the tile counts and chunk sums, the host entries'
+// staging buffers, and what the centroids add (sort keys and order, segment starts, work lists, the sort's temporary).
+// One call at a time (voxel_mutex() is held for the length of a call).
+struct VoxelWs {
+  uint32_t *tab = nullptr, *w = nullptr, *cnt = nullptr, *idx = nullptr;
+  double *in = nullptr, *out = nullptr;
+  size_t cap_tab = 0, cap_w = 0, cap_cnt = 0, cap_idx = 0, cap_in = 0, cap_out = 0;
+  // voxel_mean.hip
+  uint32_t *key = nullptr, *perm = nullptr, *start = nullptr, *ctr = nullptr, *count = nullptr, *of = nullptr;
+  uint4 *items = nullptr, *bigs = nullptr;
+  double *rec = nullptr;
+  void *sort_tmp = nullptr;
+  size_t cap_key = 0, cap_perm = 0, cap_start = 0, cap_ctr = 0, cap_count = 0, cap_of = 0, cap_items = 0, cap_bigs = 0,
+         cap_rec = 0, cap_sort = 0;
+  hipStream_t stream = nullptr;  // the host entries'
+};
+std::mutex &voxel_mutex();
+VoxelWs &voxel_ws(int device);  // (voxel_mutex() held)
+bool voxel_size_ok(double v);
+// the arguments every stand-alone entry checks before the device is touched
+bool voxel_args_ok(int dim, const void *pts, size_t n, double v, const size_t *out_count);
+// ICP_NO_DEVICE without one; -1 -> the current device; makes *device current
+int voxel_device(int *device);
+// the table for n points, preset on `s` (a table grows to the next power of two: geometric by construction)
+hipError_t voxel_table(VoxelWs &W, size_t n, hipStream_t s, size_t *mask);
+// the insert and the mark launch on `s`: w[i] (0 = its voxel's lowest index, kCropGone otherwise) and cnt[tile] for the
+// n > 0 points of d_pts
+hipError_t launch_voxel_marks(int dim, const double *d_pts, size_t n, double v, uint32_t *tab, size_t mask, uint32_t *w,
+                              uint32_t *cnt, hipStream_t s);
+
+}  // namespace icp

@@ -1246,6 +1246,56 @@ int icp_count_within_device(icp_handle *h, const double *d_q, size_t n, const ic
 int icp_remove_targets(icp_handle *h, const uint8_t *keep, uint32_t *new_index, size_t *removed);
 int icp_remove_targets_device(icp_handle *h, const uint8_t *d_keep, uint32_t *new_index, size_t *removed);
 
+/* ================================================================================
+ * 25. EXTENSION (not in the reference): voxel centroids -- per voxel the mean, the count and the point-to-voxel map
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  The voxel-grid filter as lidar pipelines know
+ * it: one point per occupied voxel, the MEAN of the voxel's points, with the number of members as a weight.  Section 22
+ * keeps one sample of every voxel; the mean is the lower-noise source cloud of a registration, the counts serve a
+ * weighted consumer or an occupancy threshold.  The reference has no such thing: no parity claim; DESIGN.md section 9w
+ * restates the definition, tests/test_voxel_mean_abi.py restates it in numpy (centroids_of).
+ *
+ * The rule.  For n points of dim coordinates and a voxel size v, every step is the definition of the bits:
+ *   membership is section 22's, exactly: the cell is floor(p_a / v) + 0.0 per axis in f64 with ONE division; two points
+ *   share a voxel iff their cells are equal as doubles; a point with a NaN or infinite coordinate is in no voxel;
+ *   the occupied voxels are numbered in ascending order of their LOWEST member index -- the order of
+ *   icp_voxel_downsample's kept points, so first_index here equals kept_index there, element for element;
+ *   for voxel r with the members i_0 < i_1 < ... < i_(c-1):
+ *     count[r] = c;
+ *     per axis a,  sum = fold(x[i_0, a], ..., x[i_(c-1), a]),  fold = the tree of section 9 verbatim: c == 1 -> the value
+ *     itself; otherwise, while more than one value is left: pad with +0.0 to a multiple of 256, g[i] += g[i + s] for
+ *     s = 128, 64, ..., 1 inside every group of 256, keep every group's g[0];
+ *     mean[r, a] = sum / (double)c: one IEEE division, no FMA, never a product with a reciprocal;
+ *   voxel_of[i] = the number r of point i's voxel, 0xffffffff for a point in no voxel (the "gone" of the new_index tables).
+ * What follows from it:
+ *   a voxel of one member returns that point's bytes: a -0.0 stays -0.0;
+ *   a voxel of c >= 2 members that are all -0.0 on an axis gives +0.0 there (the padding: -0.0 + +0.0 = +0.0);
+ *   a sum that overflows gives +-inf, and the mean with it.  The members of a voxel share their sign on every axis (the
+ *   cell 0 holds [0, v) and -0.0, the cells below only negative values), so inf - inf does not arise and no mean is a NaN;
+ *   the result is a pure function of the input: the same bytes from every call, every stream, every device.
+ * In numpy (kept_index_of: section 22's restatement):
+ *   first = kept_index_of(p, v);  voxel_of = rank of each finite point's cell in the order of first;
+ *   mean[r] = [fold(p[voxel_of == r, a]) for a] / count[r].
+ *
+ * icp_voxel_centroids (host arrays) and icp_voxel_centroids_device (device arrays; everything is enqueued on hip_stream,
+ * NULL: the default stream, and the entry returns after the one wait that delivers *voxels): dim is 2 or 3; pts holds n
+ * points and is never written.  mean (room for n points), count, first_index (room for n words each) and voxel_of (n
+ * words) are each nullable, and what is not asked for is not computed; none may overlap pts.  *voxels (required) receives
+ * the number of occupied voxels: the first *voxels entries of mean, count and first_index are the result.  n == 0 gives
+ * *voxels = 0 and ICP_OK.  device: -1 = the current one.  Statuses: ICP_BAD_ARGUMENT (dim, v as in section 22, voxels
+ * NULL, pts NULL with n > 0, n > 2^32 - 2, n > 2^27 when mean or count is asked for -- the limit of the sort underneath --,
+ * device < -1: all decided before the device is touched, and a refused call writes nothing; a device number past the
+ * last one), ICP_NO_DEVICE, ICP_HIP_ERROR, ICP_OUT_OF_MEMORY.  The workspace is section 22's, grown by the sort keys,
+ * the sorted order, the segment starts (4 B per point each), the sort's temporary (about 16 B per point) and the lists of
+ * the voxels above 256 members; icp_trim_pool releases all of it.  The calls of one process take turns with section 22's.
+ * A voxel of any size is folded by as many workgroups as it has blocks of 65 536 members, and of the points of a wave
+ * that share a cell only one goes to the table: a v far too large -- the whole cloud in one voxel -- stays within a small
+ * factor of a well-chosen one (DESIGN.md section 9w has the measured row). */
+int icp_voxel_centroids(int dim, const double *pts, size_t n, double voxel, double *mean, uint32_t *count,
+                        uint32_t *first_index, uint32_t *voxel_of, size_t *voxels, int device);
+int icp_voxel_centroids_device(int dim, const double *d_pts, size_t n, double voxel, double *d_mean, uint32_t *d_count,
+                               uint32_t *d_first_index, uint32_t *d_voxel_of, size_t *voxels, int device, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
