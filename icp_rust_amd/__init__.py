@@ -8,7 +8,7 @@ from . import _lib
 from ._lib import IcpError, Pose, build, lib  # noqa: F401
 from .api import (Icp2d, Icp3d, IcpBatch, IcpMulti, LineQuality, PlaneQuality, Quality, Transform, error, estimate_transform, gauss_newton_update,  # noqa: F401
                   huber_error, gn_path_counters, gn_filed_counters, gn_loop_counters, gn_loop_timeouts, fixed_point_skips, run_ahead_counters, nn_cert_counters, norm, reduce_geometry, residual, residual_stddevs, se2, so2,
-                  remove_radius_outliers, remove_statistical_outliers, voxel_centroids, voxel_downsample,
+                  remove_radius_outliers, remove_statistical_outliers, voxel_centroids, voxel_covariances, voxel_downsample,
                   weighted_gauss_newton_update)
 
 HUBER_K = 1.345

@@ -232,6 +232,10 @@ SIGNATURES = {
     "icp_voxel_centroids": (C.c_int, [C.c_int, _vp, _sz, C.c_double, _vp, _vp, _vp, _vp, C.POINTER(_sz), C.c_int]),
     "icp_voxel_centroids_device": (C.c_int, [C.c_int, _vp, _sz, C.c_double, _vp, _vp, _vp, _vp, C.POINTER(_sz), C.c_int,
                                              _vp]),
+    "icp_voxel_covariances": (C.c_int, [C.c_int, _vp, _sz, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, C.POINTER(_sz),
+                                        C.c_int]),
+    "icp_voxel_covariances_device": (C.c_int, [C.c_int, _vp, _sz, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                               C.POINTER(_sz), C.c_int, _vp]),
     "icp_thin_targets": (C.c_int, [_vp, C.c_double, _vp, C.POINTER(_sz)]),
     "icp_multi_thin_targets": (C.c_int, [_vp, C.c_double, C.POINTER(_sz)]),
     "icp_grid_thin_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),

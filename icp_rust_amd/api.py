@@ -177,6 +177,89 @@ def voxel_centroids(points, voxel_size, return_counts=False, return_index=False,
     return tuple(out) if len(out) > 1 else out[0]
 
 
+def _mirrored(packed, dim, xp):
+    """(V, dim (dim + 1) / 2) packed second moments (xx, xy, yy / xx, xy, xz, yy, yz, zz) -> (V, dim, dim) symmetric: a
+    pure copy of the packed values (xp: numpy or torch)"""
+    pairs = [(a, b) for a in range(dim) for b in range(a, dim)]
+    at = {ab: k for k, ab in enumerate(pairs)}
+    order = [at[(min(a, b), max(a, b))] for a in range(dim) for b in range(dim)]
+    if xp is np:
+        return np.ascontiguousarray(packed[:, order]).reshape(-1, dim, dim)
+    return packed[:, order].reshape(-1, dim, dim).contiguous()
+
+
+def voxel_covariances(points, voxel_size, ddof=1, return_means=True, return_counts=False, return_index=False,
+                      return_inverse=False, packed=False, device=-1):
+    """EXTENSION (icp_voxel_covariances[_device], include/icp_mi355x.h section 26): the covariance of the points of
+    every occupied voxel about the voxel's mean.  Membership, the order of the voxels and the means are
+    voxel_centroids' (section 25), bit for bit; a second moment is the fixed fold tree of section 9 over the products
+    (x_a - m_a) (x_b - m_b) of the members in ascending index, then one division by count - ddof (ddof 0 or 1; a voxel
+    with count <= ddof gets +0.0): the same bytes from every call.  `points` is (n, 2) or (n, 3): a numpy array (or
+    anything numpy converts) gives numpy arrays; a contiguous float64 CUDA tensor gives CUDA tensors, computed on torch's
+    current stream.  Returns the covariances, (V, dim, dim) symmetric -- the mirroring is a copy -- or, with packed=True,
+    (V, dim (dim + 1) / 2) in the order xx, xy, yy / xx, xy, xz, yy, yz, zz; then -- each only if asked for, in this
+    order -- the means (return_means, on by default), the members per voxel (return_counts), every voxel's lowest member
+    index (return_index) and per point the number of its voxel, 0xffffffff for a dropped point (return_inverse); uint32
+    in numpy, int32 bits in torch."""
+    v = _voxel_size(voxel_size)
+    if ddof not in (0, 1) or isinstance(ddof, bool):
+        raise ValueError(f"ddof must be 0 or 1, got {ddof!r}")
+    ddof = int(ddof)
+    voxels = C.c_size_t(0)
+    if _is_device_tensor(points):
+        import torch
+
+        if points.dim() != 2 or points.shape[1] not in (2, 3):
+            raise ValueError(f"points: expected (n, 2) or (n, 3), got {tuple(points.shape)}")
+        dim = points.shape[1]
+        _dev_points(points, dim, None if device < 0 else device)
+        n, ns = points.shape[0], dim * (dim + 1) // 2
+        cov = torch.empty((max(n, 1), ns), dtype=torch.float64, device=points.device)
+        means = torch.empty_like(points) if return_means else None
+
+        def words(wanted):
+            return torch.empty(max(n, 1), dtype=torch.int32, device=points.device) if wanted else None
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        counts, index, inverse = words(return_counts), words(return_index), words(return_inverse)
+        with torch.cuda.device(points.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().icp_voxel_covariances_device(dim, C.c_void_p(points.data_ptr()), n, v, ddof, ptr(cov), ptr(means),
+                                                     ptr(counts), ptr(index), ptr(inverse), C.byref(voxels),
+                                                     points.device.index, C.c_void_p(stream)),
+                  "icp_voxel_covariances_device")
+            k = voxels.value
+            out = [cov[:k] if packed else _mirrored(cov[:k], dim, torch)]
+        out += [means[:k]] if return_means else []
+        out += [counts[:k]] if return_counts else []
+        out += [index[:k]] if return_index else []
+        out += [inverse[:n]] if return_inverse else []
+        return tuple(out) if len(out) > 1 else out[0]
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] not in (2, 3):
+        raise ValueError(f"points: expected (n, 2) or (n, 3), got {p.shape}")
+    n, dim = p.shape
+    cov = np.empty((max(n, 1), dim * (dim + 1) // 2), dtype=np.float64)
+    means = np.empty((max(n, 1), dim), dtype=np.float64) if return_means else None
+    counts, index, inverse = (np.zeros(max(n, 1), dtype=np.uint32) if wanted else None
+                              for wanted in (return_counts, return_index, return_inverse))
+
+    def ptr(a):
+        return C.c_void_p(a.ctypes.data) if a is not None else None
+
+    check(lib().icp_voxel_covariances(dim, _ptr(p), n, v, ddof, ptr(cov), ptr(means), ptr(counts), ptr(index),
+                                      ptr(inverse), C.byref(voxels), int(device)), "icp_voxel_covariances")
+    k = voxels.value
+    out = [cov[:k].copy() if packed else _mirrored(cov[:k], dim, np)]
+    out += [means[:k].copy()] if return_means else []
+    out += [counts[:k].copy()] if return_counts else []
+    out += [index[:k].copy()] if return_index else []
+    out += [inverse[:n].copy()] if return_inverse else []
+    return tuple(out) if len(out) > 1 else out[0]
+
+
 def _list_length(k, most, what="k"):
     if int(k) != k or not 1 <= int(k) <= most:
         raise ValueError(f"{what} must be an integer in [1, {most}], got {k}")

@@ -214,8 +214,8 @@ void api::voxel_trim() {
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto &kv : g_ws) {
     VoxelWs &W = kv.second;
-    for (void *p : {(void *)W.tab, (void *)W.w, (void *)W.cnt, (void *)W.idx, (void *)W.in, (void *)W.out, (void *)W.key,
-                    (void *)W.perm, (void *)W.start, (void *)W.ctr, (void *)W.count, (void *)W.of, (void *)W.items,
+    for (void *p : {(void *)W.tab, (void *)W.w, (void *)W.cnt, (void *)W.idx, (void *)W.in, (void *)W.out, (void *)W.cov,
+                    (void *)W.key, (void *)W.perm, (void *)W.start, (void *)W.ctr, (void *)W.count, (void *)W.of, (void *)W.items,
                     (void *)W.bigs, (void *)W.rec, W.sort_tmp})
       if (p) (void)hipFree(p);
     if (W.stream) (void)hipStreamDestroy(W.stream);

@@ -1,5 +1,5 @@
-// What voxel thinning (voxel.hip, include/icp_mi355x.h section 22) and voxel centroids (voxel_mean.hip, section 25)
-// share: the cell of a point, the equality of cells, the hash that starts a walk, the read-only walk of the table to a
+// What voxel thinning (voxel.hip, include/icp_mi355x.h section 22), voxel centroids (voxel_mean.hip, section 25) and
+// voxel covariances (voxel_cov.hip, section 26) share: the cell of a point, the equality of cells, the hash that starts a walk, the read-only walk of the table to a
 // voxel's lowest index, and -- host side -- the per-device workspace with the launches that fill the table and the
 // marks.  One copy of the rule: both features decide membership with exactly these functions.
 #pragma once
@@ -75,8 +75,8 @@ __device__ __forceinline__ uint32_t voxel_leader(const double *__restrict__ pts,
 // One call at a time (voxel_mutex() is held for the length of a call).
 struct VoxelWs {
   uint32_t *tab = nullptr, *w = nullptr, *cnt = nullptr, *idx = nullptr;
-  double *in = nullptr, *out = nullptr;
-  size_t cap_tab = 0, cap_w = 0, cap_cnt = 0, cap_idx = 0, cap_in = 0, cap_out = 0;
+  double *in = nullptr, *out = nullptr, *cov = nullptr;  // (cov: voxel_cov.hip's host entry)
+  size_t cap_tab = 0, cap_w = 0, cap_cnt = 0, cap_idx = 0, cap_in = 0, cap_out = 0, cap_cov = 0;
   // voxel_mean.hip
   uint32_t *key = nullptr, *perm = nullptr, *start = nullptr, *ctr = nullptr, *count = nullptr, *of = nullptr;
   uint4 *items = nullptr, *bigs = nullptr;
@@ -99,5 +99,22 @@ hipError_t voxel_table(VoxelWs &W, size_t n, hipStream_t s, size_t *mask);
 // n > 0 points of d_pts
 hipError_t launch_voxel_marks(int dim, const double *d_pts, size_t n, double v, uint32_t *tab, size_t mask, uint32_t *w,
                               uint32_t *cnt, hipStream_t s);
+
+// ---- the members of a voxel (voxel_mean.hip defines them; voxel_cov.hip runs the same chain) ----
+constexpr size_t kVmMaxPoints = (size_t)1 << 27;  // what the sort of the members takes
+// The call on device buffers (voxel_mutex() held, the device current): everything on `s`, which is waited for once.
+// Every output is nullable.  d_cov == nullptr: the centroids.  Otherwise (d_mean required, ddof 0 or 1) the sorted members
+// are folded by launch_covariance_chain, the second moments beside the means.
+int voxel_centroids_on(VoxelWs &W, int dim, const double *d_pts, size_t n, double v, double *d_mean, uint32_t *d_count,
+                       uint32_t *d_first_index, uint32_t *d_voxel_of, size_t *voxels, hipStream_t s, double *d_cov,
+                       int ddof);
+// start[] and the number of voxels from the sorted keys
+hipError_t launch_vm_starts(VoxelWs &W, size_t n, hipStream_t s);
+// the means of the voxels above 256 members, from the work lists a folding launch left in W
+hipError_t launch_vm_large_means(VoxelWs &W, int dim, const double *d_pts, size_t n, double *d_mean, hipStream_t s);
+// voxel_cov.hip: behind the sort, on `s` -- start[], the means and second moments of the voxels up to 256 members, the
+// means of the larger ones, then their second moments over the same work lists
+hipError_t launch_covariance_chain(VoxelWs &W, int dim, const double *d_pts, size_t n, int ddof, double *d_cov,
+                                   double *d_mean, uint32_t *d_count, hipStream_t s);
 
 }  // namespace icp

@@ -1296,6 +1296,50 @@ int icp_voxel_centroids(int dim, const double *pts, size_t n, double voxel, doub
 int icp_voxel_centroids_device(int dim, const double *d_pts, size_t n, double voxel, double *d_mean, uint32_t *d_count,
                                uint32_t *d_first_index, uint32_t *d_voxel_of, size_t *voxels, int device, void *hip_stream);
 
+/* ================================================================================
+ * 26. EXTENSION (not in the reference): voxel covariances -- per voxel the mean, the count and the second moments
+ * ==============================================================================
+ * An addition to ABI 8, detectable by symbol (ICP_ABI_VERSION stays 8).  The other half of the voxel statistic of lidar
+ * pipelines: mean and covariance per voxel are what an NDT map, a voxelised GICP, a surfel map or a planarity filter is
+ * built from.  The reference has no such thing: no parity claim; DESIGN.md section 9x restates the definition,
+ * tests/test_voxel_cov_abi.py restates it in numpy (covariances_of).
+ *
+ * The rule.  Membership, the numbering of the voxels, count, first_index, voxel_of and mean are section 25's, bit for
+ * bit.  For voxel r with the members i_0 < ... < i_(c-1) and the mean m (section 25's bits), over the axis pairs (a, b),
+ * a <= b, in the order xx, xy, yy (dim 2) and xx, xy, xz, yy, yz, zz (dim 3):
+ *   d_j[a]  = x[i_j, a] - m[a]                    one f64 subtraction;
+ *   p_j[ab] = d_j[a] * d_j[b]                     one f64 multiplication, never fused with the addition behind it;
+ *   S[ab]   = fold(p_0[ab], ..., p_(c-1)[ab])     the tree of section 9 as section 25 states it: c == 1 -> the value;
+ *             otherwise pad with +0.0 to groups of 256, g[i] += g[i + s] for s = 128 ... 1, level after level;
+ *   cov[r, ab] = S[ab] / (double)(c - ddof)       one IEEE division; ddof is 0 (the population's) or 1 (the sample's).
+ *             A voxel with c <= ddof gets +0.0 in every entry.
+ * The two passes (the mean first, the products of the deviations second) are what keeps a cloud far from the origin
+ * accurate: the one-pass E[xx] - mm loses every digit once the offset squared outgrows 2^53 variances.
+ * What follows from it:
+ *   a voxel of one member gives +0.0 in every entry, for either ddof;
+ *   a diagonal entry is a sum of squares: never negative, never a NaN for a finite mean;
+ *   an off-diagonal entry is a NaN only where products overflow to infinities of both signs (host and device differ in
+ *   the sign bit of that NaN: compare such positions as "is a NaN", everything else by bytes);
+ *   a mean that overflowed to +-inf on an axis gives infinite deviations there (an entry is then +-inf, or a NaN where the
+ *   other axis' deviation is zero or the infinities' signs are mixed);
+ *   the result is a pure function of the input: the same bytes from every call, every stream, every device.
+ *
+ * icp_voxel_covariances (host arrays) and icp_voxel_covariances_device (device arrays; everything is enqueued on
+ * hip_stream, NULL: the default stream, and the entry returns after the one wait that delivers *voxels): as section 25's
+ * entries, with cov (REQUIRED: room for n * dim (dim + 1) / 2 doubles, the packed order above, voxel after voxel) and
+ * ddof in front of section 25's outputs.  mean, count, first_index and voxel_of are each nullable; a mean that is not
+ * asked for is computed into the workspace.  The first *voxels rows of cov, mean, count and first_index are the result.
+ * n == 0 gives *voxels = 0 and ICP_OK.  Statuses: ICP_BAD_ARGUMENT (section 25's refusals, ddof not 0 or 1, cov NULL,
+ * and n > 2^27 always, since cov needs the sort: all decided before the device is touched, and a refused call writes
+ * nothing; a device number past the last one), ICP_NO_DEVICE, ICP_HIP_ERROR, ICP_OUT_OF_MEMORY.  The workspace is
+ * section 25's, with six sums per record of a voxel above 65 536 members and the host entry's staging of cov;
+ * icp_trim_pool releases it.  The calls of one process take turns with sections 22's and 25's. */
+int icp_voxel_covariances(int dim, const double *pts, size_t n, double voxel, int ddof, double *cov, double *mean,
+                          uint32_t *count, uint32_t *first_index, uint32_t *voxel_of, size_t *voxels, int device);
+int icp_voxel_covariances_device(int dim, const double *d_pts, size_t n, double voxel, int ddof, double *d_cov,
+                                 double *d_mean, uint32_t *d_count, uint32_t *d_first_index, uint32_t *d_voxel_of,
+                                 size_t *voxels, int device, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
