@@ -103,8 +103,68 @@ __device__ __forceinline__ void wave_tree(double (&acc)[N]) {
 // histogram to complete): the wave's tree and its sum into LDS go IN FRONT of that barrier -- a wave that is through
 // with its pairs folds while the slower ones finish -- and the fold of the wave sums behind it.  Same operations in
 // the same order as block_reduce_store.
+//
+// The packed tree.  After the step with offset 32 only lanes 0-31 of a register are read again, after 16 only lanes
+// 0-15: the plain tree spends most of its additions and lane moves on lanes nobody reads.  Where the totals need not
+// all stand in lane 0 -- here, they go to LDS -- the dead lanes carry other sums:
+//   step 32   v_permlane32_swap(x, y) gives X = {x[0..31], y[0..31]} and Y = {x[32..63], y[32..63]}, so X + Y holds
+//             x[l] + x[l+32] in lanes l < 32 and y[j] + y[j+32] in lanes 32 + j: two sums per register, one addition;
+//   step 16   v_permlane16_swap(p, q) gives X = rows {p0, q0, p2, q2} and Y = rows {p1, q1, p3, q3} (rows of 16
+//             lanes), so X + Y folds the four halves of p and q at once: four sums per register;
+//   8 .. 1    DPP row shifts never leave a row of 16: each row folds its own sum.
+// Every sum sees the operands of v[l] + v[l+off] in that order, so every bit is the plain tree's.  An odd register at
+// a packed step takes the plain step (tree_down reads the same rows: both of its packed sums stay right, and the half
+// that holds no sum is never stored).
+// WHERE THE TOTALS STAND: sum k = 4 j + c is in register j, lane 0 of row 0, 2, 1, 3 for c = 0, 1, 2, 3 -- that is,
+// row r of register j holds sum 4 j + 2 (r & 1) + (r >> 1).  `acc` itself is left as it came (the plain tree below
+// leaves the totals in its lane 0; no caller reads them there).
+// (a build with ICP_TREE_BPERMUTE keeps the plain tree)
+#ifndef ICP_TREE_BPERMUTE
+template <bool P32>
+__device__ __forceinline__ double packed_fold(double x, double y) {
+  const long long bx = __double_as_longlong(x), by = __double_as_longlong(y);
+  const unsigned xl = (unsigned)(bx & 0xffffffffll), xh = (unsigned)((unsigned long long)bx >> 32);
+  const unsigned yl = (unsigned)(by & 0xffffffffll), yh = (unsigned)((unsigned long long)by >> 32);
+  unsigned Xl, Xh, Yl, Yh;
+  if constexpr (P32) {
+    const auto rl = __builtin_amdgcn_permlane32_swap(xl, yl, false, false);
+    const auto rh = __builtin_amdgcn_permlane32_swap(xh, yh, false, false);
+    Xl = rl[0], Yl = rl[1], Xh = rh[0], Yh = rh[1];
+  } else {
+    const auto rl = __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
+    const auto rh = __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
+    Xl = rl[0], Yl = rl[1], Xh = rh[0], Yh = rh[1];
+  }
+  const double X = __longlong_as_double((long long)(((unsigned long long)Xh << 32) | Xl));
+  const double Y = __longlong_as_double((long long)(((unsigned long long)Yh << 32) | Yl));
+  return X + Y;
+}
+#endif
 template <int N>
 __device__ __forceinline__ void block_reduce_waves(double (&acc)[N], double (*sm)[N]) {
+#ifndef ICP_TREE_BPERMUTE
+  if constexpr (N >= 4) {
+    constexpr int M1 = (N + 1) / 2, M2 = (M1 + 1) / 2;
+    double p[M1], q[M2];
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) p[j] = packed_fold<true>(acc[2 * j], acc[2 * j + 1]);
+    if constexpr (N & 1) p[M1 - 1] = acc[N - 1] + tree_down<32>(acc[N - 1]);
+#pragma unroll
+    for (int j = 0; j < M1 / 2; ++j) q[j] = packed_fold<false>(p[2 * j], p[2 * j + 1]);
+    if constexpr (M1 & 1) q[M2 - 1] = p[M1 - 1] + tree_down<16>(p[M1 - 1]);
+    tree_step<M2, 8>(q);
+    tree_step<M2, 4>(q);
+    tree_step<M2, 2>(q);
+    tree_step<M2, 1>(q);
+    if ((threadIdx.x & 15) == 0) {
+      const int r = (threadIdx.x >> 4) & 3, c = 2 * (r & 1) + (r >> 1);
+#pragma unroll
+      for (int j = 0; j < M2; ++j)
+        if (4 * j + c < N) sm[threadIdx.x >> 6][4 * j + c] = q[j];
+    }
+    return;
+  }
+#endif
   wave_tree<N>(acc);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
