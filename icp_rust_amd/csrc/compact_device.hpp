@@ -1,16 +1,30 @@
-// The stable compaction the gate (gate.hip), the plane gate (gate_plane.hip), the crop (crop.hip) and the voxel thinning
-// (voxel.hip) share.  A tile =
-// kCompactTile consecutive elements = one workgroup of four waves, four rounds of 256 elements.  A first launch counts
-// the survivors of every tile (a ballot per round and wave gives the wave's count and the lane's rank among its wave's
-// survivors; the sixteen counts meet in LDS) into cnt[tile]; k_compact_chunks adds the counts up in chunks of
-// kCompactChunk tiles; in the last launch a workgroup per tile adds up the chunk sums and the counts in front of it and
-// moves its survivors there.  Every term of a position counts survivors that come EARLIER in the input: the order is
-// kept and a position is a pure function of the inputs.  No atomics, no workgroup waits for another.
+// The stable compaction, in one place.  A tile = kCompactTile consecutive elements = one workgroup of four waves, four
+// rounds of 256 elements.  A first launch counts the survivors of every tile (a ballot per round and wave gives the
+// wave's count and the lane's rank among its wave's survivors; the sixteen counts meet in LDS) into cnt[tile];
+// k_compact_chunks adds the counts up in chunks of kCompactChunk tiles; in the last launch a workgroup per tile adds up
+// the chunk sums and the counts in front of it and moves its survivors there.  Every term of a position counts survivors
+// that come EARLIER in the input: the order is kept and a position is a pure function of the inputs.  No atomics, no
+// workgroup waits for another.
+//   the pieces  compact_wave_rank, compact_round_offset, compact_tile_ranks, compact_tile_base, k_compact_chunks: the
+//               gates (gate.hip: k_gate_stage, k_gate_place; gate_plane.hip: k_plgate_stage, k_lngate_stage,
+//               k_plgate_place) are built from these directly -- they compact into a tile's own staging segment and are
+//               shaped around their registers
+//   the bodies  compact_mark_tile and compact_place_tile: the whole of a mark and of a place kernel but its rule.  Every
+//               other user is one call of a body with its rule as a lambda:
+//                 marks   k_crop_mark<DIM>, k_crop_rec_mark (crop.hip), k_voxel_mark<DIM> (voxel.hip), k_mask_marks
+//                         (query.hip), k_outlier_count (outlier.hip)
+//                 places  k_crop_place<DIM> (crop.hip), k_voxel_place<DIM> (voxel.hip), k_vm_place (voxel_mean.hip;
+//                         voxel_cov.hip runs the same chain)
+//               The one exception is k_crop_rec_place (crop.hip), written out around the pieces: it was measurably
+//               slower through the body (the reason stands at the kernel).
+//   the host    compact_tiles, compact_chunks, launch_compact_chunks, and compact_total: the one read-back of the chunk
+//               sums, which is how a caller learns the number of survivors
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace icp {
 
@@ -83,6 +97,49 @@ __device__ __forceinline__ unsigned compact_tile_base(const uint32_t *__restrict
   return compact_block_sum(s, lds);
 }
 
+// The body of a mark launch (one workgroup per tile, kCompactThreads threads): keep(i) is called once for every element
+// i < n of the workgroup's tile, returns the element's flag and writes whatever mark words its caller keeps;
+// cnt[tile] = the tile's survivors.
+template <class Keep>
+__device__ __forceinline__ void compact_mark_tile(size_t n, uint32_t *__restrict__ cnt, Keep keep) {
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  bool in[kCompactRounds];
+  unsigned rank[kCompactRounds];
+#pragma unroll
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + threadIdx.x;
+    in[k] = i < n && keep(i);
+  }
+  const unsigned total = compact_tile_ranks(in, rank, wcnt);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+// The body of a place launch (the same geometry; cnt and sums as the mark launch and k_compact_chunks left them):
+// kept(i) gives the flag of every element i < n of the tile; then each(i, at, in) runs for EVERY i < n, survivor
+// (in) or not, with at = the survivors in front of i in the whole input: a survivor's position (< the survivors in all).
+template <class Kept, class Each>
+__device__ __forceinline__ void compact_place_tile(size_t n, const uint32_t *__restrict__ cnt,
+                                                   const uint32_t *__restrict__ sums, Kept kept, Each each) {
+  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
+  __shared__ unsigned lds[kCompactWaves];
+  const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
+  const size_t first = (size_t)blockIdx.x * kCompactTile;
+  bool in[kCompactRounds];
+  unsigned rank[kCompactRounds];
+#pragma unroll
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + threadIdx.x;
+    in[k] = i < n && kept(i);
+  }
+  (void)compact_tile_ranks(in, rank, wcnt);
+#pragma unroll
+  for (unsigned k = 0; k < kCompactRounds; ++k) {
+    const size_t i = first + k * kCompactThreads + threadIdx.x;
+    if (i < n) each(i, (size_t)base + rank[k], in[k]);
+  }
+}
+
 namespace {  // (a copy per translation unit that includes this: the library has no relocatable device code)
 
 // sums[c] = the survivors of tiles [kCompactChunk c, kCompactChunk (c + 1))
@@ -100,6 +157,18 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact_chunks(const uint32
 [[maybe_unused]] hipError_t launch_compact_chunks(const uint32_t *cnt, unsigned tiles, uint32_t *sums, hipStream_t stream) {
   hipLaunchKernelGGL(k_compact_chunks, dim3(compact_chunks(tiles)), dim3(kCompactThreads), 0, stream, cnt, tiles, sums);
   return hipGetLastError();
+}
+
+// *total = the survivors in all: the chunk sums copied to the host on `stream`, which is waited for, and added up
+[[maybe_unused]] hipError_t compact_total(const uint32_t *sums, unsigned chunks, hipStream_t stream, size_t *total) {
+  std::vector<uint32_t> host(chunks);
+  hipError_t e = hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return e;
+  size_t t = 0;
+  for (unsigned c = 0; c < chunks; ++c) t += host[c];
+  *total = t;
+  return hipSuccess;
 }
 
 }  // namespace

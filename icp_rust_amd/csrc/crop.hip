@@ -3,8 +3,10 @@
 // icp_append_targets (section 6).  Two STABLE compactions (compact_device.hpp): a mark launch that counts the survivors
 // of every tile of 1 024 consecutive elements, the chunk-sum launch k_compact_chunks (always run here: its sums are also
 // how the host learns the total) and a place launch in which a workgroup per tile adds up the counts in front of it and
-// moves its survivors there.
-//   targets   k_crop_mark<DIM>      w[i] = kept ? 0 : kCropGone by the keep rule, cnt[tile]
+// moves its survivors there.  k_crop_mark, k_crop_place and k_crop_rec_mark are compact_mark_tile / compact_place_tile
+// of that header with their rule as a lambda (k_crop_rec_place is written out: see there); the host learns a total
+// through its compact_total.
+//   targets  k_crop_mark<DIM>      w[i] = kept ? 0 : kCropGone by the keep rule, cnt[tile]
 //             k_crop_place<DIM>     w[i] = the new index of target i (or kCropGone): the new_index table; the points, and
 //                                   the normals where present, move to their new index in a second buffer
 //   records   k_crop_rec_mark       the grid's records are cell-sorted and removing records keeps them sorted: the
@@ -41,23 +43,13 @@ template <int DIM>
 __global__ __launch_bounds__(kCompactThreads) void k_crop_mark(const double *__restrict__ dst, unsigned m, double cx, double cy,
                                                             double r2, uint32_t *__restrict__ w,
                                                             uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = false;
-    if (i < m) {
-      const double dx = dst[i * DIM] - cx, dy = dst[i * DIM + 1] - cy;
-      const double d2 = dx * dx + dy * dy;
-      in[k] = d2 <= r2;
-      w[i] = in[k] ? 0u : kCropGone;
-    }
-  }
-  const unsigned total = compact_tile_ranks(in, rank, wcnt);
-  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+  compact_mark_tile(m, cnt, [=](size_t i) {
+    const double dx = dst[i * DIM] - cx, dy = dst[i * DIM + 1] - cy;
+    const double d2 = dx * dx + dy * dy;
+    const bool in = d2 <= r2;
+    w[i] = in ? 0u : kCropGone;
+    return in;
+  });
 }
 
 // w: in, the marks; out, the new_index table.  *normals_kept (nullable) receives the survivors among the first
@@ -70,56 +62,31 @@ __global__ __launch_bounds__(kCompactThreads) void k_crop_place(const double *__
                                                              const uint32_t *__restrict__ sums, double *__restrict__ out,
                                                              double *__restrict__ out_normals,
                                                              uint32_t *__restrict__ normals_kept) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  __shared__ unsigned lds[kCompactWaves];
-  const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
+  compact_place_tile(
+      m, cnt, sums, [=](size_t i) { return w[i] != kCropGone; },
+      [=](size_t i, size_t at, bool in) {  // (a survivor's at: inside a buffer that holds the survivors)
+        if (normals_kept && i == normals_m) *normals_kept = (uint32_t)at;
+        if (!in) return;
+        w[i] = (uint32_t)at;
 #pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = i < m && w[i] != kCropGone;
-  }
-  (void)compact_tile_ranks(in, rank, wcnt);
+        for (int d = 0; d < DIM; ++d) out[at * DIM + d] = dst[i * DIM + d];
+        if (out_normals && i < normals_m) {
 #pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    if (i >= m) continue;
-    const size_t at = (size_t)base + rank[k];  // (< the survivors in all: inside a buffer that holds them)
-    if (normals_kept && i == normals_m) *normals_kept = (uint32_t)at;
-    if (!in[k]) continue;
-    w[i] = (uint32_t)at;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) out[at * DIM + d] = dst[i * DIM + d];
-    if (out_normals && i < normals_m) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) out_normals[at * 3 + d] = normals[i * 3 + d];
-    }
-  }
+          for (int d = 0; d < 3; ++d) out_normals[at * 3 + d] = normals[i * 3 + d];
+        }
+      });
 }
 
 // w[p] = the new index of the target behind the record at sorted position p (kCropGone: removed)
 __global__ __launch_bounds__(kCompactThreads) void k_crop_rec_mark(const GridPoint *__restrict__ pts, unsigned m,
                                                                 const uint32_t *__restrict__ new_index,
                                                                 uint32_t *__restrict__ w, uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t p = first + k * kCompactThreads + threadIdx.x;
-    in[k] = false;
-    if (p < m) {
-      const uint32_t j = pts[p].idx;
-      const uint32_t to = j < m ? new_index[j] : kCropGone;  // (a record's idx is always < m: this only keeps the read in bounds)
-      w[p] = to;
-      in[k] = to != kCropGone;
-    }
-  }
-  const unsigned total = compact_tile_ranks(in, rank, wcnt);
-  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+  compact_mark_tile(m, cnt, [=](size_t p) {
+    const uint32_t j = pts[p].idx;
+    const uint32_t to = j < m ? new_index[j] : kCropGone;  // (a record's idx is always < m: this only keeps the read in bounds)
+    w[p] = to;
+    return to != kCropGone;
+  });
 }
 
 // w: in, the records' new indices; out, for EVERY sorted position p the survivors in front of it
@@ -127,6 +94,9 @@ __global__ __launch_bounds__(kCompactThreads) void k_crop_rec_place(const GridPo
                                                                  uint32_t *__restrict__ w, const uint32_t *__restrict__ cnt,
                                                                  const uint32_t *__restrict__ sums,
                                                                  GridPoint *__restrict__ pts2) {
+  // Not compact_place_tile: a place needs the word it read for the flag again (the record's new idx), and read through
+  // the body's kept(p) the tile's four loads are each waited for before the next is issued, where the loads into to[]
+  // below are in flight together (profiles/compact_bodies_ab.txt: + 1 us on an 83 us crop of 1M targets).
   __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
   __shared__ unsigned lds[kCompactWaves];
   const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
@@ -222,11 +192,8 @@ int api::remove_marked_targets(icp_handle *h, uint32_t *w, uint32_t *cnt, unsign
   const int dim = h->dim;
   uint32_t *sums = cnt + tiles, *aux = sums + chunks;
   HIP_TRY(launch_compact_chunks(cnt, tiles, sums, s));
-  std::vector<uint32_t> host(chunks + 1);
-  HIP_TRY(hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
   size_t kept_ = 0;
-  for (unsigned c = 0; c < chunks; ++c) kept_ += host[c];
+  HIP_TRY(compact_total(sums, chunks, s, &kept_));
   const unsigned kept = (unsigned)kept_;
   if (kept == m_old) {  // nothing to remove: the handle is left exactly as it was
     if (new_index)
@@ -254,9 +221,10 @@ int api::remove_marked_targets(icp_handle *h, uint32_t *w, uint32_t *cnt, unsign
   }
   size_t normals_after = with_normals ? kept : 0;
   if (count_normals) {
-    HIP_TRY(hipMemcpyAsync(&host[chunks], aux, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    uint32_t counted = 0;
+    HIP_TRY(hipMemcpyAsync(&counted, aux, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    normals_after = host[chunks];
+    normals_after = counted;
   }
   if (new_index) {
     HIP_TRY(hipMemcpyAsync(new_index, w, (size_t)m_old * sizeof(uint32_t), hipMemcpyDeviceToHost, s));

@@ -12,7 +12,8 @@
 //   statistical u (above), two runs of the fold tree (fold_device.hpp: k_stat_level is its first level, k_fold_level the
 //               others) for the mean and the deviation, k_stat_scalar between and behind them; the threshold stays on
 //               the device.
-//   shared      k_outlier_count  mark words (or u against the threshold) -> cnt[tile], as k_crop_mark's tail
+//   shared      k_outlier_count  mark words (or u against the threshold) -> cnt[tile]: compact_device.hpp's
+//               compact_mark_tile with either rule
 // Counts are integers and every sum is a fixed tree or a left fold: a result is a pure function of the input.
 #include <cmath>
 #include <map>
@@ -163,25 +164,12 @@ __global__ __launch_bounds__(kCompactThreads) void k_outlier_count(uint32_t *__r
                                                                    const double *__restrict__ u,
                                                                    const double *__restrict__ threshold,
                                                                    uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = false;
-    if (i < m) {
-      if (u) {
-        in[k] = !(u[i] > *threshold);
-        w[i] = in[k] ? 0u : kCropGone;
-      } else {
-        in[k] = w[i] != kCropGone;
-      }
-    }
-  }
-  const unsigned total = compact_tile_ranks(in, rank, wcnt);
-  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+  compact_mark_tile(m, cnt, [=](size_t i) {
+    if (!u) return w[i] != kCropGone;  // (uniform: one mode per launch)
+    const bool in = !(u[i] > *threshold);
+    w[i] = in ? 0u : kCropGone;
+    return in;
+  });
 }
 
 namespace {

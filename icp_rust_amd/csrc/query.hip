@@ -11,8 +11,8 @@
 //   order    from kQueryCellMinN queries on, lane j serves the j-th query in (cell, index) order -- the per-call sort
 //            of icp_sort_source_device (prepare_queries, sort only) -- and writes row perm[j].  Results are per query:
 //            the order changes no bit.  With q == nullptr the counts' queries are the targets, in record order.
-//   removal  k_mask_marks  keep bytes -> mark words and cnt[tile] (k_crop_mark with the mask as its rule), then the
-//            crop's back half (crop.hip: remove_marked_targets).
+//   removal  k_mask_marks  keep bytes -> mark words and cnt[tile] (compact_device.hpp: compact_mark_tile with the mask
+//            as its rule), then the crop's back half (crop.hip: remove_marked_targets).
 // Counts are integers, lists are exact selections: a result is a pure function of the input.
 #include <cmath>
 #include <map>
@@ -188,25 +188,15 @@ __global__ __launch_bounds__(256) void k_count_within(const double *__restrict__
   counts[i] = found;
 }
 
-// The keep rule of icp_remove_targets: w[i] = keep[i] != 0 ? 0 : kCropGone, and cnt[tile] -- k_crop_mark with the
-// caller's mask in place of the disc.
+// The keep rule of icp_remove_targets: w[i] = keep[i] != 0 ? 0 : kCropGone, and cnt[tile] -- compact_mark_tile with
+// the caller's mask as its rule, as k_crop_mark with the disc.
 __global__ __launch_bounds__(kCompactThreads) void k_mask_marks(const uint8_t *__restrict__ keep, unsigned m,
                                                                 uint32_t *__restrict__ w, uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = false;
-    if (i < m) {
-      in[k] = keep[i] != 0;
-      w[i] = in[k] ? 0u : kCropGone;
-    }
-  }
-  const unsigned total = compact_tile_ranks(in, rank, wcnt);
-  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+  compact_mark_tile(m, cnt, [=](size_t i) {
+    const bool in = keep[i] != 0;
+    w[i] = in ? 0u : kCropGone;
+    return in;
+  });
 }
 
 namespace {

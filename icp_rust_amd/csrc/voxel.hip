@@ -17,15 +17,18 @@
 //                                  Of the lanes of a wave that share the cell of its first inserting lane only that
 //                                  lane walks (it has the lowest index of them).
 //             k_voxel_mark<DIM>    walks the same slots read-only: kept iff the walk ends on a word that holds i;
-//                                  w[i] = kept ? 0 : kCropGone, cnt[tile] (compact_device.hpp)
+//                                  w[i] = kept ? 0 : kCropGone, cnt[tile] (compact_device.hpp: compact_mark_tile with
+//                                  this rule)
 //             k_voxel_place<DIM>   the stand-alone call's compaction: kept points and / or their indices
+//                                  (compact_place_tile)
+//             launch_voxel_front   what both stand-alone calls (this file's and voxel_mean.hip's) begin with: table, marks,
+//                                  chunk sums; they end with compact_total
 // No float reductions.  The hash only chooses where a walk starts: it has no part in the result.
 // The cell, the hash, the read-only walk and the workspace are voxel_device.hpp's: voxel_mean.hip (section 25) shares them.
 #include <cfloat>
 #include <cmath>
 #include <map>
 #include <mutex>
-#include <vector>
 
 #include "api_internal.hpp"
 #include "compact_device.hpp"
@@ -69,22 +72,12 @@ template <int DIM>
 __global__ __launch_bounds__(kCompactThreads) void k_voxel_mark(const double *__restrict__ pts, size_t n, double v,
                                                                 const uint32_t *__restrict__ tab, size_t mask,
                                                                 uint32_t *__restrict__ w, uint32_t *__restrict__ cnt) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = false;
-    if (i < n) {
-      double c[3];
-      in[k] = voxel_cell<DIM>(pts, i, v, c) && voxel_leader<DIM>(pts, n, v, tab, mask, i, c) == (uint32_t)i;
-      w[i] = in[k] ? 0u : kCropGone;
-    }
-  }
-  const unsigned total = compact_tile_ranks(in, rank, wcnt);
-  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+  compact_mark_tile(n, cnt, [=](size_t i) {
+    double c[3];
+    const bool in = voxel_cell<DIM>(pts, i, v, c) && voxel_leader<DIM>(pts, n, v, tab, mask, i, c) == (uint32_t)i;
+    w[i] = in ? 0u : kCropGone;
+    return in;
+  });
 }
 
 // out (nullable): the kept points; kept_index (nullable): their indices in the input
@@ -94,29 +87,16 @@ __global__ __launch_bounds__(kCompactThreads) void k_voxel_place(const double *_
                                                                  const uint32_t *__restrict__ cnt,
                                                                  const uint32_t *__restrict__ sums, double *__restrict__ out,
                                                                  uint32_t *__restrict__ kept_index) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  __shared__ unsigned lds[kCompactWaves];
-  const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
+  compact_place_tile(
+      n, cnt, sums, [=](size_t i) { return w[i] != kCropGone; },
+      [=](size_t i, size_t at, bool in) {
+        if (!in) return;  // (a kept point's at: < the kept points in all, which are <= n)
+        if (kept_index) kept_index[at] = (uint32_t)i;
+        if (out) {
 #pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = i < n && w[i] != kCropGone;
-  }
-  (void)compact_tile_ranks(in, rank, wcnt);
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    if (!in[k]) continue;
-    const size_t at = (size_t)base + rank[k];  // (< the kept points in all, which are <= n)
-    if (kept_index) kept_index[at] = (uint32_t)i;
-    if (out) {
-#pragma unroll
-      for (int d = 0; d < DIM; ++d) out[at * DIM + d] = pts[i * DIM + d];
-    }
-  }
+          for (int d = 0; d < DIM; ++d) out[at * DIM + d] = pts[i * DIM + d];
+        }
+      });
 }
 
 namespace {
@@ -164,6 +144,19 @@ hipError_t launch_voxel_marks(int dim, const double *d_pts, size_t n, double v, 
   return hipGetLastError();
 }
 
+// the front half of a stand-alone call (voxel_device.hpp)
+hipError_t launch_voxel_front(VoxelWs &W, int dim, const double *d_pts, size_t n, double v, hipStream_t s, size_t *mask,
+                              uint32_t **sums) {
+  const unsigned tiles = compact_tiles(n), chunks = compact_chunks(tiles);
+  hipError_t e;
+  if ((e = voxel_table(W, n, s, mask)) != hipSuccess) return e;
+  if ((e = reserve(W.w, W.cap_w, n)) != hipSuccess) return e;
+  if ((e = reserve(W.cnt, W.cap_cnt, (size_t)tiles + chunks)) != hipSuccess) return e;
+  *sums = W.cnt + tiles;
+  if ((e = launch_voxel_marks(dim, d_pts, n, v, W.tab, *mask, W.w, W.cnt, s)) != hipSuccess) return e;
+  return launch_compact_chunks(W.cnt, tiles, *sums, s);
+}
+
 namespace {
 
 // the stand-alone call on device buffers (g_mu held, the device current): everything on `s`, which is waited for
@@ -171,12 +164,8 @@ int voxel_downsample_on(VoxelWs &W, int dim, const double *d_pts, size_t n, doub
                         uint32_t *d_kept_index, size_t *kept, hipStream_t s) {
   const unsigned tiles = compact_tiles(n), chunks = compact_chunks(tiles);
   size_t mask = 0;
-  HIP_TRY(voxel_table(W, n, s, &mask));
-  HIP_TRY(reserve(W.w, W.cap_w, n));
-  HIP_TRY(reserve(W.cnt, W.cap_cnt, (size_t)tiles + chunks));
-  uint32_t *sums = W.cnt + tiles;
-  HIP_TRY(launch_voxel_marks(dim, d_pts, n, v, W.tab, mask, W.w, W.cnt, s));
-  HIP_TRY(launch_compact_chunks(W.cnt, tiles, sums, s));
+  uint32_t *sums = nullptr;
+  HIP_TRY(launch_voxel_front(W, dim, d_pts, n, v, s, &mask, &sums));
   if (d_out || d_kept_index) {
     if (dim == 3)
       hipLaunchKernelGGL(k_voxel_place<3>, dim3(tiles), dim3(kCompactThreads), 0, s, d_pts, n, (const uint32_t *)W.w,
@@ -186,12 +175,7 @@ int voxel_downsample_on(VoxelWs &W, int dim, const double *d_pts, size_t n, doub
                          (const uint32_t *)W.cnt, (const uint32_t *)sums, d_out, d_kept_index);
     HIP_TRY(hipGetLastError());
   }
-  std::vector<uint32_t> host(chunks);
-  HIP_TRY(hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  size_t total = 0;
-  for (unsigned c = 0; c < chunks; ++c) total += host[c];
-  *kept = total;
+  HIP_TRY(compact_total(sums, chunks, s, kept));
   return ICP_OK;
 }
 

@@ -99,6 +99,10 @@ hipError_t voxel_table(VoxelWs &W, size_t n, hipStream_t s, size_t *mask);
 // n > 0 points of d_pts
 hipError_t launch_voxel_marks(int dim, const double *d_pts, size_t n, double v, uint32_t *tab, size_t mask, uint32_t *w,
                               uint32_t *cnt, hipStream_t s);
+// the front half of a stand-alone call: voxel_table, W.w and W.cnt reserved for the n > 0 points of d_pts, then
+// launch_voxel_marks and the chunk sums on `s`; *sums = the chunk sums (behind the tile counts in W.cnt)
+hipError_t launch_voxel_front(VoxelWs &W, int dim, const double *d_pts, size_t n, double v, hipStream_t s, size_t *mask,
+                              uint32_t **sums);
 
 // ---- the members of a voxel (voxel_mean.hip defines them; voxel_cov.hip runs the same chain) ----
 constexpr size_t kVmMaxPoints = (size_t)1 << 27;  // what the sort of the members takes

@@ -2,9 +2,11 @@
 // points, their number, the lowest index, and per point the rank of its voxel.  Membership and order are voxel
 // thinning's (section 22, voxel_device.hpp); a sum's bits are the fold tree of section 9 over the members in ascending
 // index, so a result is a pure function of the input.
-//   the chain  k_voxel_insert, k_voxel_mark, k_compact_chunks       as the thinning runs them: w[i] = 0 for a voxel's lowest
+//   the chain  k_voxel_insert, k_voxel_mark, k_compact_chunks       as the thinning runs them (voxel.hip:
+//                                                                   launch_voxel_front): w[i] = 0 for a voxel's lowest
 //                                                                   index, cnt[tile]
-//              k_vm_place       leader i of rank r: first_index[r] = i, w[i] = r (the marks become the leaders' ranks)
+//              k_vm_place       leader i of rank r: first_index[r] = i, w[i] = r (the marks become the leaders' ranks);
+//                               compact_device.hpp's compact_place_tile with this rule
 //              k_vm_key<DIM>    point i walks the table read-only to its leader: key[i] = voxel_of[i] = w[leader]; a
 //                               dropped point: key n (sorts last), voxel_of 0xffffffff
 //              stable_sort_cells (qsort.hip)  perm: the points by (rank, index) -- a voxel's members contiguous, ascending
@@ -19,8 +21,6 @@
 // The tree and the bodies of the three folding kernels are voxel_fold_device.hpp's: voxel_cov.hip (section 26) instantiates
 // them with the second moments beside the means, and its entries run this file's chain (voxel_centroids_on) with its own
 // folding launches in place of launch_centroid_chain.  No float atomics.
-#include <vector>
-
 #include "api_internal.hpp"
 #include "compact_device.hpp"
 #include "voxel_device.hpp"
@@ -36,26 +36,13 @@ __global__ __launch_bounds__(kCompactThreads) void k_vm_place(size_t n, uint32_t
                                                               const uint32_t *__restrict__ cnt,
                                                               const uint32_t *__restrict__ sums,
                                                               uint32_t *__restrict__ first_index) {
-  __shared__ unsigned wcnt[kCompactRounds][kCompactWaves];
-  __shared__ unsigned lds[kCompactWaves];
-  const unsigned base = compact_tile_base(cnt, sums, blockIdx.x, lds);
-  const size_t first = (size_t)blockIdx.x * kCompactTile;
-  bool in[kCompactRounds];
-  unsigned rank[kCompactRounds];
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    in[k] = i < n && w[i] != kCropGone;
-  }
-  (void)compact_tile_ranks(in, rank, wcnt);
-#pragma unroll
-  for (unsigned k = 0; k < kCompactRounds; ++k) {
-    const size_t i = first + k * kCompactThreads + threadIdx.x;
-    if (!in[k]) continue;
-    const uint32_t at = base + rank[k];  // (< the voxels in all, which are <= n)
-    if (first_index) first_index[at] = (uint32_t)i;
-    w[i] = at;
-  }
+  compact_place_tile(
+      n, cnt, sums, [=](size_t i) { return w[i] != kCropGone; },
+      [=](size_t i, size_t at, bool in) {
+        if (!in) return;  // (a leader's at: < the voxels in all, which are <= n)
+        if (first_index) first_index[at] = (uint32_t)i;
+        w[i] = (uint32_t)at;
+      });
 }
 
 // key[i] = the rank of point i's voxel (n for a point in none); voxel_of (nullable): the same, 0xffffffff for none
@@ -191,10 +178,6 @@ int voxel_centroids_on(VoxelWs &W, int dim, const double *d_pts, size_t n, doubl
                        int ddof) {
   const unsigned tiles = compact_tiles(n), chunks = compact_chunks(tiles);
   const bool members = d_mean || d_count || d_voxel_of;  // (first_index and the number of voxels need no sort)
-  size_t mask = 0;
-  HIP_TRY(voxel_table(W, n, s, &mask));
-  HIP_TRY(reserve(W.w, W.cap_w, n));
-  HIP_TRY(reserve(W.cnt, W.cap_cnt, (size_t)tiles + chunks));
   if (members) {
     HIP_TRY(reserve(W.key, W.cap_key, n));  // (the sort's keys; voxel_of alone needs the launch that writes them)
     if (d_mean || d_count) {
@@ -207,9 +190,9 @@ int voxel_centroids_on(VoxelWs &W, int dim, const double *d_pts, size_t n, doubl
       HIP_TRY(reserve(W.rec, W.cap_rec, (2 * (n / kVmChunk) + 2) * (d_cov ? 6 : 3)));  // (a record: the sums of an item)
     }
   }
-  uint32_t *sums = W.cnt + tiles;
-  HIP_TRY(launch_voxel_marks(dim, d_pts, n, v, W.tab, mask, W.w, W.cnt, s));
-  HIP_TRY(launch_compact_chunks(W.cnt, tiles, sums, s));
+  size_t mask = 0;
+  uint32_t *sums = nullptr;
+  HIP_TRY(launch_voxel_front(W, dim, d_pts, n, v, s, &mask, &sums));
   if (members || d_first_index) {
     hipLaunchKernelGGL(k_vm_place, dim3(tiles), dim3(kCompactThreads), 0, s, n, W.w, (const uint32_t *)W.cnt,
                        (const uint32_t *)sums, d_first_index);
@@ -232,12 +215,7 @@ int voxel_centroids_on(VoxelWs &W, int dim, const double *d_pts, size_t n, doubl
     else if (dim == 3) HIP_TRY(launch_centroid_chain<3>(W, d_pts, n, d_mean, d_count, s));
     else HIP_TRY(launch_centroid_chain<2>(W, d_pts, n, d_mean, d_count, s));
   }
-  std::vector<uint32_t> host(chunks);
-  HIP_TRY(hipMemcpyAsync(host.data(), sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  size_t total = 0;
-  for (unsigned c = 0; c < chunks; ++c) total += host[c];
-  *voxels = total;
+  HIP_TRY(compact_total(sums, chunks, s, voxels));
   return ICP_OK;
 }
 
