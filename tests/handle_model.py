@@ -7,9 +7,12 @@ previous owner of its pooled buffers.
 Three pieces, none of which needs a GPU (`torch` is never imported here):
 
   * `Model`: what a handle holds, in numpy -- dimension, cloud, normals (m x 3 in both dimensions) with normals_m /
-    normals_k, the engine asked for, alive or closed -- and its transitions (append, crop, normals, close / create).
+    normals_k, the engine asked for, alive or closed -- and its transitions (append, keep_rows -- the one behind crop,
+    thin, the removal by mask and the two outlier filters --, normals, close / create).
   * `sequence(seed, profile)`: a list of plain-data steps (op name, sizes, sub-seed, parameters).  Every random draw of
     a step is keyed by the sub-seed the step carries, so the same list drives the GPU and any stand-in.
+    `map_sequence(seed, profile)`: the same with thin, remove, radius_filter, stat_filter and the reads through the grid
+    (neighbours, query, count_within) in the mix; their parameters come from the model's cloud.
   * `run(device, steps)`: applies each step to a Model and to `device` and compares, bit for bit unless stated, with
     the references the single-call tests already use (imported, not copied).  `device` is any object with the
     operation methods of `ReferenceDevice` below: on the GPU a thin adapter over Icp2d / Icp3d
@@ -33,7 +36,10 @@ from test_gpu_plane_parity import oracle_chain
 from test_gpu_quality import transformed
 from test_line_abi import lift, line_normals_numpy, outline
 from test_map import moved
+from test_outlier_abi import lists_of, new_index_of as filter_index_of, radius_keep, statistical_keep
 from test_p2plane import room
+from test_query_abi import count_within_ref, mask_keep, moved_queries, query_lists
+from test_voxel_abi import keep_mask as thin_mask
 
 INF = float("inf")
 TRUE_PARAM = (0.03, -0.02, 0.01)  # the pose every scan is moved by (tests/test_line_abi.py's)
@@ -44,7 +50,15 @@ BRUTE_MAX_M = 10_000              # nn_search: O.nn_brute up to here, the kd-tre
 LINE_WORK = 6_000 * 6_000
 LINE_ENDS = 512
 MODES = {"auto": I.NN_AUTO, "brute": I.NN_BRUTE, "grid": I.NN_GRID}
-MUTATING = ("create", "append", "crop", "reserve", "set_nn_mode", "normals")
+REMOVALS = ("crop", "thin", "remove", "radius_filter", "stat_filter")
+READS = ("neighbours", "query", "count_within")
+MUTATING = ("create", "append", "reserve", "set_nn_mode", "normals") + REMOVALS
+# the restatements of the filters, of the full neighbour lists and of the counts around the targets themselves are
+# quadratic in m (about 3 s each at 9 000 targets, 35 s at 30 000): the generator emits the filters up to here only, and
+# the full-range lists and the counts around the targets up to its profile's "full_max", which is lower still
+QUADRATIC_MAX_M = 12_000
+SUB_ROWS = 512                    # neighbours of a larger cloud: a sub-range of this many rows (at most 1 024)
+GONE = 0xFFFFFFFF
 
 
 def bits(a):
@@ -87,10 +101,15 @@ class Model:
         """the normals of the kept rows"""
         return self.normals[mask]
 
-    def crop(self, mask):
-        """kept rows keep their order and their normals; rows appended but not yet updated stay without"""
+    def current(self, mask):
+        """how many of the kept rows have current normals: the kept ones among the first normals_m"""
+        return int(mask[:self.normals_m].sum())
+
+    def keep_rows(self, mask):
+        """every removal (crop, thin, mask, the two filters): kept rows keep their order and their normals; rows appended
+        but not yet updated stay without"""
         self.normals = np.ascontiguousarray(self.carried(mask))
-        self.normals_m = int(mask[:self.normals_m].sum())
+        self.normals_m = self.current(mask)
         self.cloud = np.ascontiguousarray(self.cloud[mask])
 
     def set_normals(self, normals, k):
@@ -132,8 +151,71 @@ def make_pairs(n, seed):
     return np.ascontiguousarray(a), np.ascontiguousarray(b)
 
 
+def make_mask(m, share, seed, dtype):
+    """the keep mask of a `remove` step: about `share` of the m targets (1.0: all, 0.0: none); as uint8 the kept bytes
+    take values from 1 to 255, not only 1"""
+    rng = np.random.default_rng(seed)
+    keep = rng.random(m) < share
+    if dtype == "bool":
+        return keep
+    return np.where(keep, rng.integers(1, 256, m), 0).astype(np.uint8)
+
+
+def make_read_queries(cloud, n, seed, pose):
+    """the n points of a `query` / `count_within` step and the Transform they go in with: points around the CURRENT cloud
+    (make_queries), given in the frame that `pose` maps into the cloud's"""
+    if len(cloud):
+        q = make_queries(cloud, n, seed)
+    else:  # (an empty handle refuses the read: any points do)
+        q = np.ascontiguousarray(np.random.default_rng(seed).normal(size=(n, cloud.shape[1])))
+    if pose is None:
+        return q, None
+    T = I.Transform(list(pose))
+    return np.ascontiguousarray(moved(q, T.inverse())), T
+
+
+def appended_points(model, step):
+    """the points of an append step as they arrive in the cloud: make_cloud moved by the step's pose; with "clip" also
+    clipped into the bounding box of the cloud as it is -- inside the box the grid was built for, whatever was removed
+    since"""
+    pts = make_cloud(model.dim, step["k"], step["seed"], step.get("shift", (0.0, 0.0)))
+    if step.get("pose") is not None:
+        pts = moved(pts, I.Transform(step["pose"]))
+    if step.get("clip") and model.m:
+        pts = np.clip(pts, model.cloud.min(axis=0), model.cloud.max(axis=0))
+    return np.ascontiguousarray(pts)
+
+
 def opose(T):
     return O.Pose(*T.pose.as_tuple())
+
+
+# the masks of the removals, shared by the generator, trace() and run(): each is restated once per process
+_MASKS = {}
+
+
+def removal_mask(cloud, step):
+    """(keep mask, statistics or None) of a removal step on `cloud`, by the single-call tests' restatements:
+    test_gpu_crop.keep_mask, test_voxel_abi.keep_mask, test_query_abi.mask_keep, test_outlier_abi.radius_keep and
+    statistical_keep"""
+    op = step["op"]
+    if op == "crop":
+        return keep_mask(cloud, step["center"], INF if step["radius"] == "inf" else step["radius"]), None
+    if op == "thin":
+        return thin_mask(cloud, step["v"]), None
+    if op == "remove":
+        return mask_keep(make_mask(len(cloud), step["share"], step["seed"], step["dtype"]))[0], None
+    key = (op, step.get("radius"), step.get("need"), step.get("k"), step.get("ratio"), cloud.shape, hash(cloud.tobytes()))
+    if key not in _MASKS:
+        if len(_MASKS) > 64:
+            _MASKS.clear()
+        if op == "radius_filter":
+            _MASKS[key] = (radius_keep(cloud, step["radius"], step["need"]), None)
+        elif op == "stat_filter":
+            _MASKS[key] = statistical_keep(cloud, step["k"], INF if step["ratio"] == "inf" else step["ratio"])
+        else:
+            raise ValueError(f"{op!r} is no removal")
+    return _MASKS[key]
 
 
 # ------------------------------------------------------------------------------------------ the references
@@ -233,6 +315,7 @@ class ReferenceDevice:
         self.last_block = 0
         self.prev_idx = None
         self.after_poison = False
+        self.cloud_before = None  # the cloud before the last removal; None after a create or an append
 
     # -- the transitions (the sabotaged stand-ins of tests/test_handle_model.py each change one line of one of these)
     def new_model(self, dim, cloud):
@@ -251,6 +334,7 @@ class ReferenceDevice:
     # -- life
     def create(self, dim, cloud, borrowed=False, trim=False):
         self.model = self.new_model(dim, cloud)
+        self.cloud_before = None
 
     def close(self):
         self.model.alive = False
@@ -265,12 +349,60 @@ class ReferenceDevice:
     def append(self, points, T=None):
         self.model.append(moved(points, T) if T is not None else points)
         self.last_block = len(points)
+        self.cloud_before = None
+
+    def index_of(self, mask):
+        return new_index_of(mask)
+
+    def remove_rows(self, mask):
+        """what every removal ends in: (the number removed, new_index)"""
+        index = self.index_of(mask)
+        self.cloud_before = self.model.cloud
+        self.model.keep_rows(mask)
+        return int(len(mask) - mask.sum()), index
 
     def crop(self, center, radius):
-        mask = keep_mask(self.model.cloud, center, radius)
-        index = new_index_of(mask)
-        self.model.crop(mask)
-        return int(len(mask) - mask.sum()), index
+        return self.remove_rows(keep_mask(self.model.cloud, center, radius))
+
+    def thin_keep(self, cloud, v):
+        return thin_mask(cloud, v)
+
+    def thin(self, v):
+        return self.remove_rows(self.thin_keep(self.model.cloud, v))
+
+    def remove(self, keep, entry):
+        return self.remove_rows(mask_keep(keep)[0])
+
+    def radius_keep(self, cloud, radius, need):
+        return radius_keep(cloud, radius, need)
+
+    def radius_filter(self, radius, need):
+        if self.model.m == 0:
+            return 0, np.zeros(0, dtype=np.uint32)
+        return self.remove_rows(self.radius_keep(self.model.cloud, radius, need))
+
+    def stat_filter(self, k, ratio):
+        mask, stats = statistical_keep(self.model.cloud, k, ratio)
+        return self.remove_rows(mask) + (stats,)
+
+    # -- reads through the grid: (status, ...); every one sees the cloud through searched_cloud()
+    def neighbours(self, k, first, count):
+        cloud = self.searched_cloud()
+        if len(cloud) == 0:
+            return _lib.EMPTY_DST, None, None
+        return (_lib.OK,) + lists_of(cloud, k, first, len(cloud) - first if count is None else count)
+
+    def query(self, q, k, T=None, order=None):
+        cloud = self.searched_cloud()
+        if len(cloud) == 0:
+            return _lib.EMPTY_DST, None, None
+        return (_lib.OK,) + query_lists(cloud, q, k, T)
+
+    def count_within(self, q, radius, cap=None, T=None):
+        cloud = self.searched_cloud()
+        if len(cloud) == 0:
+            return _lib.EMPTY_DST, None
+        return _lib.OK, count_within_ref(cloud, q, radius, cap, T)
 
     def reserve(self, capacity):
         pass
@@ -444,6 +576,19 @@ def _step_poisoned(model, device, step, src):
     j = len(bad) // 3
     bad[j, step["seed"] % 2] = np.nan
     init, kind = I.Transform(), step["kind"]
+    if kind in ("query", "count_within"):  # the NaN point lists nothing and counts nothing; every other row as restated
+        T = I.Transform(list(TRUE_PARAM))
+        if kind == "query":
+            got = device.query(bad, step["k"], T, None)
+            _check_lists(got, query_lists(model.cloud, bad, step["k"], T), "query with a NaN point")
+            nan = np.isnan(moved_queries(bad, T)).any(axis=1)
+            _need(nan[j] and np.all(got[1][nan] == GONE) and np.all(got[2][nan] == INF), "the NaN point's row is not padding")
+        else:
+            rc, counts = device.count_within(bad, step["radius"], step["cap"], T)
+            _need(rc == _lib.OK, "count_within with a NaN point: status", rc)
+            want = count_within_ref(model.cloud, bad, step["radius"], step["cap"], T)
+            _need(np.array_equal(np.asarray(counts), want) and counts[j] == 0, "count_within with a NaN point differs")
+        return
     if kind == "estimate":
         rc = device.estimate(bad, init, step["iters"], None)[0]
     elif kind == "normal":
@@ -488,6 +633,90 @@ def _step_normals(model, device, step):
     model.set_normals(got, k)  # the device's normals, as tests/test_gpu_plane_parity.py feeds the oracle
 
 
+def _step_removal(model, device, step):
+    """crop, thin, remove, radius_filter, stat_filter: the number removed, the whole new_index map and, for the statistical
+    filter, its three statistics to the bit (as tests/test_gpu_outlier.py holds them); on an empty handle the documented
+    return values: nothing removed, an empty map, statistics of +0.0.  _check_state follows."""
+    op = step["op"]
+    mask, stats = removal_mask(model.cloud, step)
+    if op == "crop":
+        got = device.crop(step["center"], INF if step["radius"] == "inf" else step["radius"])
+    elif op == "thin":
+        got = device.thin(step["v"])
+    elif op == "remove":
+        got = device.remove(make_mask(model.m, step["share"], step["seed"], step["dtype"]), step["entry"])
+    elif op == "radius_filter":
+        got = device.radius_filter(step["radius"], step["need"])
+    else:
+        got = device.stat_filter(step["k"], INF if step["ratio"] == "inf" else step["ratio"])
+    removed, index = got[:2]
+    want = int(len(mask) - mask.sum())
+    _need(removed == want, f"{op} removed", removed, "model", want)
+    index_of = new_index_of if op == "crop" else filter_index_of
+    _need(np.array_equal(np.asarray(index), index_of(mask)), f"{op}: the index map differs")
+    if op == "stat_filter":
+        _need(np.array_equal(bits(got[2]), bits(stats)), "stat_filter: (mean, deviation, threshold)", got[2], "reference", stats)
+    model.keep_rows(mask)
+
+
+RESTATE_ROWS = 5_000  # a query of more points is restated on both ends and a seeded sample of 2 000 rows
+
+
+def _check_lists(got, want, what, rows=None):
+    """indices exactly, d2 to the bit, padding included"""
+    rc, idx, d2 = got
+    _need(rc == _lib.OK, what, "status", rc)
+    if rows is not None:
+        _need(idx.shape[0] > rows[-1], what, "rows", idx.shape)
+        idx, d2 = idx[rows], d2[rows]
+    widx, wd2 = want
+    _need(idx.shape == widx.shape and d2.shape == wd2.shape, what, "shapes", idx.shape, d2.shape, "reference", widx.shape)
+    _need(np.array_equal(idx, widx), what, "indices differ in rows", np.nonzero((idx != widx).any(axis=1))[0][:10])
+    _need(same_bits(d2, wd2), what, "d2 differs in rows", np.nonzero((bits(d2) != bits(wd2)).any(axis=1))[0][:10])
+
+
+def _step_read(model, device, step):
+    """neighbours, query, count_within: the restated rows exactly; on an empty handle the status query.hip and outlier.hip
+    document (ICP_EMPTY_DST)"""
+    op, m = step["op"], model.m
+    if op == "neighbours":
+        k, first, count = step["k"], step["first"], step["count"]
+        got = device.neighbours(k, first, count)
+        if m == 0:
+            _need(got[0] == _lib.EMPTY_DST, "neighbours on an empty handle: status", got[0])
+            return
+        _check_lists(got, lists_of(model.cloud, k, first, m - first if count is None else count), f"neighbours k={k}")
+        return
+    n = step["n"]
+    q, T = (None, None) if n is None else make_read_queries(model.cloud, n, step["seed"], step.get("pose"))
+    if op == "count_within":
+        rc, counts = device.count_within(q, step["radius"], step["cap"], T)
+        if m == 0:
+            _need(rc == _lib.EMPTY_DST, "count_within on an empty handle: status", rc)
+            return
+        _need(rc == _lib.OK, "count_within: status", rc)
+        want = count_within_ref(model.cloud, q, step["radius"], step["cap"], T)
+        counts = np.asarray(counts)
+        _need(np.array_equal(counts, want), "count_within differs at", np.nonzero(counts != want)[0][:10])
+        return
+    k, order = step["k"], step.get("order")
+    got = device.query(q, k, T, order)
+    if m == 0:
+        _need(got[0] == _lib.EMPTY_DST, "query on an empty handle: status", got[0])
+        return
+    rows = None
+    if n > RESTATE_ROWS:
+        ends = np.concatenate([np.arange(64), np.arange(n - 64, n)])
+        middle = np.random.default_rng(step["seed"]).choice(np.arange(64, n - 64), 2_000, replace=False)
+        rows = np.unique(np.concatenate([ends, middle]))
+    _check_lists(got, query_lists(model.cloud, q if rows is None else q[rows], k, T), f"query k={k} n={n} order={order}", rows)
+    if order == "cell":  # ... and in full, byte for byte, the same call in the caller's order
+        rc, idx, d2 = device.query(q, k, T, "caller")
+        _need(rc == _lib.OK, "query in the caller's order: status", rc)
+        _need(idx.tobytes() == got[1].tobytes() and d2.tobytes() == got[2].tobytes(), "the cell-ordered query differs from the "
+              "same call in the caller's order")
+
+
 def sample_rows(rows, count, seed):
     """both ends of `rows` and a seeded sample of the middle: about `count` rows, ascending"""
     ends = np.concatenate([rows[:LINE_ENDS], rows[-LINE_ENDS:]])
@@ -521,15 +750,14 @@ def apply_step(models, devices, step):
     if op == "append":
         pts = make_cloud(model.dim, step["k"], step["seed"], step.get("shift", (0.0, 0.0)))
         T = I.Transform(step["pose"]) if step.get("pose") is not None else None
+        if step.get("clip"):  # the points as they arrive in the cloud, handed over as they are
+            pts, T = appended_points(model, step), None
         model.append(moved(pts, T) if T is not None else pts)
         device.append(pts.copy(), T)
-    elif op == "crop":
-        radius = INF if step["radius"] == "inf" else step["radius"]
-        mask = keep_mask(model.cloud, step["center"], radius)
-        removed, index = device.crop(step["center"], radius)
-        _need(removed == len(mask) - mask.sum(), "crop removed", removed, "model", len(mask) - mask.sum())
-        _need(np.array_equal(index, new_index_of(mask)), "crop: the index map differs")
-        model.crop(mask)
+    elif op in REMOVALS:
+        _step_removal(model, device, step)
+    elif op in READS:
+        _step_read(model, device, step)
     elif op == "reserve":
         device.reserve(step["capacity"])
     elif op == "set_nn_mode":
@@ -579,19 +807,33 @@ def run(device, steps, seed=None, on_step=None):
 PROFILES = {
     "gpu": dict(m_create=(7_800, 1_500, 24_000, 5_000), m_later=(1_800, 9_000, 5_000), near=(7_000, 8_192), m_max=30_000,
                 n_sizes=(513, 1, 1_024, 64, 5_000, 2, 1_025, 63, 512, 65, 511), n_big=70_000, n_poison=1_025,
-                nq=2_000),
+                nq=2_000,
+                # the map sequences: a cloud a thin takes below near[1] and one a filter does; the large cloud; the second
+                # life's; where the quadratic restatements end (QUADRATIC_MAX_M) and where the full-range reads do
+                m_cross=(8_700, 8_250), m_stay=9_600, m_big=24_000, m_second=(1_800, 2_400, 3_000), quad_max=QUADRATIC_MAX_M,
+                full_max=4_500, q_sizes=(2_000, 1, 64, 63, 65)),
     # the reduced profile of tests/test_handle_model.py: the same generator, every size scaled below the thresholds
     "cpu": dict(m_create=(1_300, 400, 2_600, 900), m_later=(500, 1_500, 900), near=(1_200, 1_400), m_max=3_000,
                 n_sizes=(513, 1, 1_024, 64, 1_200, 2, 1_025, 63, 512, 65, 511), n_big=1_200, n_poison=257,
-                nq=300),
+                nq=300,
+                m_cross=(1_480, 1_430), m_stay=1_640, m_big=2_600, m_second=(500, 700, 900), quad_max=2_000, full_max=1_000,
+                q_sizes=(300, 1, 64, 63, 65)),
 }
 # what follows a change of the cloud, in rotation (a form that needs current normals is preceded by what makes them so)
 FORMS = ("nn_search", "estimate", "normal", "evaluate_inf", "estimate_half", "evaluate_normal_half", "poison_estimate",
          "normal_half", "estimate_inf", "evaluate_half", "reserve", "normal_inf", "poison_normal", "evaluate_normal_inf",
          "set_nn_mode", "poison_evaluate", "poison_gated", "poison_evaluate_normal")
 NORMALS_K = (8, 10, 6)
+# the second rotation, of the map sequences: the reads through the grid (and their poisoned forms)
+MAP_READS = ("neighbours", "query", "count_cap", "query_pose", "poison_query", "count", "poison_count")
+K_VALUES = (8, 1, 16, 17, 32)  # both kernel widths of the lists (KMAX 16 and 32) and their edges
+MASK_FORMS = (("host", "bool"), ("device", "uint8"), ("host", "uint8"), ("device", "bool"))
+FILTERS = ("radius_filter", "stat_filter")
+READ_POSE = [0.03, -0.02, 0.01]
+READ_POISON_N = 257  # the points of a poisoned read: four waves and one point
 # the sequences tests/test_gpu_sequences.py runs, and tests/test_handle_model.py asserts the coverage conditions over
 GPU_DIMS, GPU_SEEDS, GPU_INTERLEAVED_SEEDS = (3, 2), tuple(range(6)), tuple(range(3))
+GPU_MAP_SEEDS, GPU_MAP_INTERLEAVED_SEEDS = tuple(range(6)), tuple(range(2))
 CENTER = {3: (1.0, -1.0), 2: (1.0, 0.0)}
 
 
@@ -604,10 +846,19 @@ class _Generator:
         self.slot = slot
         self.form = {"create": (2 * slot + 5) % len(FORMS), "append": (2 * slot) % len(FORMS),
                      "crop": (2 * slot + len(FORMS) // 2) % len(FORMS)}
+        for at, kind in enumerate(("thin", "remove", "filter")):  # (the map sequences: the old rotation after the new removals)
+            self.form[kind] = (2 * slot + 3 + 5 * at) % len(FORMS)
+        self.read_form = {kind: (3 * slot + at) % len(MAP_READS)
+                          for at, kind in enumerate(("create", "append", "crop", "thin", "remove", "filter"))}
+        self.new_turn = {kind: (slot + at) % 2 == 0
+                         for at, kind in enumerate(("create", "append", "crop", "thin", "remove", "filter"))}
         self.last = "create"
         self.size = (3 * seed + (4 if dim_start == 2 else 0)) % len(self.P["n_sizes"])
         self.lives = 0
         self.model = None
+        self.reads = self.masks = 0
+        self.targets_done = set()
+        self.borrowed = False
 
     def emit(self, op, **kw):
         step = {"op": op, **kw}
@@ -624,20 +875,21 @@ class _Generator:
         return self.P["n_sizes"][self.size]
 
     # -- the cloud
-    def create(self, dim, m, first):
+    def create(self, dim, m, first, borrowed=None):
         seed = self.sub()
-        self.emit("create", dim=dim, m=m, seed=seed, borrowed=bool(first and self.seed % 2 == 1), trim=bool(first))
+        self.borrowed = bool(first and self.seed % 2 == 1) if borrowed is None else bool(borrowed)
+        self.emit("create", dim=dim, m=m, seed=seed, borrowed=self.borrowed, trim=bool(first))
         self.model = Model(dim, make_cloud(dim, m, seed))
         self.lives += 1
         self.last = "create"
 
-    def append(self, kind):
+    def append(self, kind, clip=False):
         mo, lo_hi = self.model, self.P["near"]
         if mo.m == 0:
             k, shift = self.P["m_later"][self.seed % 3], (0.0, 0.0)
-        elif lo_hi[0] <= mo.m < lo_hi[1]:   # across the threshold
+        elif lo_hi[0] <= mo.m < lo_hi[1] or (kind == "up" and mo.m < lo_hi[1]):   # across the threshold
             k, shift = lo_hi[1] - mo.m + mo.m // 12, (0.0, 0.0)
-        elif kind == "incremental":         # inside the box of the last build and below 1.5 x its size
+        elif kind in ("incremental", "up"):         # inside the box of the last build and below 1.5 x its size
             k, shift = max(mo.m // 8, 64), (0.0, 0.0)
         elif kind == "outside":             # beyond the box: the grid is rebuilt
             k, shift = max(mo.m // 8, 64), (1.5, -0.75)
@@ -646,10 +898,13 @@ class _Generator:
         k = min(k, max(self.P["m_max"] - mo.m, 64))
         seed = self.sub()
         pose = [0.02, -0.01, 0.005] if self.rng.random() < 0.4 else None
-        self.emit("append", k=k, seed=seed, shift=shift, pose=pose)
-        pts = make_cloud(mo.dim, k, seed, shift)
-        mo.append(moved(pts, I.Transform(pose)) if pose else pts)
+        if clip:  # (a map sequence's incremental append: surely inside the grid's box, so that the path can be predicted)
+            step = self.emit("append", k=k, seed=seed, shift=shift, pose=pose, clip=True)
+        else:
+            step = self.emit("append", k=k, seed=seed, shift=shift, pose=pose)
+        mo.append(appended_points(mo, step))
         self.last = "append"
+        self.borrowed = False
 
     def crop(self, kind):
         mo, lo_hi = self.model, self.P["near"]
@@ -666,7 +921,7 @@ class _Generator:
                 keep = min(keep, 0.85)
             radius = float(d[int(keep * (len(d) - 1))])
         self.emit("crop", center=[center[0], center[1]], radius=radius)
-        mo.crop(keep_mask(mo.cloud, center, INF if radius == "inf" else radius))
+        mo.keep_rows(keep_mask(mo.cloud, center, INF if radius == "inf" else radius))
         self.last = "crop"
 
     def normals(self, wrong_k=False):
@@ -730,6 +985,258 @@ class _Generator:
         self.emit("normal_estimate", n=self.n(), seed=self.sub(), iters=3, r="half" if self.seed % 2 else None)
 
 
+def thin_size(cloud, share):
+    """the voxel size whose restated mask keeps about `share` of `cloud`: bisected, since the 2-D outline and the 3-D room
+    thin at quite different sizes"""
+    lo, hi = 1e-4, 8.0
+    for _ in range(22):
+        mid = float(np.sqrt(lo * hi))
+        lo, hi = (mid, hi) if thin_mask(cloud, mid).mean() > share else (lo, mid)
+    return float(np.float32(np.sqrt(lo * hi)))
+
+
+class _MapGenerator(_Generator):
+    """the same generator with the four newer removals and the second rotation of forms, the reads through the grid"""
+
+    # -- parameters from the model's cloud
+    def thin_size(self, share):
+        return thin_size(self.model.cloud, share)
+
+    def kth_d2(self, k, rows=512):
+        """the restated d2 to the k-th nearest target (itself included) of a seeded sample of rows"""
+        c = self.model.cloud
+        if len(c) <= rows:
+            return lists_of(c, k)[1][:, k - 1]
+        block = rows // 8  # (eight blocks spread over the cloud: its rows come wall by wall)
+        firsts = (np.arange(8) * (len(c) - block)) // 7
+        jitter = int(self.rng.integers(0, block))
+        return np.concatenate([lists_of(c, k, max(int(f) - jitter, 0), block)[1][:, k - 1] for f in firsts])
+
+    def filter_radius(self, need, share):
+        """a radius that keeps about `share`: that quantile of the restated distance to the need-th neighbour"""
+        return float(np.sqrt(np.quantile(self.kth_d2(need), share)))
+
+    # -- the removals
+    def removal(self, kind, how):
+        """`how`: "moving" (keeps about 0.88: at least 1 / 1.5 of what the grid was built for), "rebuild" (about 0.5),
+        "light" (a radius filter that keeps about 0.94: a grid stays a grid),
+        "nothing", "everything", "handful" (a mask that keeps 3 to 12 targets)"""
+        mo = self.model
+        if kind in FILTERS and mo.m > self.P["quad_max"]:
+            kind = "thin" if how in ("moving", "rebuild") else "remove"
+        if kind == "stat_filter" and how not in ("moving", "nothing"):  # (the rule reaches no other share)
+            kind = "radius_filter"
+        if kind == "thin" and how in ("everything", "handful"):
+            kind = "remove"
+        share = {"moving": 0.88, "rebuild": 0.5, "light": 0.94}.get(how)
+        if kind == "crop":
+            self.crop(how)
+            return
+        if kind == "thin":
+            step = self.emit("thin", v=1e-9 if how == "nothing" else self.thin_size(share))
+        elif kind == "remove":
+            entry, dtype = MASK_FORMS[(self.slot + self.masks) % 4]
+            self.masks += 1
+            share = {"nothing": 1.0, "everything": 0.0, "handful": 7.0 / max(mo.m, 1)}.get(how, share)
+            while True:
+                seed = self.sub()
+                kept = int((make_mask(mo.m, share, seed, dtype) != 0).sum())
+                if how != "handful" or 3 <= kept <= 12:
+                    break
+            step = self.emit("remove", share=share, seed=seed, entry=entry, dtype=dtype)
+        elif kind == "radius_filter":
+            if how == "everything":
+                step = self.emit("radius_filter", radius=0.01, need=mo.m + 1)
+            elif how == "nothing":
+                step = self.emit("radius_filter", radius=0.0, need=1)
+            else:
+                need = 9 if how == "rebuild" else 5
+                step = self.emit("radius_filter", radius=self.filter_radius(need, share), need=need)
+        else:
+            step = self.emit("stat_filter", k=8, ratio="inf" if how == "nothing" else 1.0)
+        mask, _ = removal_mask(mo.cloud, step)
+        if mask.sum() < len(mask):
+            self.borrowed = False
+        mo.keep_rows(mask)
+        self.last = "filter" if kind in FILTERS else kind
+
+    def crop(self, kind):
+        super().crop(kind)
+        self.borrowed = False
+
+    # -- what follows
+    def read(self, name=None):
+        """the next form of the second rotation after the last change of the cloud (or the form `name`)"""
+        mo, P = self.model, self.P
+        if name is None:
+            name = MAP_READS[self.read_form[self.last]]
+            self.read_form[self.last] = (self.read_form[self.last] + 1) % len(MAP_READS)
+        k = K_VALUES[(self.slot + self.reads) % len(K_VALUES)]
+        n = P["q_sizes"][(2 * self.slot + self.reads) % len(P["q_sizes"])]
+        self.reads += 1
+        if name == "neighbours":
+            if mo.m <= P["full_max"]:
+                first, count = 0, None
+            else:  # both ends and one in the middle
+                count = min(SUB_ROWS, mo.m)
+                first = (0, mo.m - count, (mo.m - count) // 2)[self.reads % 3]
+            self.emit("neighbours", k=k, first=first, count=count)
+        elif name in ("query", "query_pose"):
+            self.emit("query", n=n, k=k, seed=self.sub(), pose=READ_POSE if name == "query_pose" else None)
+        elif name.startswith("count"):
+            radius = float(np.sqrt(np.median(self.kth_d2(8, 64))))
+            self.emit("count_within", n=None if name == "count_targets" else n, radius=radius,
+                      cap=5 if name == "count_cap" else None, seed=self.sub(),
+                      pose=READ_POSE if name == "count" and self.reads % 2 else None)
+        else:  # a poisoned read, and the checked call that has to be right after it
+            if name == "poison_query":
+                self.emit("poisoned", kind="query", n=READ_POISON_N, seed=self.sub(), iters=2, k=k)
+            else:
+                radius = float(np.sqrt(np.median(self.kth_d2(8, 64))))
+                self.emit("poisoned", kind="count_within", n=READ_POISON_N, seed=self.sub(), iters=2, radius=radius, cap=None)
+            self.emit("estimate", n=self.n(), seed=self.sub(), iters=3, r=None)
+
+    def follow(self):
+        """after a change of the cloud: the next form of the old rotation or the next two of the new one (the reads are
+        cheap), alternately"""
+        if self.model.m == 0:
+            return
+        new = self.new_turn[self.last]
+        self.new_turn[self.last] = not new
+        if new:
+            # the counts around the targets themselves are quadratic in m to restate: once per generator after each kind of
+            # change, at the first cloud small enough
+            if self.last not in self.targets_done and self.model.m <= self.P["full_max"]:
+                self.targets_done.add(self.last)
+                self.read("count_targets")
+            else:
+                self.read()
+            self.read()
+        else:
+            self.check()
+
+    def noops(self, kinds):
+        """on a borrowed cloud: removals that remove nothing (an all-ones mask, a huge ratio, a tiny voxel), each followed"""
+        for kind in kinds:
+            self.removal(kind, "nothing")
+            self.follow()
+
+    def stale_removal(self, kind):
+        """normals, an append, a removal on the stale cloud, the refused normal call, the update, the normal estimate"""
+        if self.model.stale:
+            self.normals()
+        self.append("incremental", clip=True)
+        self.removal(kind, "moving")
+        self.emit("normal_estimate", n=self.n(), seed=self.sub(), iters=2, r=None if self.seed % 2 else "half")
+        self.normals()
+        self.emit("normal_estimate", n=self.n(), seed=self.sub(), iters=3, r="half" if self.seed % 2 else None)
+
+    def empty_removals(self):
+        """every removal on the handle another removal has just emptied: nothing to remove, an empty map, statistics of +0.0
+        -- with the grid unbuilt (m_full = 0) and the marks' scratch still sized for the old cloud"""
+        assert self.model.m == 0
+        self.emit("thin", v=0.05)
+        self.emit("remove", share=1.0, seed=self.sub(), entry="host", dtype="bool")
+        self.emit("remove", share=1.0, seed=self.sub(), entry="device", dtype="uint8")
+        self.emit("radius_filter", radius=0.1, need=3)
+        self.emit("stat_filter", k=8, ratio=1.0)
+        self.emit("crop", center=list(CENTER[self.model.dim]), radius=1.0)
+        self.last = "crop"
+
+    def snapshot_query_snapshot(self):
+        """a query of n_big points, its lanes forced into cell order, between two snapshot estimates of n_big points"""
+        self.emit("estimate", n=self.P["n_big"], seed=self.sub(), iters=3, r=None)
+        self.emit("query", n=self.P["n_big"], k=8, seed=self.sub(), pose=READ_POSE, order="cell")
+        self.emit("estimate", n=self.P["n_big"], seed=self.sub(), iters=3, r=None)
+
+
+def _map_first_life(g, dim, v, big_query):
+    """create -> [no-op removals on a borrowed cloud] -> a chain of moves (removal, incremental append, removal; for the
+    smaller clouds down across the threshold and back up) -> a rebuild -> a removal on stale normals -> the end: everything
+    removed, a refused read, an append, a removal down to a handful and a list longer than the cloud (even v), or one more
+    removal (odd v) -> close.  Every change of the cloud is followed by a form."""
+    P = g.P
+    big, by_filter = v % 3 == 0, v in (1, 5)
+    # one life's filter starts well above the threshold and leaves a grid a grid (one more quadratic restatement: once)
+    stays = v == 1 and dim == 3 and g.key is None
+    m = P["m_big"] if big else (P["m_stay"] if stays else P["m_cross"][1 if by_filter else 0])
+    g.create(dim, m, True, borrowed=bool(big and g.seed % 2))
+    g.follow()
+    if g.borrowed:
+        g.noops(("remove", "thin"))
+    if big:
+        first, second = "thin", ("remove", "crop")[v // 3 % 2]
+    else:
+        first, second = (FILTERS[v // 3 % 2] if by_filter else "thin"), ("crop", "remove")[v % 2]
+    g.removal(first, "light" if stays else "moving")
+    g.follow()
+    g.append("incremental" if big else "up", clip=True)
+    g.follow()
+    g.removal(second, "moving")
+    g.follow()
+    if big_query:
+        g.snapshot_query_snapshot()
+    g.removal({0: "remove", 1: "thin", 2: "remove", 3: "thin", 4: "crop", 5: "thin", 6: "crop"}[v], "rebuild")
+    g.follow()
+    g.stale_removal({0: "thin", 1: "stat_filter", 2: "radius_filter", 3: "remove", 4: "stat_filter", 5: "radius_filter",
+                     6: "thin"}[v])
+    g.follow()
+    if v % 2 == 0:
+        g.removal({0: "remove", 2: "radius_filter", 4: "crop", 6: "remove"}[v], "everything")
+        refused = v // 2 % 3  # the read an empty handle refuses
+        if refused == 0:
+            g.emit("query", n=64, k=8, seed=g.sub(), pose=None)
+        elif refused == 1:
+            g.emit("neighbours", k=8, first=0, count=None)
+        else:
+            g.emit("count_within", n=64, radius=0.1, cap=None, seed=g.sub(), pose=None)
+        g.empty_removals()
+        g.append("grow")
+        g.follow()
+        g.removal("remove", "handful")
+        g.emit("query", n=64, k=(32, 17)[v // 2 % 2], seed=g.sub(), pose=None)
+    else:
+        g.removal(("thin", "remove", "crop")[v // 2 % 3], "moving")
+        g.follow()
+    g.emit("close")
+
+
+def _map_second_life(g, dim, v):
+    """the handle that takes the first one's buffers from the pool: borrowed for an even v, with the no-op removals"""
+    g.create(dim, g.P["m_second"][g.seed % 3], False, borrowed=v % 2 == 0)
+    g.follow()
+    if g.borrowed:
+        g.noops(("remove", "stat_filter", "thin"))
+    g.removal(("radius_filter", "thin", "stat_filter", "remove")[v % 4], "moving")
+    g.follow()
+    g.append("incremental", clip=True)
+    g.follow()
+    g.removal(("crop", "radius_filter", "remove", "thin")[v % 4], "rebuild")
+    g.follow()
+    g.emit("close")
+
+
+def map_sequence(seed, profile="gpu", dim_start=3):
+    """The steps of one random map sequence: like sequence(), with thin, remove (by mask), the two outlier filters,
+    neighbours, query and count_within in the mix.  Deterministic: the same arguments give the same list."""
+    g = _MapGenerator(seed, profile, dim_start)
+    other = dim_start if seed % 2 == 0 else 5 - dim_start
+    v = seed + (dim_start == 2)
+    _map_first_life(g, dim_start, v, big_query=seed == 0 and dim_start == 3)
+    _map_second_life(g, other, v)
+    return g.steps
+
+
+def map_interleaved(seed, profile="gpu"):
+    """a 3-D and a 2-D map handle alive together, as interleaved()"""
+    gens = []
+    for key, dim in ((0, 3), (1, 2)):
+        g = _MapGenerator(seed + 200, profile, dim, key=key)
+        _map_first_life(g, dim, 2 * seed + key + 1, big_query=False)
+        gens.append(g.steps)
+    return _shuffled(gens, np.random.default_rng([seed, 78]), profile)
+
+
 def _first_life(g, dim, m, v):
     """the handle a sequence starts with: changes of the cloud, each followed by the next form of its rotation"""
     g.create(dim, m, True)
@@ -789,7 +1296,11 @@ def interleaved(seed, profile="gpu"):
         g = _Generator(seed + 100, profile, dim, key=key)
         _first_life(g, dim, P["m_create"][(seed + key + 1) % 4], seed + key + 1)
         gens.append(g.steps)
-    rng = np.random.default_rng([seed, 77])
+    return _shuffled(gens, np.random.default_rng([seed, 77]), profile)
+
+
+def _shuffled(gens, rng, profile):
+    """the two handles' steps alternating at random, each list in its own order, free-function calls thrown in"""
     out, at = [], [0, 0]
     while at[0] < len(gens[0]) or at[1] < len(gens[1]):
         left = [len(gens[k]) - at[k] for k in (0, 1)]
@@ -818,14 +1329,31 @@ def form_of(step, stale):
         return "normals_update" if step["update"] else "normals_compute"
     if op == "poisoned":
         return "poisoned_" + step["kind"]
+    if op == "query":
+        return "query_pose" if step.get("pose") is not None else "query"
+    if op == "count_within":
+        return "count_targets" if step["n"] is None else ("count_cap" if step["cap"] is not None else "count")
     return op
+
+
+def _append_moves(mo, m_full, step, k):
+    """whether an append moves the grid's sorted records (append_grid in nn_grid.hip): True / False where the step decides
+    it, None where it hangs on whether every point lies within half a cell of the box"""
+    if mo.m == 0 or m_full == 0 or mo.m + k > 1.5 * m_full or tuple(step.get("shift", (0.0, 0.0))) != (0.0, 0.0):
+        return False
+    return True if step.get("clip") else None
+
+
+def removal_moves(kept, m_full):
+    """whether a removal that removed something moves the grid's sorted records (remove_marked_targets in crop.hip)"""
+    return kept > 0 and m_full > 0 and not (kept < m_full / 1.5)
 
 
 def trace(steps):
     """One record per step, computed by running the Model alone (no reference, no device): its number, its form,
     `after` -- the last change of the cloud in its handle's life ("create", "append", "crop"; for a create, that of the
     life closed before it) --, the target counts before and after, the source size, and whether the normals were stale."""
-    models, last, out = {}, {}, []
+    models, last, out, m_full, removed = {}, {}, [], {}, {}
     for no, step in enumerate(steps):
         key, op = step.get("h", 0), step["op"]
         mo = models.get(key)
@@ -837,16 +1365,28 @@ def trace(steps):
         rec.update(m_before=mo.m if mo is not None else 0, stale=mo.stale if mo is not None else True,
                    dim_before=mo.dim if mo is not None else None, normals_m_before=mo.normals_m if mo is not None else 0)
         rec["form"] = form_of(step, rec["stale"])
+        rec["removed_before"] = removed.get(key, 0)  # by the last removal, if no append came since
+        if op in READS and rec["m_before"] == 0:
+            rec["form"] = "read_refused"
         if op == "create":
             mo = models[key] = Model(step["dim"], make_cloud(step["dim"], step["m"], step["seed"], scale=step.get("scale", 1.0)))
-            last[key] = "create"
+            last[key], m_full[key], removed[key] = "create", mo.m, 0
+            rec["borrowed"] = bool(step.get("borrowed"))
         elif op == "append":
-            pts = make_cloud(mo.dim, step["k"], step["seed"], step.get("shift", (0.0, 0.0)))
-            mo.append(moved(pts, I.Transform(step["pose"])) if step.get("pose") is not None else pts)
-            last[key] = "append"
-        elif op == "crop":
-            mo.crop(keep_mask(mo.cloud, step["center"], INF if step["radius"] == "inf" else step["radius"]))
-            last[key] = "crop"
+            pts = appended_points(mo, step)
+            rec["moved"] = _append_moves(mo, m_full.get(key, 0), step, len(pts))
+            mo.append(pts)
+            if rec["moved"] is False:
+                m_full[key] = mo.m
+            last[key], removed[key] = "append", 0
+        elif op in REMOVALS:
+            mask = removal_mask(mo.cloud, step)[0]
+            kept = int(mask.sum())
+            rec["moved"] = removal_moves(kept, m_full[key]) if kept < len(mask) else None  # (None: nothing removed)
+            if rec["moved"] is False:
+                m_full[key] = kept
+            mo.keep_rows(mask)
+            last[key], removed[key] = ("filter" if op in FILTERS else op), len(mask) - kept
         elif op == "normals":
             if step["update"] and mo.normals_m > 0 and mo.normals_k != step["k"]:
                 rec["form"] = "normals_refused"

@@ -1,7 +1,8 @@
 """One handle through every kind of call, in arbitrary order, on the GPU: the sequences of tests/handle_model.py
 driven through Icp2d / Icp3d and held, step by step, to the references of the single-call tests.  What is held: a
-handle's answer depends on the cloud and the normals it holds, never on how it got there -- appends, crops, the engine
-asked for, a reserve, earlier calls, a poisoned call, the previous owner of its pooled buffers.
+handle's answer depends on the cloud and the normals it holds, never on how it got there -- appends, crops, thins,
+removals by mask, outlier filters, the engine asked for, a reserve, earlier calls and reads, a poisoned call, the previous
+owner of its pooled buffers.
 
 A failure prints the seed, the step and the step list up to there; handle_model.run(GpuDevice(), steps[:k]) replays a
 prefix.  tests/test_handle_model.py asserts, without a GPU, what these seeds cover and that the checker sees a wrong
@@ -50,11 +51,30 @@ class GpuDevice:
         loop (which counts as windows started) or the short pipeline, and launched a loop or placed a bet.  Which of
         these, and whether a window misses or a bet holds, follows from the residuals' statistics and from how the
         handle's previous call (or its previous owner's) ended: no fixed figure can be asserted for them;
-      * icp_nn_cert_counters: never moved by a call that takes no snapshot."""
+      * icp_nn_cert_counters: never moved by a call that takes no snapshot.
+    Per change of the cloud:
+      * a removal that removed something moves exactly one counter, of its own pair (crop_counters, thin_counters,
+        remove_counters, outlier_counters); one that removed nothing moves none and leaves a borrowed tensor borrowed;
+      * moved or rebuilt is PREDICTED from `m_full`, the number of targets the grid was last fully built for.  build_grid
+        has five callers (icp_rust_amd/csrc): create_common (api.hip); append_common where append_grid did not move the
+        records (api_ext.hip; counted as an append that rebuilt); remove_marked_targets where the records were not moved
+        (crop.hip, behind all five removals; counted in the removal's "rebuilt" counter); and the two error paths of those
+        that put the old cloud back, which a passing sequence never takes.  So m_full is m at create and after every step
+        whose "rebuilt" counter moved; reserve, set_nn_mode, the normals, the searches, the estimates and the reads never
+        reset it.  A removal moves the records exactly when kept > 0 and kept >= m_full / 1.5; an append exactly when
+        m + k <= 1.5 * m_full and every point is within half a cell of the box of the last full build -- asserted where
+        the points are inside that box (moved) or beyond it by more than half its largest extent, which no cell exceeds
+        (rebuilt).  The counters name the path and the pair; they cannot name which scratch or which second buffer a
+        launch used: that is held by the bytes that come back.
+    Per read: query_counters moves by one, on the side query_order names (cell order beyond 65 536 points when forced or
+    from 250 000 on, and always for the counts around the targets themselves); neighbours moves neither."""
 
     def __init__(self):
         self.icp = self.tensor = self.original = None
-        self.calls = 0
+        self.calls = self.m_full = 0
+        self.box = None
+        self.borrowing = False
+        self.changes = []  # (op, moved) per change of the cloud that moved a counter
         # (calls served per path; appends / crops as (records moved, grid rebuilt); gn_path_counters summed as they are)
         self.paths = {"single launch": 0, "general": 0, "snapshot order": 0, "appends": [0, 0], "crops": [0, 0],
                       "certificate searches": 0, "gn paths": [0] * 6, "loop": [0] * 3}
@@ -75,6 +95,26 @@ class GpuDevice:
             self.icp = cls(self.tensor)
         else:
             self.icp = cls(cloud)
+        self.borrowing = bool(borrowed)
+        self._rebuilt(cloud)
+
+    def _rebuilt(self, cloud=None):
+        """the grid was fully built for the cloud as it is"""
+        cloud = self.icp.read_targets() if cloud is None else cloud
+        self.m_full = len(cloud)
+        self.box = (cloud.min(axis=0), cloud.max(axis=0)) if len(cloud) else None
+
+    def _still_borrows(self):
+        """the handle reads the caller's tensor: a value written there shows in read_targets (and is put back)"""
+        import torch
+
+        was = float(self.original[0, 0])
+        self.tensor[0, 0] = was + 1.0
+        torch.cuda.synchronize()
+        seen = self.icp.read_targets(0, 1)[0, 0]
+        self.tensor[0, 0] = was
+        torch.cuda.synchronize()
+        return seen == was + 1.0
 
     def close(self):
         if self.icp is not None:
@@ -105,24 +145,130 @@ class GpuDevice:
 
     def append(self, points, T=None):
         before = self.icp.append_counters()
+        m_old, k = self.icp.target_count, len(points)
         self.icp.append(points, T)
         after = self.icp.append_counters()
         assert sum(after) == sum(before) + 1, ("append counters", before, after)
-        for k in (0, 1):
-            self.paths["appends"][k] += after[k] - before[k]
+        for j in (0, 1):
+            self.paths["appends"][j] += after[j] - before[j]
         self._borrowed_bytes_unchanged()
+        moved = after[0] == before[0] + 1
+        what = ("append", m_old, k, "m_full", self.m_full, "moved", moved)
+        if not (m_old > 0 and self.m_full > 0 and m_old + k <= 1.5 * self.m_full):
+            assert not moved, what
+        elif self.box is not None:
+            world = H.moved(points, T) if T is not None else points
+            lo, hi = self.box
+            reach = 0.5 * float(np.max(hi - lo))
+            if np.all(world >= lo) and np.all(world <= hi):
+                assert moved, what + ("every point inside the box",)
+            elif np.any(world < lo - reach) or np.any(world > hi + reach):
+                assert not moved, what + ("a point far outside the box",)
+        if not moved:
+            self._rebuilt()
+        self.borrowing = False
+        self.changes.append(("append", moved))
+
+    PAIRS = ("crop", "thin", "remove", "outlier")
+
+    def _removal(self, pair, call):
+        """one removal: its own pair of counters moves by one exactly when something was removed, on the side predicted
+        from m_full; no other pair moves; a borrowed tensor is never written and stays borrowed when nothing was removed"""
+        before = {p: getattr(self.icp, p + "_counters")() for p in self.PAIRS}
+        m_old = self.icp.target_count
+        out = call()
+        removed = out[0]
+        after = {p: getattr(self.icp, p + "_counters")() for p in self.PAIRS}
+        delta = {p: (after[p][0] - before[p][0], after[p][1] - before[p][1]) for p in self.PAIRS}
+        what = (pair, "m", m_old, "removed", removed, "m_full", self.m_full, delta)
+        assert all(delta[p] == (0, 0) for p in self.PAIRS if p != pair), ("another pair of counters moved",) + what
+        self._borrowed_bytes_unchanged()
+        if removed == 0:
+            assert delta[pair] == (0, 0), ("nothing removed, a counter moved",) + what
+            assert self.icp.target_count == m_old
+            if self.borrowing:
+                assert self.icp._keep is self.tensor and self._still_borrows(), ("the handle stopped borrowing",) + what
+            return out
+        kept = m_old - removed
+        predicted = H.removal_moves(kept, self.m_full)
+        assert delta[pair] == ((1, 0) if predicted else (0, 1)), ("moved or rebuilt", "predicted moved", predicted) + what
+        if pair == "crop":
+            for j in (0, 1):
+                self.paths["crops"][j] += delta[pair][j]
+        if not predicted:
+            self._rebuilt()
+        if self.borrowing:
+            assert self.icp._keep is None
+        self.borrowing = False
+        self.changes.append((pair, predicted))
+        return out
 
     def crop(self, center, radius):
-        before = self.icp.crop_counters()
-        removed, index = self.icp.crop(center, radius, return_index=True)
-        after = self.icp.crop_counters()
-        assert sum(after) == sum(before) + (1 if removed else 0), ("crop counters", before, after, removed)
-        for k in (0, 1):
-            self.paths["crops"][k] += after[k] - before[k]
-        self._borrowed_bytes_unchanged()
-        return removed, index
+        return self._removal("crop", lambda: self.icp.crop(center, radius, return_index=True))
+
+    def thin(self, v):
+        return self._removal("thin", lambda: self.icp.thin(v, return_index=True))
+
+    def remove(self, keep, entry):
+        if entry == "device":
+            import torch
+
+            keep = torch.from_numpy(keep).cuda()
+        return self._removal("remove", lambda: self.icp.remove(keep, return_index=True))
+
+    def radius_filter(self, radius, need):
+        return self._removal("outlier", lambda: self.icp.remove_radius_outliers(radius, need, return_index=True))
+
+    def stat_filter(self, k, ratio):
+        return self._removal("outlier", lambda: self.icp.remove_statistical_outliers(k, ratio, return_index=True,
+                                                                                     return_stats=True))
+
+    # -- the reads through the grid
+    def _read(self, side, call):
+        """query_counters moves by one on `side` (0: cell order, 1: the caller's; None: by nothing)"""
+        before = self.icp.query_counters()
+        rc, out = _status(call)
+        after = self.icp.query_counters()
+        want = [0, 0]
+        if rc == _lib.OK and side is not None:
+            want[side] = 1
+        assert [after[0] - before[0], after[1] - before[1]] == want, ("query counters", before, after, side, rc)
+        return rc, out
+
+    @staticmethod
+    def _host(a):
+        """numpy whatever came back; the device entries hand the indices and counts over as int32 bits"""
+        if isinstance(a, np.ndarray):
+            return a
+        a = a.cpu().numpy()
+        return a.view(np.uint32) if a.dtype == np.int32 else a
+
+    def neighbours(self, k, first, count):
+        rc, out = self._read(None, lambda: self.icp.neighbours(k, first, count))
+        return (rc, None, None) if rc != _lib.OK else (rc,) + out
+
+    def query(self, q, k, T=None, order=None):
+        L = I.lib()
+        if order is not None:
+            _lib.check(L.icp_query_force_order(self.icp._h, 1 if order == "cell" else -1), "icp_query_force_order")
+        try:
+            cell = order == "cell" and len(q) > KCOOP or (order is None and len(q) >= 250_000)
+            rc, out = self._read(0 if cell else 1, lambda: self.icp.query(self._src(q), k, T))
+        finally:
+            if order is not None:
+                L.icp_query_force_order(self.icp._h, 0)
+        return (rc, None, None) if rc != _lib.OK else (rc, self._host(out[0]), self._host(out[1]))
+
+    def count_within(self, q, radius, cap=None, T=None):
+        if q is None:
+            rc, out = self._read(0, lambda: self.icp.count_within(None, radius, cap=cap))
+        else:
+            rc, out = self._read(0 if len(q) >= 250_000 else 1, lambda: self.icp.count_within(self._src(q), radius, T, cap=cap))
+        return rc, (None if rc != _lib.OK else self._host(out))
 
     def reserve(self, capacity):
+        if capacity > self.icp.target_count:
+            self.borrowing = False  # (the cloud moves into storage of the handle's own)
         self.icp.reserve(capacity)
 
     def set_nn_mode(self, mode):
@@ -256,6 +402,27 @@ def test_two_handles_interleaved(seed):
     function weighted_gauss_newton_update (the scratch handle) in between, against the oracle's tree-order update"""
     steps = H.interleaved(seed, "gpu")
     assert {s["op"] for s in steps} >= {"free_update", "create", "append", "crop"}
+    run(steps, seed=seed)
+
+
+@pytest.mark.parametrize("seed", H.GPU_MAP_SEEDS)
+@pytest.mark.parametrize("dim_start", H.GPU_DIMS)
+def test_random_map_sequences(dim_start, seed):
+    """the map sequences: append, crop, thin, remove by mask (host and device entry, bool and uint8) and the two outlier
+    filters in one life, each change followed by a form of the old rotation or by reads through the grid (neighbours,
+    query, count_within).  GpuDevice asserts the counters of every removal, append and read."""
+    steps = H.map_sequence(seed, "gpu", dim_start)
+    assert {s["op"] for s in steps} >= {"thin", "remove", "neighbours", "query", "count_within", "append"}
+    run(steps, seed=seed)
+
+
+@pytest.mark.parametrize("seed", H.GPU_MAP_INTERLEAVED_SEEDS)
+def test_two_map_handles_interleaved(seed):
+    """a 3-D and a 2-D map handle alive together: the marks and counts live in each handle's grid, the query workspace
+    is one per device and shared by both"""
+    steps = H.map_interleaved(seed, "gpu")
+    ops = {s["op"] for s in steps}
+    assert ops >= {"free_update", "thin", "remove", "query", "count_within"} and ops & set(H.FILTERS)
     run(steps, seed=seed)
 
 
@@ -399,6 +566,63 @@ def test_both_append_paths_and_both_crop_paths_in_one_life():
     print("counters after each change of the cloud", seen)
     assert seen[1] == ((1, 0), (0, 0)) and seen[4] == ((1, 1), (0, 0))
     assert seen[7] == ((1, 1), (1, 0)) and seen[10] == ((1, 1), (1, 1))
+
+
+def test_four_moves_the_rebuild_m_full_forces_a_filter_back_to_the_sweep_and_a_cell_ordered_query():
+    """One 3-D life.  24 000 targets; a thin, an incremental append and two removals by mask each move the grid's records
+    (m_full stays 24 000); a third mask keeps 85 % -- more than 1 / 1.5 of the cloud it is applied to, less than
+    24 000 / 1.5 -- and so rebuilds; a fourth takes the cloud to about 8 400 (still the grid); a query of 70 000 points
+    forced into cell order sits between two snapshot estimates of 70 000 points; the statistical filter takes the handle
+    back below 8 192 (the sweep: build_target_soa / build_target_screen), and an estimate and a query follow."""
+    mask = dict(op="remove", entry="host", dtype="bool")
+    pose = [0.03, -0.02, 0.01]
+    steps = [{"op": "create", "dim": 3, "m": 24_000, "seed": 81, "trim": True},
+             {"op": "thin", "v": H.thin_size(H.make_cloud(3, 24_000, 81), 0.88)},
+             {"op": "nn_search", "n": 1_500, "seed": 82},
+             {"op": "append", "k": 2_600, "seed": 83, "shift": (0.0, 0.0), "pose": None, "clip": True},
+             {"op": "query", "n": 2_000, "k": 16, "seed": 84, "pose": None},
+             dict(mask, share=0.88, seed=85),
+             {"op": "estimate", "n": 5_000, "seed": 86, "iters": 3, "r": None},
+             dict(mask, share=0.88, seed=87, entry="device", dtype="uint8"),
+             {"op": "count_within", "n": 513, "radius": 0.05, "cap": 5, "seed": 88, "pose": pose},
+             dict(mask, share=0.85, seed=89, dtype="uint8"),
+             {"op": "neighbours", "k": 17, "first": 7_000, "count": 1_024},
+             dict(mask, share=0.54, seed=90, entry="device"),
+             {"op": "estimate", "n": 70_000, "seed": 91, "iters": 3, "r": None},
+             {"op": "query", "n": 70_000, "k": 8, "seed": 92, "pose": pose, "order": "cell"},
+             {"op": "estimate", "n": 70_000, "seed": 93, "iters": 3, "r": None},
+             {"op": "stat_filter", "k": 8, "ratio": 1.0},
+             {"op": "estimate", "n": 513, "seed": 94, "iters": 3, "r": None},
+             {"op": "query", "n": 65, "k": 32, "seed": 95, "pose": pose}]
+    t = H.trace(steps)
+    assert [t[k]["moved"] for k in (1, 3, 5, 7, 9, 11, 15)] == [True, True, True, True, False, False, True]
+    forced = t[9]
+    assert forced["m"] >= forced["m_before"] / 1.5 and forced["m"] < 24_000 / 1.5  # m_full, not the cloud it cut
+    assert KGRID <= t[11]["m"] < 9_000 and 0 < t[15]["m"] < KGRID
+    seen, engines = {}, {}
+    device = GpuDevice()
+
+    def on_step(no, step, models):
+        engines[no] = device.resolved()
+        if step["op"] in H.REMOVALS + ("append",):
+            seen[no] = (device.icp.append_counters(), device.icp.thin_counters(), device.icp.remove_counters(),
+                        device.icp.outlier_counters(), device.icp.crop_counters())
+
+    try:
+        H.run(device, steps, on_step=on_step)
+        queries = device.icp.query_counters()
+    finally:
+        device.close()
+    print("counters after each change of the cloud", seen, "query counters (cell order, caller's order)", queries)
+    # in cell order: the forced query of 70 000; in the caller's: the queries of 2 000 and 65, the counts of 513, and the
+    # 70 000 again, forced the other way
+    assert queries == (1, 4)
+    assert seen[1] == ((0, 0), (1, 0), (0, 0), (0, 0), (0, 0)) and seen[3] == ((1, 0), (1, 0), (0, 0), (0, 0), (0, 0))
+    assert seen[5][2] == (1, 0) and seen[7][2] == (2, 0) and seen[9][2] == (2, 1) and seen[11][2] == (2, 2)
+    assert seen[15] == ((1, 0), (1, 0), (2, 2), (1, 0), (0, 0))
+    assert engines[14] == I.NN_GRID and engines[15] == engines[17] == I.NN_BRUTE
+    snapshots = [c for c in device.log if c["snapshot"]]
+    assert [c["n"] for c in snapshots] == [70_000, 70_000]  # the estimates on both sides of the cell-ordered query
 
 
 def restated_search_plan(cloud, src, iters):

@@ -1,7 +1,10 @@
 """The model, the generator and the checker of the sequence tests (tests/handle_model.py), without a GPU: the generator
 is deterministic; over the exact seeds tests/test_gpu_sequences.py runs, the coverage conditions hold; the checker
 passes a stand-in built from the references themselves and catches five sabotaged ones at the first step where each
-fault can be seen.  This is the only place faults are injected -- into a numpy stand-in, never into the library."""
+fault can be seen.  The same again for the map sequences (thin, remove by mask, the two outlier filters, neighbours,
+query, count_within): the older lists are pinned by digest, the map sequences have coverage conditions of their own, the
+stand-in passes four reduced ones and an interleaved one, and five more sabotaged stand-ins are caught.  This is the
+only place faults are injected -- into a numpy stand-in, never into the library."""
 import collections
 
 import numpy as np
@@ -235,10 +238,10 @@ def failing_step(device, steps):
     return e.value.step
 
 
-def scan_for(pred, what):
+def scan_for(pred, what, make=H.sequence):
     """the first reduced sequence whose trace has a step for the fault to show at"""
     for dim, seed in CPU_RUNS + [(d, s) for s in range(4, 12) for d in (3, 2)]:
-        steps = H.sequence(seed, "cpu", dim)
+        steps = make(seed, "cpu", dim)
         t = H.trace(steps)
         if any(pred(r, t) for r in t):
             return steps, t, first(t, lambda r: pred(r, t))
@@ -287,3 +290,282 @@ def test_a_call_that_repeats_the_indices_from_before_a_poisoned_call_is_caught_r
     steps, t, poisoned = scan_for(pred, "a poisoned call behind a call that returned indices")
     assert t[poisoned + 1]["op"] in ("estimate", "normal_estimate")
     assert failing_step(RepeatsIndicesAfterPoison(), steps) == poisoned + 1
+
+
+# ------------------------------------------------------------------ the old lists are the old lists
+
+# sha256(repr(steps))[:16] of every list the older tests run, computed before the generator learnt the map sequences
+DIGESTS = {
+    ("sequence", 0, "gpu", 3): "ed6c41e1772c4abf", ("sequence", 1, "gpu", 3): "3b3dab612db389cb",
+    ("sequence", 2, "gpu", 3): "98e24e4f2c810de1", ("sequence", 3, "gpu", 3): "8967759b624e1e52",
+    ("sequence", 4, "gpu", 3): "761c0640ef8bad44", ("sequence", 5, "gpu", 3): "4c990a545074b27a",
+    ("sequence", 0, "gpu", 2): "c8dd8b17aeb03984", ("sequence", 1, "gpu", 2): "37f9031b0eec73a3",
+    ("sequence", 2, "gpu", 2): "2315614c45455931", ("sequence", 3, "gpu", 2): "e0192c71a54799b0",
+    ("sequence", 4, "gpu", 2): "b37b64d8bc89d4f9", ("sequence", 5, "gpu", 2): "ef30634d5abce910",
+    ("interleaved", 0, "gpu"): "0f07248829a21f32", ("interleaved", 1, "gpu"): "288f4ba5a5911670",
+    ("interleaved", 2, "gpu"): "dd94512dc581009b",
+    ("sequence", 0, "cpu", 3): "1cf4435dadc02b52", ("sequence", 1, "cpu", 2): "886675d9828377b2",
+    ("sequence", 2, "cpu", 3): "179aa15fd9f6bdab", ("sequence", 3, "cpu", 2): "d6172159173309e0",
+    ("interleaved", 0, "cpu"): "976305a5d077d3e5",
+}
+
+
+def test_sequence_and_interleaved_return_the_lists_they_returned_before_the_map_sequences():
+    import hashlib
+
+    wanted = ({("sequence", s, "gpu", d) for d in H.GPU_DIMS for s in H.GPU_SEEDS}
+              | {("interleaved", s, "gpu") for s in H.GPU_INTERLEAVED_SEEDS}
+              | {("sequence", s, "cpu", d) for d, s in CPU_RUNS} | {("interleaved", 0, "cpu")})
+    assert wanted == set(DIGESTS)
+    for key, want in DIGESTS.items():
+        steps = H.sequence(key[1], key[2], key[3]) if key[0] == "sequence" else H.interleaved(key[1], key[2])
+        assert hashlib.sha256(repr(steps).encode()).hexdigest()[:16] == want, key
+
+
+# ------------------------------------------------------------------ the map sequences: coverage
+
+NEW_OPS = ("thin", "remove", "radius_filter", "stat_filter", "neighbours", "query", "count_within")
+READ_FORMS = ("neighbours", "query", "query_pose", "count", "count_cap", "count_targets")
+CHANGES = ("create", "append") + H.REMOVALS
+AFTER_REMOVAL = ("crop", "thin", "remove", "filter")
+
+
+def map_lists():
+    return ([H.map_sequence(s, "gpu", d) for d in H.GPU_DIMS for s in H.GPU_MAP_SEEDS] +
+            [H.map_interleaved(s, "gpu") for s in H.GPU_MAP_INTERLEAVED_SEEDS])
+
+
+@pytest.fixture(scope="module")
+def map_traces():
+    """(steps, trace) of every map sequence tests/test_gpu_sequences.py runs"""
+    return [(steps, H.trace(steps)) for steps in map_lists()]
+
+
+def handles(steps, t):
+    """per handle of a list: its (step, record) pairs in order"""
+    out = collections.defaultdict(list)
+    for s, r in zip(steps, t):
+        if r["form"] != "free_update":
+            out[r["h"]].append((s, r))
+    return list(out.values())
+
+
+def test_map_sequences_are_deterministic_plain_data():
+    assert H.map_sequence(2, "cpu", 3) == H.map_sequence(2, "cpu", 3)
+    assert H.map_sequence(2, "cpu", 3) != H.map_sequence(2, "cpu", 2)
+    assert H.map_interleaved(1, "cpu") == H.map_interleaved(1, "cpu")
+    steps = H.map_sequence(1, "cpu", 2)
+    assert eval(repr(steps)) == steps
+
+
+def test_every_new_operation_occurs_five_times_and_every_read_form_after_every_kind_of_change(map_traces):
+    total, after = collections.Counter(), collections.defaultdict(set)
+    for steps, t in map_traces:
+        for r in t:
+            total[r["op"]] += 1
+            after[r["form"]].add(r["after"])
+    print(dict(total), {f: sorted(after[f]) for f in READ_FORMS})
+    for op in NEW_OPS:
+        assert total[op] >= 5, (op, total[op])
+    for f in READ_FORMS:
+        assert {"append", "crop", "thin", "remove", "filter"} <= after[f], (f, after[f])
+    assert total["append"] >= 5 and total["crop"] >= 5
+    for f in ("poisoned_query", "poisoned_count_within"):
+        assert after[f], f
+
+
+def test_list_lengths_query_sizes_and_where_the_quadratic_restatements_stop(map_traces):
+    ks, sizes, padded, big = set(), set(), 0, []
+    for steps, t in map_traces:
+        for s, r in zip(steps, t):
+            if r["op"] in ("neighbours", "query"):
+                ks.add(s["k"])
+                if s["k"] > r["m_before"] > 0 and r["after"] in AFTER_REMOVAL:
+                    assert r["m_before"] <= 12
+                    padded += 1
+            if r["op"] in ("query", "count_within") and s["n"] is not None:
+                sizes.add(s["n"])
+            # the filters up to 12 000 targets only; the full-range lists and the counts around the targets themselves up to
+            # the profile's lower limit
+            if r["op"] in H.FILTERS:
+                assert r["m_before"] <= H.QUADRATIC_MAX_M, (s, r["m_before"])
+            if (r["op"] == "neighbours" and s["count"] is None) or r["form"] == "count_targets":
+                assert r["m_before"] <= H.PROFILES["gpu"]["full_max"] <= H.QUADRATIC_MAX_M, (s, r["m_before"])
+            if r["op"] == "neighbours" and s["count"] is not None:
+                assert s["count"] == H.SUB_ROWS <= 1_024 and s["first"] + s["count"] <= r["m_before"]
+                big.append((s["first"], s["first"] + s["count"] == r["m_before"]))
+            if r["op"] in ("thin", "remove") and r["m_before"] >= 20_000:
+                big.append(r["op"])
+    assert {1, 8, 16, 17, 32} <= ks and padded >= 1
+    assert {1, 63, 64, 65, 2_000} <= sizes
+    assert "thin" in big and "remove" in big  # thin and remove at 20-30 k
+    ranges = [b for b in big if isinstance(b, tuple)]
+    assert any(f == 0 for f, _ in ranges) and any(end for _, end in ranges) and any(f > 0 and not end for f, end in ranges)
+    filters = [r for steps, t in map_traces for r in t if r["op"] in H.FILTERS]
+    assert any(r["m_before"] >= KGRID for r in filters) and any(0 < r["m_before"] < KGRID for r in filters)
+    # ... and one on a grid well above the threshold that removes something and leaves a grid
+    assert any(r["m_before"] >= 9_000 and KGRID <= r["m"] < r["m_before"] for r in filters)
+
+
+def test_every_map_transition_occurs_twice(map_traces):
+    c = collections.Counter()
+    for steps, t in map_traces:
+        for pairs in handles(steps, t):
+            recs = [r for _, r in pairs]
+            # the changes of the cloud, each with whether a read or an estimate came before the next change
+            changes = []
+            for s, r in pairs:
+                if r["op"] in CHANGES:
+                    changes.append([s, r, False])
+                elif changes and r["op"] in H.READS + ("nn_search", "estimate", "normal_estimate", "evaluate"):
+                    changes[-1][2] = True
+            for a, b, d in zip(changes, changes[1:], changes[2:]):
+                if (a[1]["op"] in H.REMOVALS and a[1]["moved"] is True and b[1]["op"] == "append" and b[1]["moved"] is True
+                        and d[1]["op"] in H.REMOVALS and d[1]["moved"] is True and a[2] and b[2] and d[2]):
+                    c["moved removal, incremental append, moved removal"] += 1
+            borrowed = False
+            for at, (s, r) in enumerate(pairs):
+                nxt = recs[at + 1:at + 4]
+                op = r["op"]
+                if op == "create":
+                    borrowed = r["borrowed"]
+                    if r["dim_before"] not in (None, r["dim"]) and recs[at - 1]["op"] == "close" and \
+                            recs[at - 1]["after"] in AFTER_REMOVAL:
+                        c["close after a removal, create of the other dimension"] += 1
+                if op in H.REMOVALS and op != "crop" and 0 < r["normals_m_before"] < r["m_before"] and len(nxt) == 3 and \
+                        nxt[0]["form"] == "stale_refusal" and nxt[1]["form"] == "normals_update" and \
+                        nxt[2]["form"].startswith("normal_estimate"):
+                    c[op + " on stale normals"] += 1
+                if op in H.REMOVALS and r["m_before"] >= KGRID > r["m"] > 0:
+                    c["down by " + ("a filter" if op in H.FILTERS else op)] += 1
+                if op == "append" and r["m_before"] < KGRID <= r["m"]:
+                    c["up by an append"] += 1
+                if op in H.REMOVALS and borrowed and r["m"] == r["m_before"] > 0:
+                    what = {"remove": "all-ones mask", "stat_filter": "huge ratio", "thin": "tiny voxel"}.get(op)
+                    assert op != "remove" or s["share"] == 1.0
+                    assert op != "stat_filter" or s["ratio"] == "inf"
+                    c[f"nothing removed on a borrowed cloud: {what}"] += 1
+                if op in H.REMOVALS and r["m"] == 0 < r["m_before"] and len(nxt) >= 2 and nxt[0]["form"] == "read_refused":
+                    # (the removals on the emptied handle come in between)
+                    rest = [x for x in recs[at + 2:] if not (x["op"] in H.REMOVALS and x["m_before"] == 0)]
+                    if rest and rest[0]["op"] == "append":
+                        c["everything removed, a refused read, an append"] += 1
+                if op in H.REMOVALS and r["m_before"] == 0:
+                    assert r["m"] == 0 and r["after"] in AFTER_REMOVAL
+                    c["on an empty handle: " + (op if op != "remove" else f"remove {s['entry']}")] += 1
+                if op == "remove":
+                    c[f"mask {s['entry']} {s['dtype']}"] += 1
+                    if s["dtype"] == "uint8" and 0 < s["share"] and r["m_before"]:
+                        assert H.make_mask(r["m_before"], s["share"], s["seed"], "uint8").max() > 1
+                if op == "append" or (op in H.REMOVALS and r["m"] < r["m_before"]):
+                    borrowed = False
+    print(dict(c))
+    wanted = (["moved removal, incremental append, moved removal", "close after a removal, create of the other dimension",
+               "down by thin", "down by a filter", "up by an append", "everything removed, a refused read, an append"]
+              + [k + " on stale normals" for k in ("thin", "remove", "radius_filter", "stat_filter")]
+              + [f"nothing removed on a borrowed cloud: {w}" for w in ("all-ones mask", "huge ratio", "tiny voxel")]
+              + [f"mask {e} {d}" for e in ("host", "device") for d in ("bool", "uint8")]
+              + ["on an empty handle: " + k for k in ("thin", "remove host", "remove device", "radius_filter", "stat_filter",
+                                                      "crop")])
+    for what in wanted:
+        assert c[what] >= 2, (what, dict(c))
+
+
+def test_one_cell_ordered_query_sits_between_two_snapshot_estimates(map_traces):
+    found = 0
+    for steps, t in map_traces:
+        for pairs in handles(steps, t):
+            for at, (s, r) in enumerate(pairs):
+                if s.get("order") == "cell":
+                    before, after = pairs[at - 1], pairs[at + 1]
+                    assert s["op"] == "query" and s["n"] == 70_000 and r["m_before"] >= KGRID
+                    for ps, pr in (before, after):  # beyond kGridCoopMaxN on the grid engine: a cell-sorted snapshot
+                        assert ps["op"] == "estimate" and ps["n"] == 70_000 > KCOOP and pr["m_before"] == r["m_before"]
+                    found += 1
+    assert found == 1
+
+
+# ------------------------------------------------------------------ the map checker and a right device
+
+CPU_MAP_RUNS = [(3, 0), (2, 0), (3, 2), (2, 4)]
+
+
+@pytest.mark.parametrize("dim,seed", CPU_MAP_RUNS)
+def test_the_stand_in_passes_the_reduced_map_sequences(dim, seed):
+    steps = H.map_sequence(seed, "cpu", dim)
+    t = H.trace(steps)
+    assert max(r["m"] for r in t) <= 3_000 and max(r.get("n") or 0 for r in t) <= 1_200
+    assert {r["op"] for r in t} >= {"thin", "remove", "neighbours", "query", "count_within"}
+    if (dim, seed) in ((3, 0), (3, 2)):  # these pass through every removal on an emptied handle
+        assert {r["op"] for r in t if r["op"] in H.REMOVALS and r["m_before"] == 0} == set(H.REMOVALS)
+    H.run(H.ReferenceDevice(), steps, seed=seed)
+
+
+def test_two_stand_ins_pass_the_reduced_interleaved_map_sequence():
+    steps = H.map_interleaved(0, "cpu")
+    assert {s.get("h") for s in steps} == {0, 1, None}
+    H.run({0: H.ReferenceDevice(), 1: H.ReferenceDevice()}, steps, seed=0)
+
+
+# ------------------------------------------------------------------ the map checker and five more wrong devices
+
+class ThinKeepsTheLastOfAVoxel(H.ReferenceDevice):
+    def thin_keep(self, cloud, v):
+        return np.ascontiguousarray(H.thin_mask(cloud[::-1], v)[::-1])
+
+
+class AllKeptNormalsCurrent(H.Model):
+    def current(self, mask):
+        return int(mask.sum()) if 0 < self.normals_m < self.m else super().current(mask)
+
+
+class StaleRemovalReportsCurrentNormals(H.ReferenceDevice):
+    model_cls = AllKeptNormalsCurrent
+
+
+class ReadsSearchTheCloudBeforeTheRemoval(H.ReferenceDevice):
+    def searched_cloud(self):
+        return self.model.cloud if self.cloud_before is None else self.cloud_before
+
+
+class RadiusFilterDoesNotCountTheTarget(H.ReferenceDevice):
+    def radius_keep(self, cloud, radius, need):
+        return H.radius_keep(cloud, radius, need + 1)
+
+
+class NewIndexNumbersTheOldRows(H.ReferenceDevice):
+    def index_of(self, mask):
+        return np.where(mask, np.arange(len(mask)), H.GONE).astype(np.uint32)
+
+
+def scan_map_for(pred, what):
+    return scan_for(pred, what, make=H.map_sequence)
+
+
+def test_a_thin_that_keeps_the_last_point_of_a_voxel_is_caught_at_that_thin():
+    steps, t, want = scan_map_for(lambda r, t: r["op"] == "thin" and r["m"] < r["m_before"], "a thin that removes")
+    assert failing_step(ThinKeepsTheLastOfAVoxel(), steps) == want
+
+
+def test_a_removal_on_stale_normals_that_reports_them_current_is_caught_at_that_removal():
+    def pred(r, t):
+        return r["op"] in H.REMOVALS and 0 < r["normals_m_before"] < r["m_before"] and r["m"] > 0
+
+    steps, t, want = scan_map_for(pred, "a removal on stale normals")
+    assert failing_step(StaleRemovalReportsCurrentNormals(), steps) == want
+
+
+def test_a_read_of_the_cloud_from_before_the_last_removal_is_caught_at_that_read():
+    reads = READ_FORMS + ("nn_search", "read_refused", "poisoned_query", "poisoned_count_within")
+    steps, t, want = scan_map_for(lambda r, t: r["form"] in reads and r["removed_before"] > 0, "a read after a removal")
+    assert failing_step(ReadsSearchTheCloudBeforeTheRemoval(), steps) == want
+
+
+def test_a_radius_filter_that_does_not_count_the_target_itself_is_caught_at_that_filter():
+    steps, t, want = scan_map_for(lambda r, t: r["op"] == "radius_filter" and r["m"] > 0, "a radius filter that keeps some")
+    assert failing_step(RadiusFilterDoesNotCountTheTarget(), steps) == want
+
+
+def test_a_new_index_that_numbers_the_old_rows_is_caught_at_the_first_removal_that_removes():
+    steps, t, want = scan_map_for(lambda r, t: r["op"] in H.REMOVALS and 0 < r["m"] < r["m_before"], "a removal")
+    assert failing_step(NewIndexNumbersTheOldRows(), steps) == want
